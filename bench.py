@@ -14,6 +14,10 @@ relays rank 0's line. On a box with fewer than N GPUs the spawned ranks share th
 rehearsal of the control flow, said so in the line); on a real node they use RCCL ("nccl") over xGMI.
 
   python bench.py --workload opt     the reference's demo loop (examples/test_opt_tf.py:33-88) through Raycaster
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step computed (the arrays a caller of the
+                       timed path receives) as DIR/<name>.npy, float32 or float64, at most DUMP_BUDGET_BYTES in all: inputs
+                       are seeded, so two builds run with the same arguments can be compared output for output
 """
 import argparse
 import csv
@@ -34,7 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec
 
 
 def algorithmic_bytes(vol_dtype):
@@ -132,7 +136,12 @@ def parse_args(argv=None):
                     help="roofline.traffic: 'live' collects FETCH_SIZE / WRITE_SIZE with rocprofv3 around short child runs of "
                          "this very command; 'auto' = live for the default single-GPU headline, else off")
     ap.add_argument("--pmc-json", default=None, help="use this per-launch counter file (tools/profile_round.sh) instead")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ N > 1 self-launch
@@ -438,6 +447,36 @@ def emit(line):
     out.flush()
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # data of all --dump-outputs files together (64 MB with room for the .npy headers)
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each tensor of `arrays` ({name: tensor or None}) as directory/<name>.npy, float64 if it is float64,
+    else float32. The smallest arrays are written whole first; an array larger than its even share of what is left of the
+    budget is written as a fixed sample of distinct elements of its flattened form, in index order, as <name>_sample.npy
+    (the indices come from a RandomState seeded with DUMP_SAMPLE_SEED and the array's size: the same on every run).
+    Returns {file name: shape written}."""
+    os.makedirs(directory, exist_ok=True)
+    items = sorted(((k, v.detach()) for k, v in arrays.items() if v is not None), key=lambda kv: kv[1].numel())
+    left, written = budget, {}
+    for i, (name, t) in enumerate(items):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dt == torch.float64 else 4
+        share = left // (len(items) - i)
+        if t.numel() * item <= share:
+            a = t.to(dt).cpu().numpy()
+        else:
+            n = t.numel()
+            idx = np.unique(np.random.RandomState((DUMP_SAMPLE_SEED + n) % 2 ** 32).randint(0, n, size=share // item))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].to(dt).cpu().numpy()
+            name += "_sample"
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+        written[name + ".npy"] = list(a.shape)
+    return written
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -546,7 +585,7 @@ def main():
             return int(steps.sum().item())
         else:
             steps.sum(); n.sum()  # same launches as a timed step
-        return dv, dt
+        return out, steps, dv, dt
 
     def barrier():
         reducer.wait()
@@ -559,11 +598,16 @@ def main():
         step(k, False)
     barrier()
     t0 = time.perf_counter()
-    last = (None, None)
+    last = (None, None, None, None)
     for k in range(args.steps):
         last = step(args.warmup + k, True)
     barrier()
     elapsed_local = time.perf_counter() - t0
+    # (every call of the hot path returns fresh tensors: the untimed steps below leave these as the last timed step made them;
+    #  N > 1: the gradients are the all-reduced ones, the image and sample counts rank 0's own view)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, dict(zip(("image", "sample_counts", "d_volume", "d_tf"), last)))
 
     # N > 1: the number an OPTIMISATION loop would see, next to the overlapped one -- the same steps once more with every
     # step's gradient all-reduce awaited before the next forward starts (a throughput benchmark may hide the
@@ -603,7 +647,7 @@ def main():
     allreduce_ms = None
     allreduce_bytes = None
     if dist is not None and want_bwd:
-        grads = [g for g in last if g is not None]
+        grads = [g for g in last[2:] if g is not None]
         allreduce_bytes = int(sum(g.numel() * g.element_size() for g in grads))
         barrier()
         t1 = time.perf_counter()
@@ -762,6 +806,8 @@ def main():
         "rays_recomputed_sequentially": (int(stats[15]) if stats is not None else None),   # ray_exact_kernel
         "cpu_baseline": cpu_baseline,
     }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     emit(line)
 
 
@@ -841,6 +887,7 @@ def main_opt(args):
             for k, a, b in (("gt", t0, t1), ("fwd", t1, t2), ("bwd", t2, t3), ("opt", t3, t4)):
                 ev[k].append((a, b))
             losses.append(loss.detach())
+        return res
 
     def barrier():
         torch.cuda.synchronize()
@@ -853,9 +900,14 @@ def main_opt(args):
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        iteration(args.warmup + i, True)
+        res = iteration(args.warmup + i, True)
     barrier()
     elapsed = time.perf_counter() - t0
+    # the last iteration's render, loss and (all-reduced) gradients, and the parameters its optimiser step left
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"image": res, "loss": losses[-1], "d_volume": vol.grad, "d_tf": tf.grad,
+                                                  "volume": vol, "tf": tf})
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -885,6 +937,8 @@ def main_opt(args):
         "ms_host_overhead": round(it_ms - gpu_ms, 4),   # wall time per iteration not covered by the GPU phases above
         "loss_first_last": [round(float(losses[0]), 6), round(float(losses[-1]), 6)] if losses else None,
     }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     emit(line)
 
 

@@ -101,3 +101,41 @@ def test_roofline_entry_prices_evaluated_samples_and_refuses_fractions_above_one
     # no counting step (baseline kernels): the marched count, and the guard
     e = B.roofline_entry("march_bwd", 0.34, 96.0, 2.55e8, None, "march_bwd")
     assert e["frac"] is None and e["achieved"] is None and "> 1" in e["frac_refused"] and "marched" in e["frac_kind"]
+
+
+def test_steps_is_the_timed_step_count_and_must_be_positive():
+    """ms_per_step is the time of one timed step: --steps sets how many run, and a run without one is refused."""
+    import pytest
+    B = _bench()
+    a = B.parse_args(["--steps", "7", "--warmup", "3", "--dump-outputs", "out_dir"])
+    assert a.steps == 7 and a.warmup == 3 and a.dump_outputs == "out_dir"
+    assert B.parse_args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        B.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: every array as float32 (float64 stays float64), the small ones whole, an array above its share of the
+    budget as a fixed sample of distinct elements in index order -- the same elements on every run."""
+    import numpy as np
+    import torch
+    B = _bench()
+    big = torch.arange(1 << 20, dtype=torch.float32)        # element i holds i: the sample shows which elements it took
+    arrays = {"image": torch.rand(2, 3, 4), "sample_counts": torch.arange(6, dtype=torch.int32).reshape(2, 3),
+              "d_tf": torch.ones(5, 4, dtype=torch.float64), "d_volume": big, "d_vol_absent": None}
+    budget = 1 << 20
+    files = B.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    assert set(files) == {"image.npy", "sample_counts.npy", "d_tf.npy", "d_volume_sample.npy"}
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(list(got[f].shape) == files[f] for f in files)
+    assert {f: a.dtype for f, a in got.items()} == {"image.npy": np.float32, "sample_counts.npy": np.float32,
+                                                    "d_tf.npy": np.float64, "d_volume_sample.npy": np.float32}
+    np.testing.assert_array_equal(got["image.npy"], arrays["image"].numpy())
+    assert got["sample_counts.npy"].tolist() == [[0, 1, 2], [3, 4, 5]] and (got["d_tf.npy"] == 1.0).all()
+    s = got["d_volume_sample.npy"]
+    share = (budget - sum(a.nbytes for f, a in got.items() if f != "d_volume_sample.npy")) // 4
+    assert 0.8 * share <= s.size <= share and sum(a.nbytes for a in got.values()) <= budget
+    assert (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < big.numel()
+    B.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f), got[f])

@@ -1,6 +1,6 @@
 import sys, os
 import torch, numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from differender_amd import functional as F
 from oracle import oracle as O
 from bench import synth_volume_torch, bench_tf_torch, in_circles
