@@ -1,0 +1,280 @@
+// camera_grad.hip -- gradient of the differentiable march w.r.t. the camera position look_from, gfx950.
+// The reference defines no such gradient (RaycastFunction.backward returns None, VR.py:465,473-476); this is the reverse-mode
+// derivative of its forward program with the usual frozen branches: the sample count n, the live-sample count (the forward's
+// `steps`), the jitter draw u, the slab faces fmaxf/fminf picked for tmin and tmax (VR.py:44-45), every tap's trilinear cell
+// and every max/min/clamp predicate (Taichi's rules, as in tests/golden/make_autograd_golden.py).
+//
+// The camera enters in four places: the ray direction (VR.py:127-151), the slab entry/exit (VR.py:28-53) and the jitter offset
+// built from them (VR.py:245-256), every sample position pos_s = look_from + t_s vd with t_s = mix(t0, tmax, s/(n-1))
+// (VR.py:273-280), and the Phong terms light_pos = look_from + e_y and r.(-vd) (VR.py:281-297). With, per sample,
+//   P_s = dL/dpos_s through the 7 taps, H_s = dL/d(pos_s - light_pos), D_s = dL/dvd through r.(-vd), G_s = P_s + H_s,
+// the chain collapses (the H_s of pos_s and of light_pos cancel in the direct term) to
+//   d look_from = sum P_s + J_vd^T (sum t_s G_s + sum D_s) + sum (1-f_s)(G_s.vd) grad t0 + sum f_s (G_s.vd) grad tmax,
+//   grad t0 = A grad tmin + (1-A) grad tmax,  A = (1 - u/n)(1 - 0.5/n),  f_s = s/(n-1),
+// so a ray keeps four running sums over its samples and evaluates the 3x3 Jacobian J_vd = d vd / d look_from and the slab rows
+// grad tmin, grad tmax once.
+//
+// Shape: one lane per ray, a wave per 8x8 pixel tile, a sequential march -- march_bwd_baseline_kernel's walk. The per-sample
+// adjoint needs the composite in front of the sample, which the sequential walk has for free; the wave-per-ray alternative
+// (DPP scans over 64 samples) would be faster on long rays but needs its own tap/adjoint pipeline. Sums: f32 per ray, f64 per
+// workgroup (LDS), then ONE f64 atomic per component per workgroup into d_cam[view][3] (no per-sample or per-ray atomics).
+#include "dr_device.h"
+#include "dr_kernels.h"
+#include "../../include/differender_hip.h"
+
+namespace dr {
+
+template <typename VT>
+struct CamParams {
+    VolView<VT> vol; int64_t vol_vs;
+    const float4 *tf; int64_t tf_vs; int R; float tf_len;
+    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp, *steps;
+    int W, H, S, img_W, row0; float inv_sr;
+    float near_, near_w, near_h;
+    uint32_t jitter_seed, view_base;
+    const float *grad_out, *out_fwd;
+    double *d_cam; float *d_cam_ray;
+};
+
+struct M3 { f3 r0, r1, r2; };  // rows
+__device__ __forceinline__ f3 f3_add(f3 a, f3 b) { return make_f3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ f3 f3_scale(float s, f3 a) { return make_f3(s * a.x, s * a.y, s * a.z); }
+__device__ __forceinline__ f3 f3_fma(float s, f3 a, f3 b) { return make_f3(fmaf(s, a.x, b.x), fmaf(s, a.y, b.y), fmaf(s, a.z, b.z)); }
+__device__ __forceinline__ f3 cross_f3(f3 a, f3 b) {
+    return make_f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+__device__ __forceinline__ f3 mul_t(const M3 &m, f3 g) {   // m^T g
+    return make_f3(m.r0.x * g.x + m.r1.x * g.y + m.r2.x * g.z, m.r0.y * g.x + m.r1.y * g.y + m.r2.y * g.z,
+                   m.r0.z * g.x + m.r1.z * g.y + m.r2.z * g.z);
+}
+__device__ __forceinline__ f3 col(const M3 &m, int k) {
+    return k == 0 ? make_f3(m.r0.x, m.r1.x, m.r2.x) : (k == 1 ? make_f3(m.r0.y, m.r1.y, m.r2.y) : make_f3(m.r0.z, m.r1.z, m.r2.z));
+}
+__device__ __forceinline__ M3 from_cols(f3 c0, f3 c1, f3 c2) {
+    M3 m;
+    m.r0 = make_f3(c0.x, c1.x, c2.x); m.r1 = make_f3(c0.y, c1.y, c2.y); m.r2 = make_f3(c0.z, c1.z, c2.z);
+    return m;
+}
+// Jacobian of normalize(x) applied to the columns of dx: (I - y y^T) dx / |x|
+__device__ __forceinline__ M3 d_normalize(f3 y, float inv_len, const M3 &dx) {
+    f3 c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const f3 d = col(dx, k);
+        c[k] = f3_scale(inv_len, f3_fma(-dot3(y, d), y, d));
+    }
+    return from_cols(c[0], c[1], c[2]);
+}
+__device__ __forceinline__ float inv_norm3(f3 a) { return 1.0f / sqrtf(dot3(a, a)); }
+
+// d vd / d look_from of VR.py:127-151 for the pixel with near-plane offsets (uw, vh): view_dir = normalize(-lf),
+// right = normalize(view_dir x e_y), up = normalize(right x view_dir), vd = normalize(near view_dir + uw right + vh up).
+// A camera on the y axis has right = 0 (degenerate in the forward already).
+__device__ __forceinline__ M3 ray_dir_jacobian(f3 lf, float near_, float uw, float vh) {
+    const f3 a = make_f3(-lf.x, -lf.y, -lf.z);
+    const float ia = inv_norm3(a);
+    const f3 vdir = f3_scale(ia, a);
+    M3 I3; I3.r0 = make_f3(-1.f, 0.f, 0.f); I3.r1 = make_f3(0.f, -1.f, 0.f); I3.r2 = make_f3(0.f, 0.f, -1.f);   // d(-lf)/dlf
+    const M3 Jv = d_normalize(vdir, ia, I3);
+    const f3 c = cross_f3(vdir, make_f3(0.f, 1.f, 0.f));                 // (-vdir.z, 0, vdir.x)
+    const float ic = inv_norm3(c);
+    const f3 right = f3_scale(ic, c);
+    M3 Jc; Jc.r0 = f3_scale(-1.f, Jv.r2); Jc.r1 = make_f3(0.f, 0.f, 0.f); Jc.r2 = Jv.r0;
+    const M3 Jr = d_normalize(right, ic, Jc);
+    const f3 d = cross_f3(right, vdir);
+    const float id = inv_norm3(d);
+    const f3 up = f3_scale(id, d);
+    f3 dc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dc[k] = f3_add(cross_f3(col(Jr, k), vdir), cross_f3(right, col(Jv, k)));
+    const M3 Ju = d_normalize(up, id, from_cols(dc[0], dc[1], dc[2]));
+    const f3 w = f3_add(f3_add(f3_scale(near_, vdir), f3_scale(uw, right)), f3_scale(vh, up));
+    const float iw = inv_norm3(w);
+    f3 wc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) wc[k] = f3_add(f3_add(f3_scale(near_, col(Jv, k)), f3_scale(uw, col(Jr, k))), f3_scale(vh, col(Ju, k)));
+    return d_normalize(f3_scale(iw, w), iw, from_cols(wc[0], wc[1], wc[2]));
+}
+
+// gradient of one slab distance t = (c - lf_a) / vd_a w.r.t. look_from (through lf_a and vd_a)
+__device__ __forceinline__ f3 slab_grad(int axis, float t, float inv_vda, const M3 &J) {
+    // (a weighted sum of the rows, not a selected one: a selected struct member is an indexed private array, i.e. scratch)
+    const float w0 = axis == 0 ? 1.0f : 0.0f, w1 = axis == 1 ? 1.0f : 0.0f, w2 = axis == 2 ? 1.0f : 0.0f;
+    const f3 row = f3_add(f3_add(f3_scale(w0, J.r0), f3_scale(w1, J.r1)), f3_scale(w2, J.r2));
+    return f3_fma(-inv_vda, make_f3(w0, w1, w2), f3_scale(-t * inv_vda, row));
+}
+
+__device__ __forceinline__ float cam_finite(float x) { return (x == x) ? fminf(fmaxf(x, -1.0e30f), 1.0e30f) : 0.0f; }
+
+template <typename VT, bool TF_LDS>
+__global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
+    __shared__ double red[3][256];
+    const int view = blockIdx.y;
+    const float4 *tfg = P.tf + view * P.tf_vs;
+    if (TF_LDS) {
+        for (int k = threadIdx.x; k < P.R; k += 256) lds_tf_[k] = tfg[k];
+        __syncthreads();
+    }
+    const float4 *tf = TF_LDS ? lds_tf_ : tfg;
+
+    f3 dcam = make_f3(0.f, 0.f, 0.f);
+    const int tiles_j = (P.H + 7) >> 3;
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    const int i = (wave / tiles_j) * 8 + (lane >> 3);
+    const int j = (wave % tiles_j) * 8 + (lane & 7);
+    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    const bool in_img = i < P.W && j < P.H;
+    const int n = in_img ? P.nsamp[p] : 0;
+    // H6: a single-sample ray sits at 0/0 in the reference and contributes nothing
+    if (in_img && n > 1) {
+        VolView<VT> vol = P.vol;
+        vol.p += view * P.vol_vs;
+        const f3 lf = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
+        const f3 light = make_f3(lf.x + 0.0f, lf.y + 1.0f, lf.z + 0.0f);
+        RayGeom rg;
+        rg.n = n; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
+        rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
+        rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+        int nmarch = rg.n > P.S ? P.S : rg.n;
+        nmarch = min(nmarch, P.steps[p]);   // the forward's live samples (early termination frozen)
+
+        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
+        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+        const float delta = 1e-3f;
+        f3 sP = make_f3(0.f, 0.f, 0.f), sTG = make_f3(0.f, 0.f, 0.f);
+        float s0 = 0.f, s1 = 0.f;
+        float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+        for (int s = 0; s < nmarch; ++s) {
+            Sample sm;
+            sample_pos(rg, lf.x, lf.y, lf.z, s, sm.px, sm.py, sm.pz);
+            f3 gI, gp, gm, ddx, ddy, ddz;   // slopes of the intensity tap and of the three central differences
+            sm.I = tri_sample_grad(vol, sm.px, sm.py, sm.pz, gI);
+            classify_from_I(tf, P.R, P.tf_len, P.inv_sr, sm);
+            float vp = tri_sample_grad(vol, sm.px + delta, sm.py, sm.pz, gp), vm = tri_sample_grad(vol, sm.px - delta, sm.py, sm.pz, gm);
+            const float dx = vp - vm;
+            ddx = make_f3(gp.x - gm.x, gp.y - gm.y, gp.z - gm.z);
+            vp = tri_sample_grad(vol, sm.px, sm.py + delta, sm.pz, gp); vm = tri_sample_grad(vol, sm.px, sm.py - delta, sm.pz, gm);
+            const float dy = vp - vm;
+            ddy = make_f3(gp.x - gm.x, gp.y - gm.y, gp.z - gm.z);
+            vp = tri_sample_grad(vol, sm.px, sm.py, sm.pz + delta, gp); vm = tri_sample_grad(vol, sm.px, sm.py, sm.pz - delta, gm);
+            const float dz = vp - vm;
+            ddz = make_f3(gp.x - gm.x, gp.y - gm.y, gp.z - gm.z);
+            shade_from_grad<false>(dx, dy, dz, light, vd, true, sm);
+            const float T = 1.0f - A;
+            C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
+            C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
+            C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
+            A = fmaf(T, sm.op, A);
+            const bool last = s == nmarch - 1;
+            const float suffix = (go.x * (of.x - C0) + go.y * (of.y - C1) + go.z * (of.z - C2)) + go.w * (of.w - A);
+            SampleAdj ad;
+            sample_adjoint(sm, vd, T, suffix, last, go, P.inv_sr, ad);
+            const float I_bar = intensity_adjoint(sm, tf[sm.lo], tf[sm.hi], ad, P.tf_len);
+            // dL/dpos through the taps: the intensity tap and the central differences of the normal (0 when flat, D1)
+            f3 Ps = f3_scale(I_bar, gI);
+            Ps = f3_fma(ad.gx, ddx, Ps);
+            Ps = f3_fma(ad.gy, ddy, Ps);
+            Ps = f3_fma(ad.gz, ddz, Ps);
+            // dL/d(pos - light_pos) through light_dir, dL/dvd through r.(-vd): the tail of sample_adjoint's lighting chain
+            f3 Hs = make_f3(0.f, 0.f, 0.f), Ds = make_f3(0.f, 0.f, 0.f);
+            if (!sm.flat) {
+                const float rgbdot = go.x * sm.r + go.y * sm.g + go.z * sm.b;
+                const float L_bar = sm.op * T * rgbdot;
+                const float Lraw_bar = (1.0f < sm.Lraw) ? 0.0f : L_bar;
+                const float rdv_bar = 0.3f * 32.0f * pow31(sm.rdv) * Lraw_bar;
+                const float q_bar = (0.0f < sm.q) ? rdv_bar : 0.0f;
+                const f3 rf_bar = make_f3(-vd.x * q_bar, -vd.y * q_bar, -vd.z * q_bar);
+                const float m_bar = ((0.0f < sm.m) ? 0.8f * Lraw_bar : 0.0f) - 2.0f * dot3(sm.nrm, rf_bar);
+                const f3 ld_bar = f3_fma(m_bar, sm.nrm, rf_bar);
+                const f3 lv = make_f3(sm.px - light.x, sm.py - light.y, sm.pz - light.z);
+                const float il = inv_norm3(lv);
+                Hs = f3_scale(il, f3_fma(-dot3(sm.ld, ld_bar), sm.ld, ld_bar));
+                Ds = f3_scale(-q_bar, sm.rf);
+            }
+            const float f = (float)s / (float)(rg.n - 1);
+            const float t = mixf(rg.t0, rg.exit_, f);
+            const f3 Gs = f3_add(Ps, Hs);
+            const float gv = dot3(Gs, vd);
+            sP = f3_add(sP, Ps);
+            sTG = f3_add(sTG, f3_fma(t, Gs, Ds));
+            s0 = fmaf(1.0f - f, gv, s0);
+            s1 = fmaf(f, gv, s1);
+        }
+
+        // once per ray: J_vd and the rows of the slab faces the forward picked (VR.py:28-53, same arithmetic as ray_setup.hip)
+        const float x = ((float)(i + P.row0) + 0.5f) / (float)P.img_W;
+        const float y = ((float)j + 0.5f) / (float)P.H;
+        const M3 J = ray_dir_jacobian(lf, P.near_, (x - 0.5f) * P.near_w, (y - 0.5f) * P.near_h);
+        const float fx = 1.0f / vd.x, fy = 1.0f / vd.y, fz = 1.0f / vd.z;
+        const float t1 = (-1.0f - lf.x) * fx, t2 = (1.0f - lf.x) * fx;
+        const float t3 = (-1.0f - lf.y) * fy, t4 = (1.0f - lf.y) * fy;
+        const float t5 = (-1.0f - lf.z) * fz, t6 = (1.0f - lf.z) * fz;
+        const float lo_x = fminf(t1, t2), lo_y = fminf(t3, t4), lo_z = fminf(t5, t6);
+        const float hi_x = fmaxf(t1, t2), hi_y = fmaxf(t3, t4), hi_z = fmaxf(t5, t6);
+        const float tmin = fmaxf(fmaxf(lo_x, lo_y), lo_z), tmax = fminf(fminf(hi_x, hi_y), hi_z);
+        const int amin = (tmin == lo_x) ? 0 : ((tmin == lo_y) ? 1 : 2);
+        const int amax = (tmax == hi_x) ? 0 : ((tmax == hi_y) ? 1 : 2);
+        const float ivmin = amin == 0 ? fx : (amin == 1 ? fy : fz), ivmax = amax == 0 ? fx : (amax == 1 ? fy : fz);
+        const f3 g_tmin = slab_grad(amin, tmin, ivmin, J), g_tmax = slab_grad(amax, tmax, ivmax, J);
+        const float nf = (float)rg.n;
+        const float u = P.jitter_seed != 0u ? jitter_u(P.jitter_seed, P.view_base + (uint32_t)view, (uint32_t)((i + P.row0) * P.H + j)) : 0.0f;
+        const float Acoef = (1.0f - u / nf) * (1.0f - 0.5f / nf);
+        const f3 g_t0 = f3_fma(Acoef, g_tmin, f3_scale(1.0f - Acoef, g_tmax));
+        dcam = f3_add(sP, mul_t(J, sTG));
+        dcam = f3_fma(s0, g_t0, dcam);
+        dcam = f3_fma(s1, g_tmax, dcam);
+        // D5: a NaN ray (NaN upstream gradient) contributes nothing, infinities are clamped
+        dcam = make_f3(cam_finite(dcam.x), cam_finite(dcam.y), cam_finite(dcam.z));
+    }
+    if (in_img && P.d_cam_ray) {
+        P.d_cam_ray[3 * p] = dcam.x; P.d_cam_ray[3 * p + 1] = dcam.y; P.d_cam_ray[3 * p + 2] = dcam.z;
+    }
+    red[0][threadIdx.x] = (double)dcam.x; red[1][threadIdx.x] = (double)dcam.y; red[2][threadIdx.x] = (double)dcam.z;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+            red[2][threadIdx.x] += red[2][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3 && red[threadIdx.x][0] != 0.0) atomicAdd(P.d_cam + 3 * view + threadIdx.x, red[threadIdx.x][0]);
+}
+
+template <typename VT>
+static int cam_dispatch(const MarchArgs &a, const CamArgs &c, hipStream_t stream) {
+    CamParams<VT> P;
+    P.vol.p = static_cast<const VT *>(a.vol);
+    P.vol.sx = a.sx; P.vol.sy = a.sy; P.vol.sz = a.sz;
+    P.vol.VX = a.VX; P.vol.VY = a.VY; P.vol.VZ = a.VZ;
+    P.vol.scx = (float)((double)a.VX - 1.0 - 1e-4);
+    P.vol.scy = (float)((double)a.VY - 1.0 - 1e-4);
+    P.vol.scz = (float)((double)a.VZ - 1.0 - 1e-4);
+    P.vol_vs = a.vol_vs;
+    P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4; P.R = a.R; P.tf_len = (float)(a.R - 1);
+    P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp; P.steps = c.steps;
+    P.W = a.W; P.H = a.H; P.S = a.S; P.img_W = a.img_W; P.row0 = a.row0; P.inv_sr = 1.0f / a.sr;
+    // VR.py:146-147 as ray_setup.hip forms them: doubles, rounded once
+    const double near_h = 2.0 * tan(a.fov_rad) * a.near_plane;
+    const double near_w = near_h * ((double)a.img_W / (double)a.H);
+    P.near_ = (float)a.near_plane; P.near_w = (float)near_w; P.near_h = (float)near_h;
+    P.jitter_seed = c.jitter_seed; P.view_base = c.view_base;
+    P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
+    P.d_cam = c.d_cam; P.d_cam_ray = c.d_cam_ray;
+    const int tiles = ((a.W + 7) / 8) * ((a.H + 7) / 8);
+    const dim3 grid((tiles + 3) / 4, a.n_views);
+    const size_t lds = (size_t)a.R * sizeof(float4);
+    if (lds <= 48 * 1024) hipLaunchKernelGGL((camera_grad_kernel<VT, true>), grid, dim3(256), lds, stream, P);
+    else hipLaunchKernelGGL((camera_grad_kernel<VT, false>), grid, dim3(256), 0, stream, P);   // a large TF is read where it lies
+    return (int)hipGetLastError();
+}
+
+int launch_camera_grad(const MarchArgs &a, const CamArgs &c, hipStream_t stream) {
+    return a.vol_dtype == DR_F16 ? cam_dispatch<__half>(a, c, stream) : cam_dispatch<float>(a, c, stream);
+}
+
+}  // namespace dr

@@ -224,6 +224,29 @@ int dr_march_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t
                              workspace, workspace_bytes, W, 0, stream);
 }
 
+int dr_march_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                     int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                     const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                     int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed,
+                     uint32_t view_base, int img_W, int row0, const int32_t *steps, const float *grad_out,
+                     const float *out_rgba, double *d_cam, float *d_cam_ray, void *stream) {
+    MarchArgs a;
+    int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
+                         entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!steps || !grad_out || !out_rgba || !d_cam) return DR_EINVAL;
+    if (row0 < 0 || img_W < W || row0 > img_W - W) return DR_EINVAL;
+    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    a.img_W = img_W; a.row0 = row0; a.mode = DR_MODE_DIFF;
+    a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    if (!launch_camera_grad) return DR_EUNSUPPORTED;   // (a library linked without camera_grad.o)
+    CamArgs c;
+    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    return launch_camera_grad(a, c, (hipStream_t)stream);
+}
+
 int dr_mse_loss_grad(const float *out_rgba, const float *reference, int64_t n, float inv_norm, float *grad_out,
                      double *loss, void *stream) {
     if (!out_rgba || !reference || n <= 0 || (!grad_out && !loss)) return DR_EINVAL;

@@ -132,6 +132,32 @@ __device__ __forceinline__ float tri_sample(const VolView<VT> &v, float px, floa
     return mixf(zl, zh, c.fz);
 }
 
+// tri_sample's value (same corners, same lerps, same bits) and its gradient w.r.t. the position (px, py, pz), for the camera
+// gradient (camera_grad.hip). The cell is frozen (floor has no gradient); an axis passes the gradient iff 0 < 0.5 p + 0.5 <= 1:
+// Taichi's rules for max(x, 0) (clamp's lower bound and low_high_frac's) and min(1, x). A high index clamped onto the low one
+// (last cell of an axis) gives equal corners and a zero slope, as the reference's program does.
+template <typename VT>
+__device__ __forceinline__ float tri_sample_grad(const VolView<VT> &v, float px, float py, float pz, f3 &grad) {
+    Cell c;
+    tri_cell(v, px, py, pz, c);
+    const VT *b00 = v.p + c.x0 * v.sx + c.y0 * v.sy, *b10 = v.p + c.x1 * v.sx + c.y0 * v.sy;
+    const VT *b01 = v.p + c.x0 * v.sx + c.y1 * v.sy, *b11 = v.p + c.x1 * v.sx + c.y1 * v.sy;
+    const int64_t o0 = c.z0 * v.sz, o1 = c.z1 * v.sz;
+    const float v000 = ld_voxel(b00 + o0), v100 = ld_voxel(b10 + o0), v010 = ld_voxel(b01 + o0), v110 = ld_voxel(b11 + o0);
+    const float v001 = ld_voxel(b00 + o1), v101 = ld_voxel(b10 + o1), v011 = ld_voxel(b01 + o1), v111 = ld_voxel(b11 + o1);
+    const float a0 = mixf(v000, v100, c.fx), b0 = mixf(v010, v110, c.fx);
+    const float a1 = mixf(v001, v101, c.fx), b1 = mixf(v011, v111, c.fx);
+    const float zl = mixf(a0, b0, c.fy), zh = mixf(a1, b1, c.fy);
+    const float dfx = mixf(mixf(v100 - v000, v110 - v010, c.fy), mixf(v101 - v001, v111 - v011, c.fy), c.fz);
+    const float dfy = mixf(b0 - a0, b1 - a1, c.fz);
+    const float dfz = zh - zl;
+    const float yx = fmaf(0.5f, px, 0.5f), yy = fmaf(0.5f, py, 0.5f), yz = fmaf(0.5f, pz, 0.5f);
+    grad.x = (0.0f < yx && !(1.0f < yx)) ? dfx * (0.5f * v.scx) : 0.0f;
+    grad.y = (0.0f < yy && !(1.0f < yy)) ? dfy * (0.5f * v.scy) : 0.0f;
+    grad.z = (0.0f < yz && !(1.0f < yz)) ? dfz * (0.5f * v.scz) : 0.0f;
+    return mixf(zl, zh, c.fz);
+}
+
 // Float atomic add to a gradient in global memory that can never leave +-FLT_MAX (the "finite by construction" promise of
 // the sanitising backward). Addends up to 1e30 -- everything the kernels produce from ordinary upstream
 // gradients, and every per-sample contribution after its clamp -- go through the hardware atomic: 3e8 of them would have to

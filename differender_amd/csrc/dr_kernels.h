@@ -60,6 +60,16 @@ hipError_t flat_invalidate_workspace(void *workspace, size_t workspace_bytes, hi
 int launch_march_fwd_flat(const MarchArgs &a, hipStream_t stream);   // one lane per sample
 int launch_march_bwd_flat(const MarchArgs &a, hipStream_t stream);
 
+// Camera gradient (camera_grad.hip): the extra arguments of dr_march_bwd_cam beside the MarchArgs of the backward
+struct CamArgs {
+    uint32_t jitter_seed, view_base;
+    const int32_t *steps;   // the forward's live samples per ray
+    double *d_cam;          // [n_views][3], accumulated
+    float *d_cam_ray;       // [n_views][W][H][3] per-ray contributions, nullable
+};
+// weak: the C entry (capi.o) must load in a library linked from the other objects alone (tests/test_abi.py's what-if build)
+__attribute__((weak)) int launch_camera_grad(const MarchArgs &a, const CamArgs &c, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -13,7 +13,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "march_fwd", "march_bwd", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
+__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 
 
@@ -396,6 +396,34 @@ def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, g
                                        *_rows(rows, W), _stream())
     N.check(rc, "dr_march_bwd_rows")
     return d_vol, d_tf
+
+
+def march_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
+                  near=0.1, jitter_seed=0, view_base=0, rows=None, per_ray=False):
+    """Gradient of the differentiable march w.r.t. the camera positions `cam` (views, 3) (dr_march_bwd_cam; the
+    reference has none, VR.py:465). The ray buffers, `steps`, `out`, jitter_seed, view_base and rows are those of the forward
+    (ray_setup + march_fwd). Returns d_cam (views, 3) float32 -- and, with per_ray=True, each ray's contribution
+    (views, W, H, 3) float32 as well."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    cam = cam.to(torch.float32).contiguous()
+    grad_out = grad_out.to(torch.float32).contiguous()
+    out = out.contiguous()
+    steps = steps.to(torch.int32).contiguous()
+    vargs = _vol_args(vol, V)
+    targs = _tf_args(tf, V)
+    d_cam = torch.zeros((V, 3), dtype=torch.float64, device=vol.device)
+    d_ray = torch.empty((V, W, H, 3), dtype=torch.float32, device=vol.device) if per_ray else None
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_march_bwd_cam(*vargs, targs[0], targs[1], targs[2], cam.data_ptr(), entry.data_ptr(),
+                                      exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), V, W, H, int(max_samples),
+                                      float(sampling_rate), float(np.radians(fov_deg)), float(near),
+                                      int(jitter_seed) & 0xFFFFFFFF, int(view_base), *_rows(rows, W), steps.data_ptr(),
+                                      grad_out.data_ptr(), out.data_ptr(), d_cam.data_ptr(),
+                                      d_ray.data_ptr() if per_ray else None, _stream())
+    N.check(rc, "dr_march_bwd_cam")
+    d_cam = torch.nan_to_num(d_cam.float())   # D5: a sum beyond the float range saturates, as nan_to_num makes of d_tf
+    return (d_cam, d_ray) if per_ray else d_cam
 
 
 def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):

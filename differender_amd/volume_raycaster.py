@@ -277,7 +277,10 @@ class RaycastFunction(torch.autograd.Function):
         tape = tape and ws is not None
         out, steps = F.march_fwd(volume, tf, cam, e, x, r, n, vr.max_samples, sampling_rate, N.DR_MODE_DIFF,
                                  fov_deg=vr.fov_deg, near=vr.near, workspace=ws, hints=hints, tape=tape)
-        ctx.save_for_backward(volume, tf, cam, e, x, r, n, out)
+        # the camera gradient needs the forward's live samples; nothing more is kept when it is not asked for
+        ctx.want_cam = bool(ctx.needs_input_grad[3])
+        ctx.save_for_backward(volume, tf, cam, e, x, r, n, out, *((steps,) if ctx.want_cam else ()))
+        ctx.lf_shape, ctx.lf_dtype = look_from.shape, look_from.dtype
         ctx.workspace = ws  # coarse tape of the forward (per-segment prefixes), consumed by backward
         ctx.tape = tape
         ctx.vr, ctx.sampling_rate, ctx.batched, ctx.jitter_seed = vr, sampling_rate, is_batched, seed
@@ -288,7 +291,7 @@ class RaycastFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, tf, cam, e, x, r, n, out = ctx.saved_tensors
+        volume, tf, cam, e, x, r, n, out = ctx.saved_tensors[:8]
         g = grad_output if ctx.batched else grad_output[None]
         want_vol, want_tf = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         dv, dt = F.march_bwd(volume, tf, cam, e, x, r, n, ctx.vr.max_samples, ctx.sampling_rate, g, out,
@@ -303,7 +306,15 @@ class RaycastFunction(torch.autograd.Function):
                 dv = torch.nan_to_num(dv)
             if dt is not None:
                 dt = torch.nan_to_num(dt)
-        return None, dv, dt, None, None, None, None, None
+        d_cam = None
+        if ctx.want_cam:   # after march_bwd, on the same stream
+            d_cam = F.march_bwd_cam(volume, tf, cam, e, x, r, n, ctx.saved_tensors[8], ctx.vr.max_samples, ctx.sampling_rate,
+                                    g, out, fov_deg=ctx.vr.fov_deg, near=ctx.vr.near, jitter_seed=ctx.jitter_seed)
+            # back to the shape look_from came in: an un-batched camera expanded to the batch's views gets their sum
+            if d_cam.shape[0] * 3 != math.prod(ctx.lf_shape):
+                d_cam = d_cam.sum(0)
+            d_cam = d_cam.reshape(ctx.lf_shape).to(ctx.lf_dtype)
+        return None, dv, dt, d_cam, None, None, None, None
 
 
 class Raycaster(torch.nn.Module):

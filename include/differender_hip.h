@@ -142,7 +142,8 @@ int dr_march_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
  *   d_vol    f32, element strides (dsx,dsy,dsz), nullable; ACCUMULATED into (caller zeroes)
  *   d_tf     [n_views or 1][R][4] f32, nullable; ACCUMULATED into (caller zeroes)
  *   workspace: the buffer the forward call of the same inputs filled (fast path), or NULL (baseline).
- * Gradients w.r.t. camera and sampling rate are not defined (the reference returns None, VR.py:465). */
+ * The gradient w.r.t. the camera position is dr_march_bwd_cam (below); the one w.r.t. the sampling rate is not defined
+ * (the reference returns None for both, VR.py:465,473-476). */
 int dr_march_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                  int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
                  const float *tf, int R, int64_t tf_view_stride,
@@ -196,6 +197,31 @@ int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                       float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
                       float *d_tf, int64_t dtf_view_stride,
                       void *workspace, size_t workspace_bytes, int img_W, int row0, void *stream);
+
+/* Gradient of the DR_MODE_DIFF march w.r.t. the camera position look_from -- a capability the reference lacks
+ * (its backward returns None for look_from, VR.py:465,473-476). The camera enters the forward through the ray direction
+ * (VR.py:127-151), the slab entry/exit and the jitter offset (VR.py:28-53,245-256), every sample position
+ * (VR.py:273-280) and the Phong terms light_pos = look_from + (0,1,0) and r.(-vd) (VR.py:281-297); this is the reverse-mode
+ * derivative of that program with its branches frozen: the sample count n, the live samples `steps`, the jitter draw, the
+ * slab faces chosen for tmin / tmax, every trilinear cell and every max/min/clamp predicate. Flat normals send no gradient
+ * through the normal (D1); single-sample rays contribute nothing (H6); a NaN ray contributes nothing and infinities are clamped
+ * (D5). A camera on the y axis is degenerate in the forward already (right = 0) and is not special-cased.
+ *   vol ... fov_rad, near_plane: as for dr_march_bwd_rows, the forward's ray buffers (dr_ray_setup_rows) included
+ *   jitter_seed, view_base, img_W, row0: those the ray buffers were generated with (the jitter draw is recomputed)
+ *   steps    [n_views][W][H] i32: the forward's live samples (dr_march_fwd[_rows]'s `steps`)
+ *   grad_out, out_rgba: as for dr_march_bwd_rows
+ *   d_cam    [n_views][3] f64, ACCUMULATED into (caller zeroes); one atomic per component per workgroup
+ *   d_cam_ray [n_views][W][H][3] f32, nullable: each ray's contribution (overwritten)
+ * Bands add up like views: the d_cam of the bands of an image sum to the whole image's. */
+int dr_march_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                     int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                     const float *tf, int R, int64_t tf_view_stride,
+                     const float *cam, const float *entry, const float *exit_, const float *rays,
+                     const int32_t *nsamp, int n_views, int W, int H, int max_samples,
+                     float sampling_rate, double fov_rad, double near_plane,
+                     uint32_t jitter_seed, uint32_t view_base, int img_W, int row0,
+                     const int32_t *steps, const float *grad_out, const float *out_rgba,
+                     double *d_cam, float *d_cam_ray, void *stream);
 
 /* The one exchange step of the path when views (or image bands) are sharded over the GPUs of a node: an in-place float32
  * SUM all-reduce of the shared gradients over RCCL / xGMI (the reference is single-device and has no

@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Reference camera gradients (d look_from): tests/golden/camgrad_*.npz.
+
+A float64 PyTorch transliteration of the reference's ray setup -- compute_entry_exit + get_ray_direction +
+get_entry_exit_points (differender/volume_raycaster.py:221-259, 127-151, 28-53) -- feeding `raycast` of
+make_autograd_golden.py (imported, not copied). torch.autograd differentiates the whole program w.r.t. the camera; nothing
+is derived by hand. Frozen, as in any reverse-mode AD of a program with branches: the sample count n (a floor), the jitter
+draw u (recomputed from the counter hash the oracle and the kernels share), the slab faces max/min pick, and everything
+make_autograd_golden.py freezes.
+
+Each ray gets its own leaf copy of the camera (cam.expand(P, 3) made a leaf), so the fixtures hold every ray's contribution
+as well as the total. Single-sample rays (0/0 position in the reference, H6) contribute nothing.
+Run:  python tests/golden/make_camgrad_golden.py
+"""
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+import make_autograd_golden as G  # noqa: E402
+
+
+def _hash_u32(x):
+    x = np.uint32(x)
+    with np.errstate(over="ignore"):
+        x ^= x >> np.uint32(16); x = np.uint32(x * np.uint32(0x7feb352d)); x ^= x >> np.uint32(15)
+        x = np.uint32(x * np.uint32(0x846ca68b)); x ^= x >> np.uint32(16)
+    return x
+
+
+def jitter_u(seed, view, pix):
+    """U[0,1) of (seed, view, pixel): the counter hash of oracle/dr_oracle_impl.inc and csrc/dr_device.h (24 bits)."""
+    with np.errstate(over="ignore"):
+        h = _hash_u32(np.uint32(seed) ^ np.uint32(0x9E3779B9))
+        h = _hash_u32(h ^ np.uint32(np.uint32(view) * np.uint32(0x85EBCA6B) + np.uint32(0xC2B2AE35)))
+        h = _hash_u32(h ^ np.uint32(pix).astype(np.uint32))
+    return (h >> np.uint32(8)).astype(np.float64) * (1.0 / 16777216.0)
+
+
+def _normalized(a):
+    return a / torch.sqrt((a * a).sum(-1, keepdim=True))
+
+
+def ray_setup(cam, W, H, vol_shape, sr, fov_deg=30.0, near=0.1, jitter_seed=0, view=0):
+    """VR.py:221-259 (+127-151, 28-53) for all W*H pixels, as torch functions of `cam` ((3,) or one row per pixel (W*H, 3)).
+    Returns entry, exit (P,), rays (P,3) and n (P,) int64 (frozen)."""
+    dt = cam.dtype
+    cam = cam.expand(W * H, 3) if cam.ndim == 1 else cam
+    near_h = 2.0 * math.tan(math.radians(fov_deg)) * near
+    near_w = near_h * (W / H)
+    VX, VY, VZ = vol_shape
+    diag = math.sqrt((VX - 1) ** 2 + (VY - 1) ** 2 + (VZ - 1) ** 2)
+    ii, jj = torch.meshgrid(torch.arange(W, dtype=dt), torch.arange(H, dtype=dt), indexing="ij")
+    u = ((ii.reshape(-1) + 0.5) / W - 0.5)[:, None]
+    v = ((jj.reshape(-1) + 0.5) / H - 0.5)[:, None]
+    view_dir = _normalized(-cam)
+    up0 = torch.tensor([0.0, 1.0, 0.0], dtype=dt).expand_as(view_dir)
+    right = _normalized(torch.cross(view_dir, up0, dim=-1))
+    up = _normalized(torch.cross(right, view_dir, dim=-1))
+    near_m = cam + near * view_dir
+    near_pos = near_m + (u * near_w) * right + (v * near_h) * up
+    vd = _normalized(near_pos - cam)
+    t_lo = (-1.0 - cam) / vd
+    t_hi = (1.0 - cam) / vd
+    tmin = torch.minimum(t_lo, t_hi).max(dim=-1).values
+    tmax = torch.maximum(t_lo, t_hi).min(dim=-1).values
+    hit = ~((tmax < 0) | (tmin > tmax))
+    ray_len = tmax - tmin
+    n = torch.where(hit, torch.floor(sr * ray_len.detach() * diag) + 1.0, torch.zeros_like(ray_len)).detach()
+    entry = tmin
+    if jitter_seed != 0:
+        uu = torch.from_numpy(jitter_u(jitter_seed, view, np.arange(W * H))).to(dt)
+        entry = tmin + uu * ray_len / torch.where(n > 0, n, torch.ones_like(n))   # (a missed ray's entry is never used)
+    return entry, tmax, vd, n.long()
+
+
+class _PerRayCam:
+    """`raycast` takes one camera; this hands it one row per ray: cam[None, :] and the light position both stay (P, 3)."""
+
+    def __init__(self, c):
+        self.c = c
+
+    def __getitem__(self, idx):
+        return self.c
+
+    def __add__(self, o):
+        return _PerRayCam(self.c + o)
+
+    def __rsub__(self, o):
+        return o - self.c
+
+
+CASES = {
+    # name: (volume shape, image, R, sampling rate, max_samples, TF kind, camera, jitter seed)
+    "a_orbit_sr1": ((16, 16, 16), (16, 16), 8, 1.0, 4096, "thin", ("orbit", 0.8), 0),
+    "b_sr2_ert": ((20, 16, 24), (16, 12), 16, 2.0, 4096, "opaque", ("orbit", 2.1), 0),
+    "c_clip": ((24, 24, 24), (12, 16), 12, 1.0, 23, "thin", ("orbit", 4.0), 0),
+    "d_jitter": ((18, 22, 16), (16, 16), 32, 1.0, 4096, "opaque", ("orbit", 5.2), 4242),
+    "e_nonsquare": ((16, 20, 16), (20, 12), 8, 1.0, 4096, "thin", ("orbit", 1.3), 0),
+    "f_near_face": ((16, 16, 16), (16, 16), 8, 1.0, 4096, "thin", ("point", (1.2, 0.35, 1.25)), 0),
+}
+VIEW = 2   # view index of the jitter hash
+
+
+def make_inputs(name):
+    from oracle import oracle as O
+    vshape, WH, R, sr, S, kind, (ck, cv), seed = CASES[name]
+    rng = np.random.RandomState(sorted(CASES).index(name) + 11)
+    vol = O.synth_volume(vshape, dtype=np.float64)
+    vol = np.clip(vol + 0.02 * rng.standard_normal(vshape), 0.0, 1.0)
+    tf = rng.uniform(0.05, 0.95, size=(R, 4))
+    tf[:, 3] = np.linspace(0.01, 0.06, R) if kind == "thin" else np.linspace(0.0, 0.9, R) ** 2 + 0.05
+    cam = O.in_circles(cv).astype(np.float64) if ck == "orbit" else np.array(cv, np.float64)
+    g = rng.standard_normal((*WH, 4))
+    return dict(vol=vol, tf=tf, cam=cam, grad_out=g, sr=np.float64(sr), max_samples=np.int32(S), jitter_seed=np.int64(seed),
+                view=np.int32(VIEW))
+
+
+def run_case(inp, dtype=torch.float64, pixels=None):
+    """Per-ray and total d look_from of sum(out * grad_out), the forward in `dtype` (float32: the same program in f32).
+    pixels: flat indices of the rays to march (default all; rays are independent, the others get zeros)."""
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
+    W, H = inp["grad_out"].shape[:2]
+    P = W * H
+    cam_pp = T(inp["cam"]).expand(P, 3).clone().requires_grad_(True)
+    vshape = inp["vol"].shape
+    e, x, r, n = ray_setup(cam_pp, W, H, vshape, float(inp["sr"]), jitter_seed=int(inp["jitter_seed"]), view=int(inp["view"]))
+    live = n > 1
+    if pixels is not None:
+        live &= torch.zeros_like(live).index_fill_(0, torch.as_tensor(pixels), True)
+    sel = torch.nonzero(live)[:, 0]
+    old = G.F64
+    G.F64 = dtype   # the transliteration reads its float type at call time
+    try:
+        out_sel, cnt = G.raycast(T(inp["vol"]), T(inp["tf"]), _PerRayCam(cam_pp[sel]), e[sel], x[sel], r[sel], n[sel],
+                                 int(inp["max_samples"]), float(inp["sr"]))
+    finally:
+        G.F64 = old
+    (out_sel * T(inp["grad_out"]).reshape(P, 4)[sel]).sum().backward()
+    out = np.zeros((P, 4)); out[sel.numpy()] = out_sel.detach().double().numpy()
+    steps = np.zeros(P, np.int32); steps[sel.numpy()] = cnt.numpy()
+    d_ray = cam_pp.grad.double().numpy()
+    return dict(entry=e.detach().double().numpy().reshape(W, H), exit=x.detach().double().numpy().reshape(W, H),
+                rays=r.detach().double().numpy().reshape(W, H, 3), n=n.numpy().astype(np.int32).reshape(W, H),
+                rgba=out.reshape(W, H, 4), steps=steps.reshape(W, H), dcam_ray=d_ray.reshape(W, H, 3), dcam=d_ray.sum(0))
+
+
+def main():
+    for name in CASES:
+        inp = make_inputs(name)
+        res = run_case(inp)
+        path = os.path.join(HERE, f"camgrad_{name}.npz")
+        np.savez_compressed(path, **inp, **res)
+        print("wrote", path, os.path.getsize(path), "bytes; rays n>1:", int((res["n"] > 1).sum()), "terminated early:",
+              int(((res["steps"] < np.minimum(res["n"], inp["max_samples"])) & (res["n"] > 1)).sum()),
+              "clipped:", int((res["n"] > inp["max_samples"]).sum()), "dcam", res["dcam"])
+
+
+if __name__ == "__main__":
+    main()
