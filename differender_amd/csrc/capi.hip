@@ -5,6 +5,7 @@
 #include "../../include/differender_hip.h"
 #include "dr_kernels.h"
 
+#include <cmath>
 #include <mutex>
 #include <unordered_map>
 
@@ -253,6 +254,46 @@ int dr_mse_loss_grad(const float *out_rgba, const float *reference, int64_t n, f
     DeviceOf guard(out_rgba);
     if (guard.err != hipSuccess) return (int)guard.err;
     return (int)launch_mse_loss_grad(out_rgba, reference, n, inv_norm, grad_out, loss, (hipStream_t)stream);
+}
+
+static int fill_loss(LossArgs &a, const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                     double data_range, int win_size, double win_sigma, double K1, double K2, int flags, double *stats) {
+    if (!x || !y || !strides4 || !stats) return DR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return DR_EINVAL;
+    if (win_size < 1 || win_size > 31 || win_size % 2 == 0) return DR_EINVAL;
+    if (!std::isfinite(data_range) || !(data_range > 0.0) || !std::isfinite(win_sigma) || !(win_sigma > 0.0)) return DR_EINVAL;
+    if (!std::isfinite(K1) || !std::isfinite(K2) || (flags & ~DR_SSIM_NONNEGATIVE)) return DR_EINVAL;
+    a.x = x; a.y = y; a.N = N; a.C = C; a.H = H; a.W = W;
+    for (int i = 0; i < 4; ++i) a.strides[i] = strides4[i];
+    a.data_range = data_range; a.win_sigma = win_sigma; a.K1 = K1; a.K2 = K2; a.win_size = win_size; a.flags = flags;
+    a.stats = stats; a.upstream = nullptr; a.grad_x = a.grad_y = nullptr;
+    return 0;
+}
+
+int dr_dssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
+                     int win_size, double win_sigma, double K1, double K2, int flags, double *stats, void *stream) {
+    LossArgs a;
+    int rc = fill_loss(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, flags, stats);
+    if (rc) return rc;
+    DeviceOf guard(x);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_dssim_mse_fwd) return DR_EUNSUPPORTED;   // (a library linked without image_loss.o)
+    return launch_dssim_mse_fwd(a, (hipStream_t)stream);
+}
+
+int dr_dssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
+                     int win_size, double win_sigma, double K1, double K2, int flags, const double *stats,
+                     const float *upstream3, float *grad_x, float *grad_y, void *stream) {
+    LossArgs a;
+    int rc = fill_loss(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, flags,
+                       const_cast<double *>(stats));
+    if (rc) return rc;
+    if (!grad_x) return DR_EINVAL;
+    a.upstream = upstream3; a.grad_x = grad_x; a.grad_y = grad_y;
+    DeviceOf guard(x);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_dssim_mse_bwd) return DR_EUNSUPPORTED;
+    return launch_dssim_mse_bwd(a, (hipStream_t)stream);
 }
 
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,

@@ -70,6 +70,21 @@ struct CamArgs {
 // weak: the C entry (capi.o) must load in a library linked from the other objects alone (tests/test_abi.py's what-if build)
 __attribute__((weak)) int launch_camera_grad(const MarchArgs &a, const CamArgs &c, hipStream_t stream);
 
+// DSSIM + MSE image loss (image_loss.hip): the arguments of dr_dssim_mse_fwd / dr_dssim_mse_bwd
+struct LossArgs {
+    const float *x, *y;
+    int N, C, H, W;
+    int64_t strides[4];        // element strides of the logical NCHW, shared by x, y and the gradients
+    double data_range, win_sigma, K1, K2;
+    int win_size, flags;       // flags: DR_SSIM_NONNEGATIVE
+    double *stats;             // [N*C] S_nc, then loss, dssim, mse (the forward writes, the backward reads)
+    const float *upstream;     // backward: (d loss, d dssim, d mse) on the device, nullable = (1, 0, 0)
+    float *grad_x, *grad_y;    // backward; grad_y nullable
+};
+// weak, as launch_camera_grad: capi.o must load in a library linked without image_loss.o
+__attribute__((weak)) int launch_dssim_mse_fwd(const LossArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_dssim_mse_bwd(const LossArgs &a, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -5,6 +5,7 @@ current torch stream. Volume tensors live in the reference's field index space (
 (W, D, H) of the user's (1, D, H, W) tensor (VR.py:481) and may have arbitrary strides, so the
 permuted view of VR.py:566,571 is consumed without a copy.
 """
+import ctypes
 import math
 import warnings
 
@@ -14,7 +15,7 @@ import torch
 from . import _native as N
 
 __all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
-           "mse_loss_grad", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
+           "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 
 
 def _stream():
@@ -447,6 +448,86 @@ def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):
                                       grad.data_ptr() if want_grad else None, loss.data_ptr(), _stream())
     N.check(rc, "dr_mse_loss_grad")
     return loss, grad
+
+
+def _dense(t):
+    """True if t's elements occupy one dense block in some axis order (no gaps, no overlaps): a gradient with its strides can
+    be written without two pixels landing on one element."""
+    dims = sorted((st, sz) for st, sz in zip(t.stride(), t.shape) if sz > 1)
+    expect = 1
+    for st, sz in dims:
+        if st != expect:
+            return False
+        expect *= sz
+    return True
+
+
+def _loss_inputs(out, reference):
+    if out.ndim != 4 or reference.shape != out.shape:
+        raise ValueError("the DSSIM + MSE loss expects two (N, C, H, W) tensors of the same shape")
+    _require_gpu(out, "out")
+    _require_gpu(reference, "reference")
+    if reference.device != out.device:
+        raise ValueError("reference must be on the device of out")
+    if out.dtype != torch.float32 or reference.dtype != torch.float32:
+        raise TypeError("out and reference must be float32")
+    if out.stride() != reference.stride() or not _dense(out):   # one set of strides serves x, y and the gradients
+        out, reference = out.contiguous(), reference.contiguous()
+    return out, reference, (ctypes.c_int64 * 4)(*out.stride())
+
+
+def _loss_config(data_range, win_size, win_sigma, K, nonnegative_ssim):
+    return (float(data_range), int(win_size), float(win_sigma), float(K[0]), float(K[1]),
+            N.DR_SSIM_NONNEGATIVE if nonnegative_ssim else 0)
+
+
+def dssim_mse_fwd(out, reference, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03), nonnegative_ssim=True):
+    """Forward of the demo's loss nan_to_num(1 - ssim(out, reference)) + mse(out, reference) (dr_dssim_mse_fwd, DESIGN.md D9;
+    OPT.py:70-72 with differender_amd.utils.ssim2d's semantics). out, reference: (N, C, H, W) float32 on the GPU.
+    Returns `stats`, a float64 tensor of N*C + 3 on the device: the per-plane SSIM, then loss, dssim, mse."""
+    x, y, strides = _loss_inputs(out, reference)
+    n, c, h, w = x.shape
+    stats = torch.empty(n * c + 3, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = N.lib().dr_dssim_mse_fwd(x.data_ptr(), y.data_ptr(), n, c, h, w, strides,
+                                      *_loss_config(data_range, win_size, win_sigma, K, nonnegative_ssim),
+                                      stats.data_ptr(), _stream())
+    N.check(rc, "dr_dssim_mse_fwd")
+    return stats
+
+
+def dssim_mse_bwd(out, reference, stats, upstream=None, want_ref_grad=False, data_range=1.0, win_size=11, win_sigma=1.5,
+                  K=(0.01, 0.03), nonnegative_ssim=True):
+    """Gradient of dssim_mse_fwd's outputs (dr_dssim_mse_bwd): `stats` is that forward's, `upstream` the gradients of the
+    caller's objective w.r.t. (loss, dssim, mse), a 3-element float32 tensor on the device (None = (1, 0, 0): loss.backward()).
+    Returns (d out, d reference or None); bitwise deterministic."""
+    x, y, strides = _loss_inputs(out, reference)
+    n, c, h, w = x.shape
+    if stats.dtype != torch.float64 or stats.numel() != n * c + 3 or stats.device != x.device or not stats.is_contiguous():
+        raise ValueError("stats must be the float64 output of dssim_mse_fwd for these images")
+    if upstream is not None:
+        upstream = upstream.to(device=x.device, dtype=torch.float32).contiguous()
+        if upstream.numel() != 3:
+            raise ValueError("upstream holds the gradients of (loss, dssim, mse): 3 elements")
+    gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
+    gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device) if want_ref_grad else None
+    with torch.cuda.device(x.device):
+        rc = N.lib().dr_dssim_mse_bwd(x.data_ptr(), y.data_ptr(), n, c, h, w, strides,
+                                      *_loss_config(data_range, win_size, win_sigma, K, nonnegative_ssim),
+                                      stats.data_ptr(), None if upstream is None else upstream.data_ptr(), gx.data_ptr(),
+                                      None if gy is None else gy.data_ptr(), _stream())
+    N.check(rc, "dr_dssim_mse_bwd")
+    return gx, gy
+
+
+def dssim_mse_loss_grad(out, reference, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03), nonnegative_ssim=True):
+    """The demo's loss and its gradient w.r.t. `out` in one forward + backward (the counterpart of mse_loss_grad).
+    Returns (loss, dssim, mse, grad_out): three 0-d float64 tensors on the device and a float32 gradient shaped like out."""
+    cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma, K=K, nonnegative_ssim=nonnegative_ssim)
+    stats = dssim_mse_fwd(out, reference, **cfg)
+    grad, _ = dssim_mse_bwd(out, reference, stats, **cfg)
+    loss, dssim, mse = stats[-3:].unbind(0)
+    return loss, dssim, mse, grad
 
 
 def tf_momentum_step(tf, d_tf, momentum, lr, gamma, max_grad):

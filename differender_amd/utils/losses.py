@@ -5,11 +5,14 @@
 not vendored by the reference, so its semantics are taken from memory of the package [mem: parity unpinned] -- 11-tap
 gaussian window (sigma 1.5), separable, VALID convolution per channel, K = (0.01, 0.03), the per-channel mean of the SSIM map,
 `relu` on it when nonnegative_ssim, mean over channels and batch when size_average. Plain torch ops (differentiable through
-autograd); used by the synthetic counterparts of the demo (examples/test_opt_synthetic.py, bench.py --workload opt)."""
+autograd); used by the synthetic counterparts of the demo (examples/test_opt_synthetic.py, bench.py --workload opt).
+
+`fused_dssim_mse_loss` is the same loss on the HIP kernels: one forward and one backward over the images, with
+ssim2d / dssim_mse_loss as its definition."""
 import torch
 import torch.nn.functional as F
 
-__all__ = ["ssim2d", "dssim_mse_loss"]
+__all__ = ["ssim2d", "dssim_mse_loss", "fused_dssim_mse_loss"]
 
 
 def _gauss_window(size, sigma, dtype, device):
@@ -53,3 +56,38 @@ def dssim_mse_loss(res, gt):
     dssim = 1.0 - ssim2d(res, gt, data_range=1.0, size_average=True, nonnegative_ssim=True)
     mse = F.mse_loss(res, gt)
     return torch.nan_to_num(dssim) + mse, dssim, mse
+
+
+class _FusedDSSIMMSE(torch.autograd.Function):
+    """(loss, dssim, mse) as one 3-element float32 tensor; the caller unbinds it, so autograd hands backward the three upstream
+    gradients stacked on the device and the kernel reads them there (no host read)."""
+
+    @staticmethod
+    def forward(ctx, res, gt, cfg):
+        from differender_amd import functional as DF
+        stats = DF.dssim_mse_fwd(res, gt, **cfg)
+        ctx.save_for_backward(res, gt, stats)
+        ctx.cfg = cfg
+        return stats[-3:].float()
+
+    @staticmethod
+    def backward(ctx, g3):
+        from differender_amd import functional as DF
+        res, gt, stats = ctx.saved_tensors
+        gx, gy = DF.dssim_mse_bwd(res, gt, stats, upstream=g3, want_ref_grad=ctx.needs_input_grad[1], **ctx.cfg)
+        return (gx if ctx.needs_input_grad[0] else None), gy, None
+
+
+def fused_dssim_mse_loss(res, gt, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03), nonnegative_ssim=True):
+    """dssim_mse_loss on the HIP kernels: returns (loss, dssim, mse), 0-d float32 tensors, with
+    loss = nan_to_num(1 - ssim2d(res, gt, data_range, ..., nonnegative_ssim)) + mse_loss(res, gt). Differentiable w.r.t. res
+    and, when it requires a gradient, gt. res and gt: (N, C, H, W) float32 on a ROCm GPU (there is no CPU path)."""
+    if res.ndim != 4 or gt.shape != res.shape:
+        raise ValueError("fused_dssim_mse_loss expects two (N, C, H, W) tensors of the same shape")
+    if res.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise TypeError("fused_dssim_mse_loss expects float32 tensors")
+    if not (res.is_cuda and gt.is_cuda):
+        raise RuntimeError("fused_dssim_mse_loss runs on a ROCm GPU only: there is no CPU path")
+    cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma, K=tuple(K), nonnegative_ssim=nonnegative_ssim)
+    loss, dssim, mse = _FusedDSSIMMSE.apply(res, gt, cfg).unbind(0)
+    return loss, dssim, mse

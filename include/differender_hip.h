@@ -250,6 +250,29 @@ int dr_comm_destroy(void *comm);
 int dr_mse_loss_grad(const float *out_rgba, const float *reference, int64_t n, float inv_norm,
                      float *grad_out, double *loss, void *stream);
 
+/* The demo's image loss and its gradient: nan_to_num(1 - ssim(res, gt, data_range=1, nonnegative_ssim=True))
+ * + mse(res, gt) of examples/test_opt_tf.py:70-72 ("OPT.py"), fused, as differender_amd.utils.losses.ssim2d /
+ * dssim_mse_loss define it: an odd win_size Gaussian window (f32 exp, divided by its f32 sum), separable VALID filtering along
+ * H then W with a pass skipped when that side is shorter than the window, C1 = (K1 data_range)^2, C2 = (K2 data_range)^2,
+ * S_nc the mean of the SSIM map of plane (n, c) (relu'd when flags has DR_SSIM_NONNEGATIVE), ssim its mean over the planes,
+ * dssim = 1 - ssim, mse over the full N*C*H*W images. The gradient follows torch's rules: relu passes only where S_nc > 0,
+ * nan_to_num only where dssim is finite (a NaN in x gives a NaN loss through the mse and no dssim gradient).
+ *   x, y      the render and the target, f32, logical (N, C, H, W) with the element strides strides4[4] (a host array; shared
+ *             by x, y and the gradients): a host passes the march's [n_views][W][H][4] output as it lies, with no copy
+ *   win_size  odd, <= 31; data_range finite and > 0
+ *   stats     [N*C + 3] f64 on the device, WRITTEN (not accumulated): S_nc per plane, then loss, dssim, mse
+ *   upstream3 (bwd) 3 f32 on the device: d loss, d dssim, d mse of the caller's objective; NULL = (1, 0, 0)
+ *   grad_x    (bwd) [like x] f32, overwritten; grad_y nullable
+ * The backward reads only the forward's stats (relu's mask, dssim's finiteness): its gradient is bitwise deterministic. At
+ * most three launches per call, no allocation, no host synchronisation. */
+enum { DR_SSIM_NONNEGATIVE = 1 };
+int dr_dssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                     double data_range, int win_size, double win_sigma, double K1, double K2, int flags,
+                     double *stats, void *stream);
+int dr_dssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                     double data_range, int win_size, double win_sigma, double K1, double K2, int flags,
+                     const double *stats, const float *upstream3, float *grad_x, float *grad_y, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
