@@ -5,6 +5,7 @@
 #include "../../include/differender_hip.h"
 #include "dr_kernels.h"
 
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 #include <unordered_map>
@@ -294,6 +295,66 @@ int dr_dssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W,
     if (guard.err != hipSuccess) return (int)guard.err;
     if (!launch_dssim_mse_bwd) return DR_EUNSUPPORTED;
     return launch_dssim_mse_bwd(a, (hipStream_t)stream);
+}
+
+static_assert(MS_MAX_LEVELS == DR_MSSSIM_MAX_LEVELS, "dr_kernels.h and the public header disagree on the MS-SSIM levels");
+
+static bool msssim_shape_ok(int N, int C, int H, int W, int levels) {
+    return N > 0 && C > 0 && H > 0 && W > 0 && levels >= 1 && levels <= DR_MSSSIM_MAX_LEVELS;
+}
+
+size_t dr_msssim_workspace_bytes(int N, int C, int H, int W, int levels, int want_grad_y) {
+    if (!msssim_shape_ok(N, C, H, W, levels)) return 0;
+    return msssim_layout(N, C, H, W, levels, want_grad_y != 0).bytes;
+}
+
+static int fill_msssim(MSArgs &a, const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                       double data_range, int win_size, double win_sigma, double K1, double K2, const double *weights,
+                       int levels, void *workspace, double *stats) {
+    if (!x || !y || !strides4 || !stats || !weights) return DR_EINVAL;
+    if (!msssim_shape_ok(N, C, H, W, levels)) return DR_EINVAL;
+    if (win_size < 1 || win_size > 31 || win_size % 2 == 0) return DR_EINVAL;
+    if (std::min(H, W) <= (win_size - 1) * 16) return DR_EINVAL;   // the window fits every level of a 5-level pyramid
+    if (!std::isfinite(data_range) || !(data_range > 0.0) || !std::isfinite(win_sigma) || !(win_sigma > 0.0)) return DR_EINVAL;
+    if (!std::isfinite(K1) || !std::isfinite(K2)) return DR_EINVAL;
+    for (int l = 0; l < levels; ++l)
+        if (!std::isfinite(weights[l]) || !(weights[l] > 0.0)) return DR_EINVAL;
+    if (!workspace && levels > 1) return DR_EINVAL;
+    a.x = x; a.y = y; a.N = N; a.C = C; a.H = H; a.W = W;
+    for (int i = 0; i < 4; ++i) a.strides[i] = strides4[i];
+    a.data_range = data_range; a.win_sigma = win_sigma; a.K1 = K1; a.K2 = K2; a.win_size = win_size; a.levels = levels;
+    for (int l = 0; l < levels; ++l) a.weights[l] = weights[l];
+    a.workspace = workspace; a.stats = stats; a.upstream = nullptr; a.grad_x = a.grad_y = nullptr;
+    return 0;
+}
+
+int dr_msssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
+                      int win_size, double win_sigma, double K1, double K2, const double *weights, int levels,
+                      void *workspace, double *stats, void *stream) {
+    MSArgs a;
+    int rc = fill_msssim(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, weights, levels, workspace,
+                         stats);
+    if (rc) return rc;
+    DeviceOf guard(x);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_msssim_mse_fwd) return DR_EUNSUPPORTED;   // (a library linked without msssim.o)
+    return launch_msssim_mse_fwd(a, (hipStream_t)stream);
+}
+
+int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
+                      int win_size, double win_sigma, double K1, double K2, const double *weights, int levels,
+                      const double *stats, const float *upstream3, float *grad_x, float *grad_y, void *workspace,
+                      void *stream) {
+    MSArgs a;
+    int rc = fill_msssim(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, weights, levels, workspace,
+                         const_cast<double *>(stats));
+    if (rc) return rc;
+    if (!grad_x) return DR_EINVAL;
+    a.upstream = upstream3; a.grad_x = grad_x; a.grad_y = grad_y;
+    DeviceOf guard(x);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_msssim_mse_bwd) return DR_EUNSUPPORTED;
+    return launch_msssim_mse_bwd(a, (hipStream_t)stream);
 }
 
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,

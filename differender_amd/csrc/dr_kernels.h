@@ -85,6 +85,48 @@ struct LossArgs {
 __attribute__((weak)) int launch_dssim_mse_fwd(const LossArgs &a, hipStream_t stream);
 __attribute__((weak)) int launch_dssim_mse_bwd(const LossArgs &a, hipStream_t stream);
 
+// MS-SSIM + MSE image loss (msssim.hip): the arguments of dr_msssim_mse_fwd / dr_msssim_mse_bwd
+constexpr int MS_MAX_LEVELS = 5;   // DR_MSSSIM_MAX_LEVELS of the public header (checked in capi.hip)
+struct MSArgs {
+    const float *x, *y;
+    int N, C, H, W;
+    int64_t strides[4];        // element strides of the logical NCHW, shared by x, y and the gradients
+    double data_range, win_sigma, K1, K2;
+    double weights[MS_MAX_LEVELS];
+    int win_size, levels;
+    void *workspace;           // msssim_layout(...).bytes
+    double *stats;             // v[levels][N*C], ms[N*C], loss, dms, mse (the forward writes, the backward reads)
+    const float *upstream;     // backward: (d loss, d dms, d mse) on the device, nullable = (1, 0, 0)
+    float *grad_x, *grad_y;    // backward; grad_y nullable
+};
+// The workspace: levels 1..L-1 of X and Y (pyramid), and for the backward dX_l (and dY_l), each a dense [N*C][H_l][W_l] f32
+// block at a 256-byte aligned offset. H_{l+1} = ceil(H_l / 2) (avg_pool2d(2, padding=H_l % 2)).
+struct MSLayout {
+    int H[MS_MAX_LEVELS], W[MS_MAX_LEVELS];
+    size_t x[MS_MAX_LEVELS], y[MS_MAX_LEVELS], dx[MS_MAX_LEVELS], dy[MS_MAX_LEVELS];
+    size_t bytes;
+};
+inline MSLayout msssim_layout(int N, int C, int H, int W, int levels, bool want_grad_y) {
+    MSLayout m{};
+    size_t off = 0;
+    auto take = [&off](size_t n) { const size_t o = off; off += (n * sizeof(float) + 255) / 256 * 256; return o; };
+    for (int l = 0; l < levels; ++l) {
+        m.H[l] = l == 0 ? H : (m.H[l - 1] + 1) / 2;
+        m.W[l] = l == 0 ? W : (m.W[l - 1] + 1) / 2;
+        if (l == 0) continue;
+        const size_t n = (size_t)N * C * m.H[l] * m.W[l];
+        m.x[l] = take(n);
+        m.y[l] = take(n);
+        m.dx[l] = take(n);
+        if (want_grad_y) m.dy[l] = take(n);
+    }
+    m.bytes = off;
+    return m;
+}
+// weak, as launch_camera_grad: capi.o must load in a library linked without msssim.o
+__attribute__((weak)) int launch_msssim_mse_fwd(const MSArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_msssim_mse_bwd(const MSArgs &a, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

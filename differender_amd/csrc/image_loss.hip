@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "dr_kernels.h"
+#include "dr_ssim.h"
 #include "../../include/differender_hip.h"
 
 namespace dr {
@@ -32,11 +33,7 @@ hipError_t allow_lds_impl(const void *kernel, size_t bytes);  // capi.hip
 
 namespace {
 
-constexpr int TX = 64;          // tile width: one wave row along W
-constexpr int NT = 256;         // threads per workgroup
-constexpr int KMAX = 31;        // largest window (validated by the C entry)
-constexpr size_t LDS_DEFAULT = 64 * 1024, LDS_MAX = 160 * 1024;
-constexpr size_t STATIC_LDS = 256;   // the window and the reduction slots beside the dynamic carve
+using namespace ssim;
 
 struct LossParams {
     const float *x, *y;
@@ -51,42 +48,6 @@ struct LossParams {
     float *gx, *gy;
 };
 
-// _gauss_window in f32 into w[0..k), and w[KMAX] = 1: a side shorter than the window is not filtered (the one-tap window {1})
-__device__ void build_window(const LossParams &P, float *w) {
-    if (threadIdx.x == 0) {
-        float s = 0.0f;
-        for (int i = 0; i < P.k; ++i) {
-            const float t = (float)(i - P.k / 2);
-            w[i] = expf(-(t * t) / P.sigma_den);
-            s += w[i];
-        }
-        for (int i = 0; i < P.k; ++i) w[i] = w[i] / s;
-        w[KMAX] = 1.0f;
-    }
-    __syncthreads();
-}
-
-// Every workgroup filters its tile shifted by one of its own pixels, (x - cx, y - cy): sigma^2 = E[x^2] - E[x]^2 cancels in
-// f32 when the mean is large against the spread (a flat region gives 1e-4 of noise in the loss unshifted); shifted it is
-// computed from small numbers. The means are put back as mu = G(x - c) + c sum(w), the shift leaves the maths unchanged.
-__device__ __forceinline__ float tile_shift(const float *p, int64_t o) {
-    const float c = p[o];
-    return isfinite(c) ? c : 0.0f;
-}
-__device__ __forceinline__ float window_mass(const float *wv, int kh, const float *wh, int kw) {   // G applied to a constant 1
-    float sv = 0.0f, s = 0.0f;
-    for (int j = 0; j < kh; ++j) sv += wv[j];
-    for (int j = 0; j < kw; ++j) s += wh[j] * sv;
-    return s;
-}
-
-__device__ __forceinline__ double block_sum(double v, double *red) {  // red: NT/64 doubles; result valid in thread 0
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
     extern __shared__ float lds[];
     __shared__ float wg[KMAX + 1];
@@ -97,7 +58,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
     const int64_t base = (int64_t)(plane / P.C) * P.s0 + (int64_t)(plane % P.C) * P.s1;
     const float *xp = P.x + base, *yp = P.y + base;
     float *in_x = lds, *in_y = lds + IH * IW, *V = lds + 2 * IH * IW;   // V[5][TY][IW]
-    build_window(P, wg);
+    build_window(P.k, P.sigma_den, wg);
     const float *wv = P.kh == 1 ? wg + KMAX : wg, *wh = P.kw == 1 ? wg + KMAX : wg;
 
     // the tile's input with its halo (zeros beyond the image feed only output positions that do not exist); the squared error
@@ -215,7 +176,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
         const int r1 = max(2 * IH * IW, 4 * QH * QW);
         float *in_x = lds, *in_y = lds + IH * IW, *Dm = lds;   // region 1: the input, then the adjoint maps Dm[4][QH][QW]
         float *V = lds + r1;                                     // region 2: the vertical moments V[5][QH][IW], then Tt[4][QH][TX]
-        build_window(P, wg);
+        build_window(P.k, P.sigma_den, wg);
         const int64_t o0 = y0 * P.s2 + x0 * P.s3;
         cx = tile_shift(xp, o0);
         cy = tile_shift(yp, o0);
@@ -309,24 +270,6 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
         P.gx[base + o] = r[0] + 2.0f * xs * r[2] + ys * r[3] + e;
         if (P.gy) P.gy[base + o] = r[1] + 2.0f * ys * r[2] + xs * r[3] - e;
     }
-}
-
-size_t fwd_lds_floats(int TY, int kh, int kw) {
-    const int IH = TY + kh - 1, IW = TX + kw - 1;
-    return (size_t)2 * IH * IW + (size_t)5 * TY * IW;
-}
-size_t bwd_lds_floats(int TY, int kh, int kw) {
-    const int IH = TY + 2 * (kh - 1), IW = TX + 2 * (kw - 1), QH = TY + kh - 1, QW = TX + kw - 1;
-    return std::max((size_t)2 * IH * IW, (size_t)4 * QH * QW) + std::max((size_t)5 * QH * IW, (size_t)4 * QH * TX);
-}
-
-// The tallest tile (16 rows at most) whose LDS fits the default 64 KB; a wide window falls back to the opt-in above it
-template <typename F>
-int pick_ty(F lds_floats, int kh, int kw, size_t *bytes) {
-    for (size_t cap : {LDS_DEFAULT, LDS_MAX})
-        for (int TY = 16; TY >= 1; TY >>= 1)
-            if ((*bytes = lds_floats(TY, kh, kw) * sizeof(float)) + STATIC_LDS <= cap) return TY;
-    return 0;
 }
 
 int fill_params(LossParams &P, const LossArgs &a, bool bwd, size_t *lds) {

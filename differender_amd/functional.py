@@ -15,7 +15,8 @@ import torch
 from . import _native as N
 
 __all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
-           "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
+           "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
+           "msssim_mse_loss_grad", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 
 
 def _stream():
@@ -528,6 +529,74 @@ def dssim_mse_loss_grad(out, reference, data_range=1.0, win_size=11, win_sigma=1
     grad, _ = dssim_mse_bwd(out, reference, stats, **cfg)
     loss, dssim, mse = stats[-3:].unbind(0)
     return loss, dssim, mse, grad
+
+
+def _msssim_config(data_range, win_size, win_sigma, K, weights):
+    from .utils.losses import MS_SSIM_WEIGHTS
+    w = [float(v) for v in (MS_SSIM_WEIGHTS if weights is None else weights)]
+    return (float(data_range), int(win_size), float(win_sigma), float(K[0]), float(K[1]), (ctypes.c_double * len(w))(*w),
+            len(w))
+
+
+def _msssim_workspace(x, levels, want_ref_grad):
+    n, c, h, w = x.shape
+    nbytes = N.lib().dr_msssim_workspace_bytes(n, c, h, w, levels, int(want_ref_grad))
+    return torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+
+
+def msssim_mse_fwd(out, reference, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03),
+                   weights=None):
+    """Forward of nan_to_num(1 - ms_ssim(out, reference)) + mse(out, reference) (dr_msssim_mse_fwd, DESIGN.md D10;
+    differender_amd.utils.ms_ssim2d's semantics). out, reference: (N, C, H, W) float32 on the GPU, min(H, W) > 16 (win_size - 1).
+    Returns `stats`, float64 on the device: v[levels][N*C], ms[N*C], then loss, dms, mse."""
+    x, y, strides = _loss_inputs(out, reference)
+    n, c, h, w = x.shape
+    cfg = _msssim_config(data_range, win_size, win_sigma, K, weights)
+    stats = torch.empty((cfg[-1] + 1) * n * c + 3, dtype=torch.float64, device=x.device)
+    ws = _msssim_workspace(x, cfg[-1], False)
+    with torch.cuda.device(x.device):
+        rc = N.lib().dr_msssim_mse_fwd(x.data_ptr(), y.data_ptr(), n, c, h, w, strides, *cfg,
+                                       None if ws is None else ws.data_ptr(), stats.data_ptr(), _stream())
+    N.check(rc, "dr_msssim_mse_fwd")
+    return stats
+
+
+def msssim_mse_bwd(out, reference, stats, upstream=None, want_ref_grad=False, data_range=1.0, win_size=11, win_sigma=1.5,
+                   K=(0.01, 0.03), weights=None):
+    """Gradient of msssim_mse_fwd's outputs (dr_msssim_mse_bwd): `stats` is that forward's, `upstream` the gradients of the
+    caller's objective w.r.t. (loss, dms, mse), 3 float32 on the device (None = (1, 0, 0)). Returns (d out, d reference or
+    None); bitwise deterministic."""
+    x, y, strides = _loss_inputs(out, reference)
+    n, c, h, w = x.shape
+    cfg = _msssim_config(data_range, win_size, win_sigma, K, weights)
+    if stats.dtype != torch.float64 or stats.numel() != (cfg[-1] + 1) * n * c + 3 or stats.device != x.device \
+            or not stats.is_contiguous():
+        raise ValueError("stats must be the float64 output of msssim_mse_fwd for these images and levels")
+    if upstream is not None:
+        upstream = upstream.to(device=x.device, dtype=torch.float32).contiguous()
+        if upstream.numel() != 3:
+            raise ValueError("upstream holds the gradients of (loss, dms, mse): 3 elements")
+    gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
+    gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device) if want_ref_grad else None
+    ws = _msssim_workspace(x, cfg[-1], want_ref_grad)
+    with torch.cuda.device(x.device):
+        rc = N.lib().dr_msssim_mse_bwd(x.data_ptr(), y.data_ptr(), n, c, h, w, strides, *cfg, stats.data_ptr(),
+                                       None if upstream is None else upstream.data_ptr(), gx.data_ptr(),
+                                       None if gy is None else gy.data_ptr(), None if ws is None else ws.data_ptr(),
+                                       _stream())
+    N.check(rc, "dr_msssim_mse_bwd")
+    return gx, gy
+
+
+def msssim_mse_loss_grad(out, reference, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03),
+                         weights=None):
+    """The MS-SSIM + MSE loss and its gradient w.r.t. `out` in one forward + backward.
+    Returns (loss, dms, mse, grad_out): three 0-d float64 tensors on the device and a float32 gradient shaped like out."""
+    cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma, K=K, weights=weights)
+    stats = msssim_mse_fwd(out, reference, **cfg)
+    grad, _ = msssim_mse_bwd(out, reference, stats, **cfg)
+    loss, dms, mse = stats[-3:].unbind(0)
+    return loss, dms, mse, grad
 
 
 def tf_momentum_step(tf, d_tf, momentum, lr, gamma, max_grad):

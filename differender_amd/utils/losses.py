@@ -8,11 +8,17 @@ gaussian window (sigma 1.5), separable, VALID convolution per channel, K = (0.01
 autograd); used by the synthetic counterparts of the demo (examples/test_opt_synthetic.py, bench.py --workload opt).
 
 `fused_dssim_mse_loss` is the same loss on the HIP kernels: one forward and one backward over the images, with
-ssim2d / dssim_mse_loss as its definition."""
+ssim2d / dssim_mse_loss as its definition.
+
+`ms_ssim2d` restates `pytorch_msssim.ms_ssim`, the package's multi-scale SSIM, from the same memory [mem: parity unpinned]:
+per level the SSIM and contrast-structure (CS) maps of ssim2d and their per-plane means, relu'd; 2x2 average pooling between
+levels; the weighted product over the levels. `fused_ms_dssim_mse_loss` is ms_dssim_mse_loss on the HIP kernels (DESIGN.md
+D10)."""
 import torch
 import torch.nn.functional as F
 
-__all__ = ["ssim2d", "dssim_mse_loss", "fused_dssim_mse_loss"]
+__all__ = ["ssim2d", "dssim_mse_loss", "fused_dssim_mse_loss", "MS_SSIM_WEIGHTS", "ms_ssim2d", "ms_dssim_mse_loss",
+           "fused_ms_dssim_mse_loss"]
 
 
 def _gauss_window(size, sigma, dtype, device):
@@ -91,3 +97,90 @@ def fused_dssim_mse_loss(res, gt, data_range=1.0, win_size=11, win_sigma=1.5, K=
     cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma, K=tuple(K), nonnegative_ssim=nonnegative_ssim)
     loss, dssim, mse = _FusedDSSIMMSE.apply(res, gt, cfg).unbind(0)
     return loss, dssim, mse
+
+
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def _ssim_cs(X, Y, win, data_range, K):
+    """Per-plane means (N, C) of the SSIM map and of the CS map, formed exactly as ssim2d forms them."""
+    C1, C2 = (K[0] * data_range) ** 2, (K[1] * data_range) ** 2
+    c = X.shape[1]
+    m = _filter(torch.cat([X, Y, X * X, Y * Y, X * Y], dim=1), win)
+    mu1, mu2 = m[:, :c], m[:, c:2 * c]
+    mu1_sq, mu2_sq, mu12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s1 = m[:, 2 * c:3 * c] - mu1_sq
+    s2 = m[:, 3 * c:4 * c] - mu2_sq
+    s12 = m[:, 4 * c:] - mu12
+    cs_map = (2.0 * s12 + C2) / (s1 + s2 + C2)
+    ssim_map = ((2.0 * mu12 + C1) / (mu1_sq + mu2_sq + C1)) * cs_map
+    return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)
+
+
+def ms_ssim2d(X, Y, data_range=255.0, size_average=True, win_size=11, win_sigma=1.5, weights=None, K=(0.01, 0.03)):
+    """Multi-scale SSIM of two (N, C, H, W) image batches (pytorch_msssim.ms_ssim; see the module docstring).
+    Level l < L-1 contributes relu(CS_nc), the last level relu(SSIM_nc); between levels X and Y are 2x2 average pooled with a
+    padding of (H % 2, W % 2), the padded zeros counted. ms_nc = prod_l v_l ** w_l, averaged over (N, C), or over C when not
+    size_average. With weights=(1.0,) it is ssim2d(..., nonnegative_ssim=True)."""
+    if X.shape != Y.shape or X.ndim != 4:
+        raise ValueError("ms_ssim2d expects two (N, C, H, W) tensors of the same shape")
+    if min(X.shape[-2:]) <= (win_size - 1) * 2 ** 4:
+        raise ValueError(f"ms_ssim2d needs both sides longer than {(win_size - 1) * 2 ** 4} (the window at the 5th scale)")
+    weights = torch.tensor(MS_SSIM_WEIGHTS if weights is None else weights, dtype=X.dtype, device=X.device)
+    win = _gauss_window(win_size, win_sigma, X.dtype, X.device)
+    levels = weights.numel()
+    vals = []
+    for i in range(levels):
+        ssim_nc, cs_nc = _ssim_cs(X, Y, win, data_range, K)
+        if i < levels - 1:
+            vals.append(torch.relu(cs_nc))
+            padding = [X.shape[2] % 2, X.shape[3] % 2]
+            X = F.avg_pool2d(X, kernel_size=2, padding=padding)
+            Y = F.avg_pool2d(Y, kernel_size=2, padding=padding)
+    vals.append(torch.relu(ssim_nc))
+    ms_nc = torch.prod(torch.stack(vals, dim=0) ** weights.view(-1, 1, 1), dim=0)
+    return ms_nc.mean() if size_average else ms_nc.mean(1)
+
+
+def ms_dssim_mse_loss(res, gt, win_size=11, win_sigma=1.5, weights=None, K=(0.01, 0.03)):
+    """nan_to_num(1 - ms_ssim2d(res, gt, data_range=1)) + mse, the multi-scale counterpart of dssim_mse_loss.
+    Returns (loss, dms, mse)."""
+    dms = 1.0 - ms_ssim2d(res, gt, data_range=1.0, size_average=True, win_size=win_size, win_sigma=win_sigma,
+                          weights=weights, K=K)
+    mse = F.mse_loss(res, gt)
+    return torch.nan_to_num(dms) + mse, dms, mse
+
+
+class _FusedMSDSSIMMSE(torch.autograd.Function):
+    """(loss, dms, mse) as one 3-element float32 tensor, as _FusedDSSIMMSE: the upstream gradients are read on the device."""
+
+    @staticmethod
+    def forward(ctx, res, gt, cfg):
+        from differender_amd import functional as DF
+        stats = DF.msssim_mse_fwd(res, gt, **cfg)
+        ctx.save_for_backward(res, gt, stats)
+        ctx.cfg = cfg
+        return stats[-3:].float()
+
+    @staticmethod
+    def backward(ctx, g3):
+        from differender_amd import functional as DF
+        res, gt, stats = ctx.saved_tensors
+        gx, gy = DF.msssim_mse_bwd(res, gt, stats, upstream=g3, want_ref_grad=ctx.needs_input_grad[1], **ctx.cfg)
+        return (gx if ctx.needs_input_grad[0] else None), gy, None
+
+
+def fused_ms_dssim_mse_loss(res, gt, data_range=1.0, win_size=11, win_sigma=1.5, weights=None, K=(0.01, 0.03)):
+    """ms_dssim_mse_loss on the HIP kernels: returns (loss, dms, mse), 0-d float32 tensors, with
+    loss = nan_to_num(1 - ms_ssim2d(res, gt, data_range, ...)) + mse_loss(res, gt). Differentiable w.r.t. res and, when it
+    requires a gradient, gt. res and gt: (N, C, H, W) float32 on a ROCm GPU (there is no CPU path)."""
+    if res.ndim != 4 or gt.shape != res.shape:
+        raise ValueError("fused_ms_dssim_mse_loss expects two (N, C, H, W) tensors of the same shape")
+    if res.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise TypeError("fused_ms_dssim_mse_loss expects float32 tensors")
+    if not (res.is_cuda and gt.is_cuda):
+        raise RuntimeError("fused_ms_dssim_mse_loss runs on a ROCm GPU only: there is no CPU path")
+    cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma,
+               weights=tuple(float(w) for w in (MS_SSIM_WEIGHTS if weights is None else weights)), K=tuple(K))
+    loss, dms, mse = _FusedMSDSSIMMSE.apply(res, gt, cfg).unbind(0)
+    return loss, dms, mse

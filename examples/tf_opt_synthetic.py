@@ -4,7 +4,8 @@ synthetic data: fit a transfer function to a reference render with momentum grad
 is render -> loss + d(loss)/d(image) -> backward -> momentum step, all through the C ABI
 (dr_march_fwd, dr_mse_loss_grad, dr_march_bwd, dr_tf_momentum_step): no host round trip in the loop.
 --loss dssim fits with the demo's loss nan_to_num(1 - ssim) + mse instead (OPT.py:70-72; dr_dssim_mse_fwd / _bwd),
-read straight from the march's [view][W][H][4] output through strides."""
+read straight from the march's [view][W][H][4] output through strides; --loss msssim with nan_to_num(1 - ms_ssim) + mse
+(dr_msssim_mse_fwd / _bwd; needs --img > 160)."""
 import argparse
 import os
 import sys
@@ -27,7 +28,7 @@ if __name__ == "__main__":
     ap.add_argument("--mom", type=float, default=0.8)
     ap.add_argument("--clip-grads", type=float, default=1.0)
     ap.add_argument("--bw-sampling-rate", type=float, default=1.0)
-    ap.add_argument("--loss", choices=("mse", "dssim"), default="mse")
+    ap.add_argument("--loss", choices=("mse", "dssim", "msssim"), default="mse")
     args = ap.parse_args()
     dev = torch.device("cuda")
     N, R, WH, S = args.vol, args.tf_res, (args.img, args.img), 1 << 20
@@ -50,8 +51,10 @@ if __name__ == "__main__":
             loss, g = F.mse_loss_grad(out, ref)
         else:
             # the march buffer [view][W][H][4] read in place as (view, 4, H, W): the rendered image up to a vertical flip, which
-            # neither SSIM (symmetric window) nor MSE sees; the gradient comes back in the buffer's own layout
-            loss, _, _, g = F.dssim_mse_loss_grad(out.permute(0, 3, 2, 1), ref.permute(0, 3, 2, 1))
+            # neither SSIM (symmetric window) nor MSE sees (MS-SSIM only through the pooling of odd level sides); the gradient
+            # comes back in the buffer's own layout
+            loss_grad = F.dssim_mse_loss_grad if args.loss == "dssim" else F.msssim_mse_loss_grad
+            loss, _, _, g = loss_grad(out.permute(0, 3, 2, 1), ref.permute(0, 3, 2, 1))
             g = g.permute(0, 3, 2, 1)
         _, d_tf = F.march_bwd(vol, tf, cam, e, x, r, n, S, sr, g, out, want_vol=False, workspace=ws, tape=True)
         F.tf_momentum_step(tf, d_tf, mom, lr, args.mom, args.clip_grads)

@@ -273,6 +273,36 @@ int dr_dssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W,
                      double data_range, int win_size, double win_sigma, double K1, double K2, int flags,
                      const double *stats, const float *upstream3, float *grad_x, float *grad_y, void *stream);
 
+/* Multi-scale SSIM + MSE image loss and its gradient: nan_to_num(1 - ms_ssim(x, y, data_range, weights))
+ * + mse(x, y), fused, as differender_amd.utils.losses.ms_ssim2d / ms_dssim_mse_loss define it (pytorch_msssim.ms_ssim).
+ * Level 0 is (x, y); level l+1 is the 2x2 average pool of level l with padding (H_l % 2, W_l % 2), padded zeros counted.
+ * Each level takes the SSIM and CS (contrast-structure) maps of dr_dssim_mse_fwd's window; v[l][n][c] is the relu'd per-plane
+ * mean of CS for l < levels-1 and of SSIM at the last level; ms[n][c] = prod_l v^weights[l]; dms = 1 - mean(ms); mse over
+ * the level-0 images. The gradient follows torch's rules: a plane gets MS gradient only where all its v > 0, and only where
+ * dms is finite (nan_to_num).
+ *   x, y        f32, logical (N, C, H, W), element strides strides4[4] (a host array, shared by x, y and the gradients;
+ *               negative strides allowed: the march's [n_views][W][H][4] output is passed as it lies)
+ *   win_size    odd, <= 31, and min(H, W) > 16 (win_size - 1) (pytorch_msssim's condition, whatever `levels`)
+ *   weights     host array of `levels` finite weights > 0, 1 <= levels <= DR_MSSSIM_MAX_LEVELS
+ *   data_range  finite and > 0
+ *   workspace   dr_msssim_workspace_bytes(N, C, H, W, levels, want_grad_y) bytes on the device (want_grad_y: grad_y will be
+ *               non-NULL); NULL allowed when that is 0 (levels = 1). Scratch only: nothing is kept in it between calls.
+ *   stats       [(levels + 1) N C + 3] f64 on the device, WRITTEN (not accumulated): v[l][n][c], ms[n][c], loss, dms, mse
+ *   upstream3   (bwd) 3 f32 on the device: d loss, d dms, d mse of the caller's objective; NULL = (1, 0, 0)
+ *   grad_x      (bwd) [like x] f32, overwritten; grad_y nullable
+ * The forward is memset + (levels - 1) pooling launches + one tile launch + a finalize; the backward pools again and runs
+ * one launch per level with no atomics: its gradient is bitwise deterministic. No allocation, no host synchronisation.
+ * Returns 0 for dr_msssim_workspace_bytes' invalid arguments. */
+enum { DR_MSSSIM_MAX_LEVELS = 5 };
+size_t dr_msssim_workspace_bytes(int N, int C, int H, int W, int levels, int want_grad_y);
+int dr_msssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                      double data_range, int win_size, double win_sigma, double K1, double K2,
+                      const double *weights, int levels, void *workspace, double *stats, void *stream);
+int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                      double data_range, int win_size, double win_sigma, double K1, double K2,
+                      const double *weights, int levels, const double *stats, const float *upstream3,
+                      float *grad_x, float *grad_y, void *workspace, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
