@@ -30,12 +30,37 @@ __device__ __forceinline__ void build_window(int k, float sigma_den, float *w) {
     __syncthreads();
 }
 
-// Every workgroup filters its tile shifted by one of its own pixels, (x - cx, y - cy): sigma^2 = E[x^2] - E[x]^2 cancels in
-// f32 when the mean is large against the spread (a flat region gives 1e-4 of noise in the loss unshifted); shifted it is
-// computed from small numbers. The means are put back as mu = G(x - c) + c sum(w), the shift leaves the maths unchanged.
-__device__ __forceinline__ float tile_shift(const float *p, int64_t o) {
-    const float c = p[o];
-    return isfinite(c) ? c : 0.0f;
+// Every workgroup filters its tile shifted by one constant, (x - c, y - c): sigma^2 = E[x^2] - E[x]^2 cancels in f32 when the
+// mean is large against the spread (a flat region gives 1e-4 of noise in the loss unshifted). c = clamp(0, lo, hi), [lo, hi]
+// the range of the finite in-image pixels of both staged tiles (0 when there are none), so |v - c| <= |v| for every pixel:
+// the shifted moments are never larger than torch's unshifted ones, and a tile away from 0 is taken from its nearest level.
+// (One pixel of the tile would not do: on a bright pixel every dark window of the tile cancels, and a tile mean puts the
+// flat black half of a tile off 0.) The means are put back as mu = G(x - c) + c sum(w); the shift leaves the maths unchanged.
+// Min and max are exact and order-free, so c, and with it the gradient, is the same run to run.
+__device__ __forceinline__ void range_add(float v, float &lo, float &hi) {   // lo = +inf, hi = -inf to start
+    if (isfinite(v)) {
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+}
+__device__ __forceinline__ float block_shift(float lo, float hi, float *red) {   // red: 2 NT/64 floats; c in every thread
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = lo;
+        red[NT / 64 + (threadIdx.x >> 6)] = hi;
+    }
+    __syncthreads();
+    lo = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    hi = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    return lo <= hi ? fminf(fmaxf(0.0f, lo), hi) : 0.0f;
+}
+// the staged tile (n floats) shifted in place, between block_shift's barrier and the caller's before the first pass over it.
+// The zeros beyond the image become -c: they feed only outputs that do not exist.
+__device__ __forceinline__ void shift_tile(float *t, int n, float c) {
+    for (int i = threadIdx.x; i < n; i += NT) t[i] -= c;
 }
 __device__ __forceinline__ float window_mass(const float *wv, int kh, const float *wh, int kw) {   // G applied to a constant 1
     float sv = 0.0f, s = 0.0f;

@@ -52,6 +52,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
     extern __shared__ float lds[];
     __shared__ float wg[KMAX + 1];
     __shared__ double red[2][NT / 64];
+    __shared__ float rng[2 * NT / 64];
     const int tile = blockIdx.x % P.tiles, plane = blockIdx.x / P.tiles;
     const int x0 = (tile % P.tiles_x) * TX, y0 = (tile / P.tiles_x) * P.TY;
     const int TY = P.TY, kh = P.kh, kw = P.kw, IH = TY + kh - 1, IW = TX + kw - 1;
@@ -64,9 +65,8 @@ __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
     // the tile's input with its halo (zeros beyond the image feed only output positions that do not exist); the squared error
     // of the pixels this tile owns: its own 64 x TY block, and up to the image edge for the last tile of a row / column
     const bool last_x = x0 + TX >= P.Wo, last_y = y0 + TY >= P.Ho;
-    const int64_t o0 = y0 * P.s2 + x0 * P.s3;
-    const float cx = tile_shift(xp, o0), cy = tile_shift(yp, o0), sw = window_mass(wv, kh, wh, kw);
-    float se = 0.0f;
+    const float sw = window_mass(wv, kh, wh, kw);
+    float se = 0.0f, lo = INFINITY, hi = -INFINITY;
     for (int i = threadIdx.x; i < IH * IW; i += NT) {
         const int r = i / IW, c = i - r * IW, gy = y0 + r, gx = x0 + c;
         float xv = 0.0f, yv = 0.0f;
@@ -78,12 +78,14 @@ __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
                 const float d = xv - yv;
                 se += d * d;
             }
-            xv -= cx;
-            yv -= cy;
+            range_add(xv, lo, hi);
+            range_add(yv, lo, hi);
         }
         in_x[i] = xv;
         in_y[i] = yv;
     }
+    const float sh = block_shift(lo, hi, rng);   // the tile's shift
+    shift_tile(lds, 2 * IH * IW, sh);
     __syncthreads();
     // vertical pass (along H) of the five moments, on every column of the tile's input
     const int nV = TY * IW;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f;
         for (int j = 0; j < kh; ++j) {
             const float w = wv[j], xv = in_x[(b + j) * IW + c], yv = in_y[(b + j) * IW + c];
-            a0 += w * xv; a1 += w * yv; a2 += w * (xv * xv); a3 += w * (yv * yv); a4 += w * (xv * yv);
+            a0 = fmaf(w, xv, a0); a1 = fmaf(w, yv, a1); a2 = fmaf(w, xv * xv, a2); a3 = fmaf(w, yv * yv, a3); a4 = fmaf(w, xv * yv, a4);
         }
         V[i] = a0; V[nV + i] = a1; V[2 * nV + i] = a2; V[3 * nV + i] = a3; V[4 * nV + i] = a4;
     }
@@ -107,9 +109,9 @@ __global__ __launch_bounds__(NT) void dssim_mse_fwd_kernel(LossParams P) {
             const float w = wh[j];
             const int o = b * IW + a + j;
 #pragma unroll
-            for (int q = 0; q < 5; ++q) m[q] += w * V[q * nV + o];
+            for (int q = 0; q < 5; ++q) m[q] = fmaf(w, V[q * nV + o], m[q]);
         }
-        const float mu1 = m[0] + cx * sw, mu2 = m[1] + cy * sw;
+        const float mu1 = m[0] + sh * sw, mu2 = m[1] + sh * sw;
         const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
         const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
         const float cs = (2.0f * s12 + P.C2) / (s1 + s2 + P.C2);
@@ -153,6 +155,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_finalize_kernel(LossParams P) {
 __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
     extern __shared__ float lds[];
     __shared__ float wg[KMAX + 1];
+    __shared__ float rng[2 * NT / 64];
     const int tile = blockIdx.x % P.tiles, plane = blockIdx.x / P.tiles;
     const int x0 = (tile % P.tiles_x) * TX, y0 = (tile / P.tiles_x) * P.TY;
     const int TY = P.TY, kh = P.kh, kw = P.kw;
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
 
     const float *wv = P.kh == 1 ? wg + KMAX : wg, *wh = P.kw == 1 ? wg + KMAX : wg;
     const float *Tt = nullptr;
-    float cx = 0.0f, cy = 0.0f;
+    float sh = 0.0f;
     // (workgroup-uniform) no SSIM gradient for this plane: the mse term alone, and no 0 * NaN from the moments
     if (g != 0.0f) {
         const int IH = TY + 2 * (kh - 1), IW = TX + 2 * (kw - 1), QH = TY + kh - 1, QW = TX + kw - 1;
@@ -177,21 +180,23 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
         float *in_x = lds, *in_y = lds + IH * IW, *Dm = lds;   // region 1: the input, then the adjoint maps Dm[4][QH][QW]
         float *V = lds + r1;                                     // region 2: the vertical moments V[5][QH][IW], then Tt[4][QH][TX]
         build_window(P.k, P.sigma_den, wg);
-        const int64_t o0 = y0 * P.s2 + x0 * P.s3;
-        cx = tile_shift(xp, o0);
-        cy = tile_shift(yp, o0);
         const float sw = window_mass(wv, kh, wh, kw);
+        float lo = INFINITY, hi = -INFINITY;
         for (int i = threadIdx.x; i < IH * IW; i += NT) {
             const int r = i / IW, c = i - r * IW, gy = y0 - (kh - 1) + r, gx = x0 - (kw - 1) + c;
             float xv = 0.0f, yv = 0.0f;
             if (gy >= 0 && gy < P.H && gx >= 0 && gx < P.W) {
                 const int64_t o = gy * P.s2 + gx * P.s3;
-                xv = xp[o] - cx;
-                yv = yp[o] - cy;
+                xv = xp[o];
+                yv = yp[o];
+                range_add(xv, lo, hi);
+                range_add(yv, lo, hi);
             }
             in_x[i] = xv;
             in_y[i] = yv;
         }
+        sh = block_shift(lo, hi, rng);
+        shift_tile(lds, 2 * IH * IW, sh);
         __syncthreads();
         const int nV = QH * IW;
         for (int i = threadIdx.x; i < nV; i += NT) {
@@ -199,7 +204,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f;
             for (int j = 0; j < kh; ++j) {
                 const float w = wv[j], xv = in_x[(b + j) * IW + c], yv = in_y[(b + j) * IW + c];
-                a0 += w * xv; a1 += w * yv; a2 += w * (xv * xv); a3 += w * (yv * yv); a4 += w * (xv * yv);
+                a0 = fmaf(w, xv, a0); a1 = fmaf(w, yv, a1); a2 = fmaf(w, xv * xv, a2); a3 = fmaf(w, yv * yv, a3); a4 = fmaf(w, xv * yv, a4);
             }
             V[i] = a0; V[nV + i] = a1; V[2 * nV + i] = a2; V[3 * nV + i] = a3; V[4 * nV + i] = a4;
         }
@@ -215,10 +220,10 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
                     const float w = wh[j];
                     const int o = b * IW + a + j;
 #pragma unroll
-                    for (int q = 0; q < 5; ++q) m[q] += w * V[q * nV + o];
+                    for (int q = 0; q < 5; ++q) m[q] = fmaf(w, V[q * nV + o], m[q]);
                 }
-                // A from the means, B from the shifted moments (m[0], m[1] = mu1 - cx sum(w), mu2 - cy sum(w))
-                const float mu1 = m[0] + cx * sw, mu2 = m[1] + cy * sw;
+                // A from the means, B from the shifted moments (m[0], m[1] = mu1 - sh sum(w), mu2 - sh sum(w))
+                const float mu1 = m[0] + sh * sw, mu2 = m[1] + sh * sw;
                 const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
                 const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
                 const float a2 = mu1_sq + mu2_sq + P.C1, b2 = s1 + s2 + P.C2;
@@ -266,7 +271,7 @@ __global__ __launch_bounds__(NT) void dssim_mse_bwd_kernel(LossParams P) {
                 for (int q = 0; q < 4; ++q) r[q] += w * Tt[q * nT + t];
             }
         }
-        const float xs = xv - cx, ys = yv - cy;   // the chain through the shifted x^2 and xy
+        const float xs = xv - sh, ys = yv - sh;   // the chain through the shifted x^2 and xy
         P.gx[base + o] = r[0] + 2.0f * xs * r[2] + ys * r[3] + e;
         if (P.gy) P.gy[base + o] = r[1] + 2.0f * ys * r[2] + xs * r[3] - e;
     }

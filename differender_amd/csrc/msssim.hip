@@ -84,6 +84,7 @@ __global__ __launch_bounds__(NT) void msssim_fwd_kernel(MSParams P) {
     extern __shared__ float lds[];
     __shared__ float wg[KMAX + 1];
     __shared__ double red[2][NT / 64];
+    __shared__ float rng[2 * NT / 64];
     int l = 0;
     for (int i = 1; i < P.L; ++i)
         if ((int)blockIdx.x >= P.lv[i].block0) l = i;
@@ -101,9 +102,8 @@ __global__ __launch_bounds__(NT) void msssim_fwd_kernel(MSParams P) {
     // squared error of the pixels this tile owns: its own 64 x TY block, and up to the image edge for the last tile of a row /
     // column
     const bool last_x = x0 + TX >= V.Wo, last_y = y0 + TY >= V.Ho;
-    const int64_t o0 = y0 * V.s2 + x0 * V.s3;
-    const float cx = tile_shift(xp, o0), cy = tile_shift(yp, o0), sw = window_mass(wg, k, wg, k);
-    float se = 0.0f;
+    const float sw = window_mass(wg, k, wg, k);
+    float se = 0.0f, lo = INFINITY, hi = -INFINITY;
     for (int i = threadIdx.x; i < IH * IW; i += NT) {
         const int r = i / IW, c = i - r * IW, gy = y0 + r, gx = x0 + c;
         float xv = 0.0f, yv = 0.0f;
@@ -115,12 +115,14 @@ __global__ __launch_bounds__(NT) void msssim_fwd_kernel(MSParams P) {
                 const float d = xv - yv;
                 se += d * d;
             }
-            xv -= cx;
-            yv -= cy;
+            range_add(xv, lo, hi);
+            range_add(yv, lo, hi);
         }
         in_x[i] = xv;
         in_y[i] = yv;
     }
+    const float sh = block_shift(lo, hi, rng);   // the tile's shift
+    shift_tile(lds, 2 * IH * IW, sh);
     __syncthreads();
     const int nV = TY * IW;
     for (int i = threadIdx.x; i < nV; i += NT) {
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(NT) void msssim_fwd_kernel(MSParams P) {
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f;
         for (int j = 0; j < k; ++j) {
             const float w = wg[j], xv = in_x[(b + j) * IW + c], yv = in_y[(b + j) * IW + c];
-            a0 += w * xv; a1 += w * yv; a2 += w * (xv * xv); a3 += w * (yv * yv); a4 += w * (xv * yv);
+            a0 = fmaf(w, xv, a0); a1 = fmaf(w, yv, a1); a2 = fmaf(w, xv * xv, a2); a3 = fmaf(w, yv * yv, a3); a4 = fmaf(w, xv * yv, a4);
         }
         Vm[i] = a0; Vm[nV + i] = a1; Vm[2 * nV + i] = a2; Vm[3 * nV + i] = a3; Vm[4 * nV + i] = a4;
     }
@@ -143,12 +145,12 @@ __global__ __launch_bounds__(NT) void msssim_fwd_kernel(MSParams P) {
             const float w = wg[j];
             const int o = b * IW + a + j;
 #pragma unroll
-            for (int q = 0; q < 5; ++q) m[q] += w * Vm[q * nV + o];
+            for (int q = 0; q < 5; ++q) m[q] = fmaf(w, Vm[q * nV + o], m[q]);
         }
         const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
         const float cs = (2.0f * s12 + P.C2) / (s1 + s2 + P.C2);
         if (last) {
-            const float mu1 = m[0] + cx * sw, mu2 = m[1] + cy * sw;
+            const float mu1 = m[0] + sh * sw, mu2 = m[1] + sh * sw;
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
             ss += ((2.0f * mu12 + P.C1) / (mu1_sq + mu2_sq + P.C1)) * cs;
         } else {
@@ -199,6 +201,7 @@ __global__ __launch_bounds__(NT) void msssim_finalize_kernel(MSParams P) {
 __global__ __launch_bounds__(NT) void msssim_bwd_kernel(MSParams P, int l) {
     extern __shared__ float lds[];
     __shared__ float wg[KMAX + 1];
+    __shared__ float rng[2 * NT / 64];
     const MSLevel &V = P.lv[l];
     const int tile = blockIdx.x % V.tiles, plane = blockIdx.x / V.tiles;
     const int x0 = (tile % V.tiles_x) * TX, y0 = (tile / V.tiles_x) * P.TY;
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(NT) void msssim_bwd_kernel(MSParams P, int l) {
     const float wm = l == 0 ? (float)(2.0 * (u0 + u2) * P.inv_numel) : 0.0f;
 
     const float *Tt = nullptr;
-    float cx = 0.0f, cy = 0.0f;
+    float sh = 0.0f;
     // (workgroup-uniform) no MS gradient for this plane: skip the moments, and with them any 0 * NaN
     if (g != 0.0f) {
         const int IH = TY + 2 * (k - 1), IW = TX + 2 * (k - 1), QH = TY + k - 1, QW = TX + k - 1;
@@ -229,21 +232,23 @@ __global__ __launch_bounds__(NT) void msssim_bwd_kernel(MSParams P, int l) {
         float *in_x = lds, *in_y = lds + IH * IW, *Dm = lds;   // region 1: the input, then the adjoint maps Dm[4][QH][QW]
         float *Vm = lds + r1;                                    // region 2: the vertical moments Vm[5][QH][IW], then Tt[4][QH][TX]
         build_window(k, P.sigma_den, wg);
-        const int64_t o0 = y0 * V.s2 + x0 * V.s3;
-        cx = tile_shift(xp, o0);
-        cy = tile_shift(yp, o0);
         const float sw = window_mass(wg, k, wg, k);
+        float lo = INFINITY, hi = -INFINITY;
         for (int i = threadIdx.x; i < IH * IW; i += NT) {
             const int r = i / IW, c = i - r * IW, gy = y0 - (k - 1) + r, gx = x0 - (k - 1) + c;
             float xv = 0.0f, yv = 0.0f;
             if (gy >= 0 && gy < V.H && gx >= 0 && gx < V.W) {
                 const int64_t o = gy * V.s2 + gx * V.s3;
-                xv = xp[o] - cx;
-                yv = yp[o] - cy;
+                xv = xp[o];
+                yv = yp[o];
+                range_add(xv, lo, hi);
+                range_add(yv, lo, hi);
             }
             in_x[i] = xv;
             in_y[i] = yv;
         }
+        sh = block_shift(lo, hi, rng);
+        shift_tile(lds, 2 * IH * IW, sh);
         __syncthreads();
         const int nV = QH * IW;
         for (int i = threadIdx.x; i < nV; i += NT) {
@@ -251,7 +256,7 @@ __global__ __launch_bounds__(NT) void msssim_bwd_kernel(MSParams P, int l) {
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f;
             for (int j = 0; j < k; ++j) {
                 const float w = wg[j], xv = in_x[(b + j) * IW + c], yv = in_y[(b + j) * IW + c];
-                a0 += w * xv; a1 += w * yv; a2 += w * (xv * xv); a3 += w * (yv * yv); a4 += w * (xv * yv);
+                a0 = fmaf(w, xv, a0); a1 = fmaf(w, yv, a1); a2 = fmaf(w, xv * xv, a2); a3 = fmaf(w, yv * yv, a3); a4 = fmaf(w, xv * yv, a4);
             }
             Vm[i] = a0; Vm[nV + i] = a1; Vm[2 * nV + i] = a2; Vm[3 * nV + i] = a3; Vm[4 * nV + i] = a4;
         }
@@ -267,14 +272,14 @@ __global__ __launch_bounds__(NT) void msssim_bwd_kernel(MSParams P, int l) {
                     const float w = wg[j];
                     const int o = b * IW + a + j;
 #pragma unroll
-                    for (int q = 0; q < 5; ++q) m[q] += w * Vm[q * nV + o];
+                    for (int q = 0; q < 5; ++q) m[q] = fmaf(w, Vm[q * nV + o], m[q]);
                 }
-                // B from the shifted moments (m[0], m[1] = mu1 - cx sum(w), mu2 - cy sum(w)); A from the means
+                // B from the shifted moments (m[0], m[1] = mu1 - sh sum(w), mu2 - sh sum(w)); A from the means
                 const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
                 const float b2 = s1 + s2 + P.C2, B = (2.0f * s12 + P.C2) / b2;
                 const float gb = g / b2;
                 if (last) {
-                    const float mu1 = m[0] + cx * sw, mu2 = m[1] + cy * sw;
+                    const float mu1 = m[0] + sh * sw, mu2 = m[1] + sh * sw;
                     const float a2 = mu1 * mu1 + mu2 * mu2 + P.C1, A = (2.0f * (mu1 * mu2) + P.C1) / a2;
                     const float ga = g / a2;
                     d0 = 2.0f * B * (mu2 - mu1 * A) * ga + 2.0f * A * (m[0] * B - m[1]) * gb;
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(NT) void msssim_bwd_kernel(MSParams P, int l) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) r[q] += w * Tt[q * nT + t];
             }
-            const float xs = xp[o] - cx, ys = yp[o] - cy;   // the chain through the shifted x^2 and xy
+            const float xs = xp[o] - sh, ys = yp[o] - sh;   // the chain through the shifted x^2 and xy
             rx = r[0] + 2.0f * xs * r[2] + ys * r[3];
             ry = r[1] + 2.0f * ys * r[2] + xs * r[3];
         }
