@@ -20,6 +20,7 @@ DR_COUNT_EVALUATED = 0x400   # ... and of dr_march_bwd[_rows]: measurement only 
 DR_TAPE_TF = 0x800           # forward (DIFF) + the TF-only backward of the same inputs: per-sample tape of (intensity, lighting)
 DR_SSIM_NONNEGATIVE = 1      # flags of dr_dssim_mse_fwd / _bwd: relu on the per-plane SSIM
 DR_MSSSIM_MAX_LEVELS = 5     # levels of dr_msssim_mse_fwd / _bwd
+DR_TV_L1, DR_TV_ISO, DR_TV_SQ = 0, 1, 2   # norm of dr_tv3d_fwd / _bwd
 
 _c = ctypes
 _P, _I, _L, _F, _D, _U, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_double, _c.c_uint32, _c.c_size_t
@@ -57,6 +58,8 @@ SIGNATURES = {
     "dr_msssim_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "dr_msssim_mse_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _I, _D, _D, _D, _P, _I, _P, _P, _P]),
     "dr_msssim_mse_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _I, _D, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "dr_tv3d_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _D, _P, _P]),
+    "dr_tv3d_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _D, _P, _F, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -357,6 +357,47 @@ int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W
     return launch_msssim_mse_bwd(a, (hipStream_t)stream);
 }
 
+static int fill_tv(TVArgs &a, const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4, int norm,
+                   double eps) {
+    if (!vol || !strides4) return DR_EINVAL;
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return DR_EINVAL;
+    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
+    if (norm != DR_TV_L1 && norm != DR_TV_ISO && norm != DR_TV_SQ) return DR_EINVAL;
+    if (!std::isfinite(eps) || (norm == DR_TV_ISO && !(eps > 0.0))) return DR_EINVAL;
+    a = TVArgs{};
+    a.vol = vol; a.vol_dtype = vol_dtype; a.B = B; a.D = D; a.H = H; a.W = W;
+    for (int i = 0; i < 4; ++i) a.strides[i] = strides4[i];
+    a.norm = norm; a.eps = eps; a.scale = 1.0f;
+    return 0;
+}
+
+int dr_tv3d_fwd(const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4, int norm, double eps,
+                double *sum, void *stream) {
+    TVArgs a;
+    int rc = fill_tv(a, vol, vol_dtype, B, D, H, W, strides4, norm, eps);
+    if (rc) return rc;
+    if (!sum) return DR_EINVAL;
+    a.sum = sum;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_tv3d_fwd) return DR_EUNSUPPORTED;   // (a library linked without tv_loss.o)
+    return launch_tv3d_fwd(a, (hipStream_t)stream);
+}
+
+int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4, int norm, double eps,
+                const float *upstream, float scale, float *grad, const int64_t *grad_strides4, int accumulate, void *stream) {
+    TVArgs a;
+    int rc = fill_tv(a, vol, vol_dtype, B, D, H, W, strides4, norm, eps);
+    if (rc) return rc;
+    if (!grad || !grad_strides4 || !std::isfinite(scale)) return DR_EINVAL;
+    a.upstream = upstream; a.scale = scale; a.grad = grad; a.accumulate = accumulate != 0;
+    for (int i = 0; i < 4; ++i) a.grad_strides[i] = grad_strides4[i];
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_tv3d_bwd) return DR_EUNSUPPORTED;
+    return launch_tv3d_bwd(a, (hipStream_t)stream);
+}
+
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,
                         void *stream) {
     if (!tf || !d_tf || !momentum || n <= 0 || !(max_grad >= 0.0f)) return DR_EINVAL;

@@ -127,6 +127,24 @@ inline MSLayout msssim_layout(int N, int C, int H, int W, int levels, bool want_
 __attribute__((weak)) int launch_msssim_mse_fwd(const MSArgs &a, hipStream_t stream);
 __attribute__((weak)) int launch_msssim_mse_bwd(const MSArgs &a, hipStream_t stream);
 
+// 3-D total variation (tv_loss.hip): the arguments of dr_tv3d_fwd / dr_tv3d_bwd
+struct TVArgs {
+    const void *vol;
+    int vol_dtype, B, D, H, W;
+    int64_t strides[4];        // element strides of the logical (B, D, H, W)
+    int norm;                  // DR_TV_*
+    double eps;
+    double *sum;               // forward: written
+    const float *upstream;     // backward: d objective / d sum on the device, nullable = 1
+    float scale;
+    float *grad;               // backward
+    int64_t grad_strides[4];
+    int accumulate;
+};
+// weak, as launch_camera_grad: capi.o must load in a library linked without tv_loss.o
+__attribute__((weak)) int launch_tv3d_fwd(const TVArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_tv3d_bwd(const TVArgs &a, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

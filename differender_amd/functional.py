@@ -16,7 +16,7 @@ from . import _native as N
 
 __all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
-           "msssim_mse_loss_grad", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
+           "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 
 
 def _stream():
@@ -597,6 +597,90 @@ def msssim_mse_loss_grad(out, reference, data_range=1.0, win_size=11, win_sigma=
     grad, _ = msssim_mse_bwd(out, reference, stats, **cfg)
     loss, dms, mse = stats[-3:].unbind(0)
     return loss, dms, mse, grad
+
+
+_TV_NORMS = {"l1": N.DR_TV_L1, "iso": N.DR_TV_ISO, "sq": N.DR_TV_SQ}
+
+
+def _tv_config(norm, eps):
+    if norm not in _TV_NORMS:
+        raise ValueError(f"norm must be one of {sorted(_TV_NORMS)}, got {norm!r}")
+    eps = float(eps)
+    if not math.isfinite(eps) or (norm == "iso" and not eps > 0.0):
+        raise ValueError(f"eps must be finite (and > 0 for norm='iso'), got {eps}")
+    return _TV_NORMS[norm], eps
+
+
+def _tv_strides(t):
+    """(B, D, H, W, int64 strides[4]) of t's last three axes and its leading axes taken as one, or None when the leading axes
+    do not collapse into one stride."""
+    lead = [(n, s) for n, s in zip(t.shape[:-3], t.stride()[:-3]) if n > 1]
+    for (n0, s0), (n1, s1) in zip(lead, lead[1:]):
+        if s0 != n1 * s1:
+            return None
+    b = math.prod(t.shape[:-3])
+    sb = lead[-1][1] if lead else 0
+    return (b, *t.shape[-3:], (ctypes.c_int64 * 4)(sb, *t.stride()[-3:]))
+
+
+def _tv_volume(vol):
+    if vol.ndim < 3:
+        raise ValueError(f"the TV regulariser expects a volume (..., D, H, W), got {vol.ndim} dimensions")
+    _require_gpu(vol, "vol")
+    if vol.dtype == torch.float32:
+        tag = N.DR_F32
+    elif vol.dtype == torch.float16:
+        tag = N.DR_F16
+    else:
+        raise TypeError(f"the TV regulariser reads float32 or float16 volumes, got {vol.dtype}")
+    geo = _tv_strides(vol)
+    if geo is None:   # leading axes that no single stride describes: one copy
+        vol = vol.contiguous()
+        geo = _tv_strides(vol)
+    return vol, tag, geo
+
+
+def tv3d_fwd(vol, norm="l1", eps=1e-3):
+    """Sum over the voxels of the 3-D total variation of `vol` (dr_tv3d_fwd; differender_amd.utils.tv3d with
+    reduction="sum"). vol: (..., D, H, W) float32 or float16 on the GPU, any strides. Returns a 0-d float64 tensor on the
+    device."""
+    n, e = _tv_config(norm, eps)
+    vol, tag, (b, d, h, w, strides) = _tv_volume(vol)
+    out = torch.empty((), dtype=torch.float64, device=vol.device)
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_tv3d_fwd(vol.data_ptr(), tag, b, d, h, w, strides, n, e, out.data_ptr(), _stream())
+    N.check(rc, "dr_tv3d_fwd")
+    return out
+
+
+def tv3d_bwd(vol, upstream=None, scale=1.0, norm="l1", eps=1e-3, out=None, accumulate=False):
+    """Gradient of tv3d_fwd's sum (dr_tv3d_bwd): out = (out if accumulate else 0) + upstream * scale * dTV/dvol, float32, shaped
+    like vol. `upstream`: one float32 on the device (None = 1), read there (no host synchronisation). `out` may be any
+    float32 tensor of vol's shape whose elements do not overlap (e.g. the d_volume of the march); None allocates one in vol's
+    stride order. Bitwise deterministic."""
+    n, e = _tv_config(norm, eps)
+    vol, tag, (b, d, h, w, strides) = _tv_volume(vol)
+    if upstream is not None:
+        upstream = upstream.to(device=vol.device, dtype=torch.float32).contiguous()
+        if upstream.numel() != 1:
+            raise ValueError("upstream is the gradient of the scalar TV sum: 1 element")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs `out`")
+        out = torch.empty_like(vol, dtype=torch.float32)
+        if not _dense(out) or _tv_strides(out) is None:
+            out = torch.empty(vol.shape, dtype=torch.float32, device=vol.device)
+    if out.shape != vol.shape or out.dtype != torch.float32 or out.device != vol.device:
+        raise ValueError("out must be a float32 tensor of vol's shape on vol's device")
+    gstrides = _tv_strides(out)
+    if gstrides is None or not _dense(out):
+        raise ValueError("out must not have overlapping elements, and its leading axes must collapse into one stride")
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_tv3d_bwd(vol.data_ptr(), tag, b, d, h, w, strides, n, e,
+                                 None if upstream is None else upstream.data_ptr(), float(scale), out.data_ptr(),
+                                 gstrides[-1], int(bool(accumulate)), _stream())
+    N.check(rc, "dr_tv3d_bwd")
+    return out
 
 
 def tf_momentum_step(tf, d_tf, momentum, lr, gamma, max_grad):

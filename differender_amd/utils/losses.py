@@ -13,12 +13,17 @@ ssim2d / dssim_mse_loss as its definition.
 `ms_ssim2d` restates `pytorch_msssim.ms_ssim`, the package's multi-scale SSIM, from the same memory [mem: parity unpinned]:
 per level the SSIM and contrast-structure (CS) maps of ssim2d and their per-plane means, relu'd; 2x2 average pooling between
 levels; the weighted product over the levels. `fused_ms_dssim_mse_loss` is ms_dssim_mse_loss on the HIP kernels (DESIGN.md
-D10)."""
+D10).
+
+`tv3d` is the 3-D total-variation prior on a volume, the regulariser of a volume reconstruction such as the
+demo's (salt noise in `vol`, examples/vol_denoise_tv_synthetic.py); `fused_tv3d_loss` is tv3d on the HIP kernels. With
+differender_amd.distributed.all_reduce_gradients, add the term on one rank only (or after the reduce): otherwise it is counted
+once per rank."""
 import torch
 import torch.nn.functional as F
 
 __all__ = ["ssim2d", "dssim_mse_loss", "fused_dssim_mse_loss", "MS_SSIM_WEIGHTS", "ms_ssim2d", "ms_dssim_mse_loss",
-           "fused_ms_dssim_mse_loss"]
+           "fused_ms_dssim_mse_loss", "tv3d", "fused_tv3d_loss"]
 
 
 def _gauss_window(size, sigma, dtype, device):
@@ -184,3 +189,70 @@ def fused_ms_dssim_mse_loss(res, gt, data_range=1.0, win_size=11, win_sigma=1.5,
                weights=tuple(float(w) for w in (MS_SSIM_WEIGHTS if weights is None else weights)), K=tuple(K))
     loss, dms, mse = _FusedMSDSSIMMSE.apply(res, gt, cfg).unbind(0)
     return loss, dms, mse
+
+
+TV_NORMS = ("l1", "iso", "sq")
+
+
+def tv3d(vol, norm="l1", eps=1e-3, reduction="mean"):
+    """3-D total variation of vol (..., D, H, W); the leading axes are separate volumes. Forward differences along each of the
+    last three axes with the last slice repeated (0 at the far edge), per voxel |dD| + |dH| + |dW| ("l1", anisotropic),
+    sqrt(dD^2 + dH^2 + dW^2 + eps^2) ("iso", Charbonnier, eps > 0) or dD^2 + dH^2 + dW^2 ("sq", Tikhonov); summed
+    (reduction="sum") or divided by vol.numel() ("mean"). Plain torch: any device, any float dtype; autograd gives the
+    gradient (sign(0) = 0 for "l1"). This is the definition fused_tv3d_loss and dr_tv3d_fwd / _bwd implement."""
+    if vol.ndim < 3:
+        raise ValueError(f"tv3d expects a volume (..., D, H, W), got {vol.ndim} dimensions")
+    if norm not in TV_NORMS:
+        raise ValueError(f"norm must be one of {TV_NORMS}, got {norm!r}")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    d = [torch.diff(vol, dim=a, append=vol.narrow(a, vol.shape[a] - 1, 1)) for a in (-3, -2, -1)]
+    if norm == "l1":
+        t = d[0].abs() + d[1].abs() + d[2].abs()
+    elif norm == "sq":
+        t = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+    else:
+        if not eps > 0:
+            raise ValueError(f"norm='iso' needs eps > 0, got {eps}")
+        t = torch.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + eps * eps)
+    s = t.sum()
+    return s / vol.numel() if reduction == "mean" else s
+
+
+class _FusedTV3D(torch.autograd.Function):
+    """The TV sum from dr_tv3d_fwd, times `scale`, as a 0-d float32; backward hands the upstream gradient to dr_tv3d_bwd on the
+    device (no host read)."""
+
+    @staticmethod
+    def forward(ctx, vol, norm, eps, scale):
+        from differender_amd import functional as DF
+        total = DF.tv3d_fwd(vol, norm, eps)
+        ctx.save_for_backward(vol)
+        ctx.cfg = (norm, eps, scale)
+        return (total * scale).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        from differender_amd import functional as DF
+        (vol,) = ctx.saved_tensors
+        norm, eps, scale = ctx.cfg
+        grad = DF.tv3d_bwd(vol, upstream=g, scale=scale, norm=norm, eps=eps)
+        return grad.to(vol.dtype), None, None, None
+
+
+def fused_tv3d_loss(vol, norm="l1", eps=1e-3, reduction="mean"):
+    """tv3d on the HIP kernels: a 0-d float32 tensor, differentiable w.r.t. vol (the gradient comes back in vol's dtype and
+    shape). vol: (..., D, H, W) float32 or float16 on a ROCm GPU (there is no CPU path), any strides -- Raycaster's user
+    layouts (1, D, H, W) and (BS, 1, D, H, W) and its permuted views included."""
+    if vol.ndim < 3:
+        raise ValueError(f"fused_tv3d_loss expects a volume (..., D, H, W), got {vol.ndim} dimensions")
+    if vol.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"fused_tv3d_loss expects a float32 or float16 volume, got {vol.dtype}")
+    if not vol.is_cuda:
+        raise RuntimeError("fused_tv3d_loss runs on a ROCm GPU only: there is no CPU path")
+    if norm not in TV_NORMS:
+        raise ValueError(f"norm must be one of {TV_NORMS}, got {norm!r}")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    scale = 1.0 / vol.numel() if reduction == "mean" else 1.0
+    return _FusedTV3D.apply(vol, norm, float(eps), scale)

@@ -303,6 +303,30 @@ int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W
                       const double *weights, int levels, const double *stats, const float *upstream3,
                       float *grad_x, float *grad_y, void *workspace, void *stream);
 
+/* 3-D total variation of a volume and its gradient, as differender_amd.utils.losses.tv3d defines it: forward
+ * differences d_a along each of the three axes D, H, W of every volume with the last slice repeated (so d_a = 0 at the far edge
+ * and an axis of extent 1 contributes nothing; no difference crosses from one volume of the batch into the next), per voxel
+ *   DR_TV_L1   |dD| + |dH| + |dW|                       (anisotropic)
+ *   DR_TV_ISO  sqrt(dD^2 + dH^2 + dW^2 + eps^2)         (isotropic, Charbonnier; eps > 0)
+ *   DR_TV_SQ   dD^2 + dH^2 + dW^2                       (quadratic, Tikhonov)
+ * summed over the voxels of all B volumes. Arithmetic in f32, the sum in f64.
+ *   vol       DR_F32 or DR_F16, logical (B, D, H, W) with the int64 element strides strides4[4] (a host array; any order:
+ *             Raycaster's permuted (W, D, H) view and d_vol of dr_march_bwd need no copy)
+ *   sum       (fwd) one f64 on the device, WRITTEN (not accumulated); a NaN in vol gives a NaN sum
+ *   upstream  (bwd) one f32 on the device, d objective / d sum; NULL = 1
+ *   grad      (bwd) f32, logical (B, D, H, W) with the strides grad_strides4[4], no two voxels on one element, not aliasing vol:
+ *             grad = (accumulate ? grad : 0) + (*upstream) * scale * dTV/dvol, with sign(0) = 0 for DR_TV_L1. accumulate lets a
+ *             caller add the regulariser straight into the d_vol of dr_march_bwd.
+ * Invalid arguments (null pointers, extents <= 0, an unknown norm or dtype, a non-finite eps or scale, eps <= 0 with DR_TV_ISO)
+ * return DR_EINVAL before any HIP call. One launch each (after a memset of sum in the forward), no allocation, no host
+ * synchronisation; the backward has no atomics and its gradient is bitwise deterministic. */
+enum { DR_TV_L1 = 0, DR_TV_ISO = 1, DR_TV_SQ = 2 };
+int dr_tv3d_fwd(const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4,
+                int norm, double eps, double *sum, void *stream);
+int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4,
+                int norm, double eps, const float *upstream, float scale, float *grad,
+                const int64_t *grad_strides4, int accumulate, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
