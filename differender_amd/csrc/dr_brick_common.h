@@ -374,6 +374,15 @@ __device__ __forceinline__ bool segment_range(const BrickCtx &c, f3 cam, f3 vd, 
 //       many ulps. (A mean that DRIFTS leaves a sawtooth of roundings that cancels but for a partial cycle of random sign; charging
 //       those remainders was tried and flagged thousands of rays whose true error was below 1e-6 -- a segment's sample count says
 //       nothing about how many of its samples contribute at all: profiles/r06_ab_experiments.txt. They belong to the random walk.)
+//   (2') a COLOUR segment whose mean contribution per sample is below half an ulp of the value after it and within half of itself
+//       of the previous segment's mean: min(contribution, samples * ulp / 2), i.e. its whole partial,
+//       added linearly like (1). Its contributions may all be dropped: a nearly black TF colour of ordinary opacity behind a bright
+//       structure (tests/test_gpu_d4_dim_shell.py; up to 5e-5 per ray at 256^3, rate 8, before this term). The steadiness keeps
+//       out SPARSE segments -- a few ordinary samples among many of opacity 0, or among the skipped ones of a non-differentiable
+//       march -- whose small mean hides samples far above an ulp: charged, they sent 84 of 65 536 faint tf1 rays to the exact pass
+//       at 256^3, rate 8, non-differentiable (the preset test allows 65). (Alpha needs no such term: an ordinary opacity, >= DR_D4_TINY_OP, adds
+//       T * op >= 1e-6 to alpha before a ray terminates -- 17 ulps and more; only tiny ones can fall below an ulp, and (1) counts
+//       those.)
 //   (3) long rays: the random walk of the sequential roundings alone (0.29 ulp per sample; the ulp of the ray's largest final
 //       channel bounds every running value's) leaves no room under the 1e-5 bar once 3 sigma = 0.87 ulp sqrt(samples) passes
 //       DR_D4_WALK = 5.7e-6 -- 12 000 samples of a composite in [0.5, 1), 3 000 of a colour in [1, 2) (unclamped highlights of the
@@ -381,8 +390,9 @@ __device__ __forceinline__ bool segment_range(const BrickCtx &c, f3 cam, f3 vd, 
 // An error in alpha also moves every later contribution: bound(alpha) * later partial (the callers add that). A ray whose bound
 // exceeds DR_D4_BUDGET has its pixel recomputed sample by sample (ray_exact_kernel); in the crossing search the bound widens the
 // band inside which the early-termination decision is repeated exactly.
-// Not covered: colour contributions below half an ulp from samples of ORDINARY opacity (a nearly black TF colour behind a bright
-// structure): their number is not known per segment, and a small mean alone cannot tell them from a sparse segment.
+// Covered by (2'): colour contributions below half an ulp from samples of ORDINARY opacity (a nearly black TF colour behind a bright
+// structure) -- their number is not known per segment, so a small, steady mean is charged with the whole partial. Not covered:
+// such samples in a segment whose mean a few lit samples lift above half an ulp (their number is not known per segment either).
 #ifdef DR_D4_BUDGET_OVERRIDE   // (what-if builds: a huge budget switches the exact pass off -- marked in dr_experiment.h)
 #define DR_D4_BUDGET DR_D4_BUDGET_OVERRIDE
 #else
@@ -413,6 +423,8 @@ __device__ __forceinline__ D4Bound d4_zero() { D4Bound b; b.lin = b.sq = b.mprev
 // builds most of the composite itself (a ray that spends 800 samples in its first brick) rounds against its own growing sum, not
 // against the prefix it started from (fuzz seed 4100169, round 6: alpha off by 1.3e-5 on a ray whose first segment held 660 of
 // its 861 samples, all of tiny opacity, on a prefix of 0).
+// COLOUR: a colour channel, charged by (2') as well; alpha is not.
+template <bool COLOUR>
 __device__ __forceinline__ void d4_risk(float post, float contrib, float cnt, float rcnt, float tiny, D4Bound &b) {
     const float hu = 0.5f * ulp_of(post), c = fabsf(contrib);
     const float m = c * rcnt;
@@ -427,11 +439,15 @@ __device__ __forceinline__ void d4_risk(float post, float contrib, float cnt, fl
     // by `tiny`) or a SPARSE segment, a few ordinary samples among many that contribute nothing (a thin shell, the skipped samples
     // of a non-differentiable march): nothing is rounded alike there
     const bool steady = !(d > hu) && m >= hu;
+    // dim (2'): a colour mean below half an ulp, within half of itself of the previous segment's -- every contribution of the
+    // segment may have been dropped (a mean that jumps from segment to segment is a faint SPARSE ray: a few samples, each of them
+    // far larger). Two segments, not three as in (2): a dim body seen through a shell may span only five or six segments.
+    const bool dim = COLOUR && m < hu && !(d1 > 0.5f * m);
     // (a handful of tiny samples in a segment is the foot of a TF ramp -- opacities that sweep from 0 upwards round this way and that:
     //  charged in quadrature; from D4_TINY_RUN on they count as a stretch of like samples: linearly)
     const float tq = tiny * hu;
     const bool run = tiny >= DR_D4_TINY_RUN;
-    b.lin += fmaxf(run ? tq : 0.0f, steady ? worst : 0.0f);
+    b.lin += fmaxf(run ? tq : 0.0f, (steady || dim) ? worst : 0.0f);
     b.sq = fmaf(run ? 0.0f : tq, tq, b.sq);
 }
 

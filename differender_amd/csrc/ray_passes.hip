@@ -117,8 +117,8 @@ __global__ __launch_bounds__(256) void ray_compose_kernel(BrickParams<VT> P) {
                         b0.lin = fmaf(ea, fabsf(sg[k].x), b0.lin); b1.lin = fmaf(ea, fabsf(sg[k].y), b1.lin); b2.lin = fmaf(ea, fabsf(sg[k].z), b2.lin);
                     }
                     const float n0 = fmaf(T, sg[k].x, C0), n1 = fmaf(T, sg[k].y, C1), n2 = fmaf(T, sg[k].z, C2), n3 = fmaf(T, sg[k].w, A);
-                    d4_risk(n0, T * sg[k].x, cf, rcf, tiny, b0); d4_risk(n1, T * sg[k].y, cf, rcf, tiny, b1);
-                    d4_risk(n2, T * sg[k].z, cf, rcf, tiny, b2); d4_risk(n3, T * sg[k].w, cf, rcf, tiny, b3);
+                    d4_risk<true>(n0, T * sg[k].x, cf, rcf, tiny, b0); d4_risk<true>(n1, T * sg[k].y, cf, rcf, tiny, b1);
+                    d4_risk<true>(n2, T * sg[k].z, cf, rcf, tiny, b2); d4_risk<false>(n3, T * sg[k].w, cf, rcf, tiny, b3);
                     C0 = n0; C1 = n1; C2 = n2; A = n3;
                     total += cnt[k];
                 }
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void ray_alpha_kernel(BrickParams<VT> P) {
                 const float sa = sa4[k];
                 const float A_after = fmaf(1.0f - A, sa, A);
                 D4Bound b2 = bA;
-                d4_risk(A_after, (1.0f - A) * sa, (float)cnt, __builtin_amdgcn_rcpf((float)cnt), tiny, b2);
+                d4_risk<false>(A_after, (1.0f - A) * sa, (float)cnt, __builtin_amdgcn_rcpf((float)cnt), tiny, b2);
                 // the crossing segment (with a margin for the re-associated partials -- 1e-5, or the random walk of the sequential roundings
                 // where a ray has tens of thousands of samples behind it: cross_band -- and for what sequential rounding may have done
                 // systematically so far) starts at sample sacc: resolved by ray_cross_kernel

@@ -1,7 +1,8 @@
 /*
  * dr_oracle.c -- CPU oracle for the Differender volume_raycaster hot path (see dr_oracle_impl.inc).
  * TEST INFRASTRUCTURE ONLY (tests/, __graft_entry__.smoke(), bench.py cpu_baseline). PARITY UNPINNED.
- * Exports dro_*_f32 (parity oracle) and dro_*_f64 (finite-difference reference).
+ * Exports dro_*_f32 (parity oracle), dro_*_f64 (finite-difference reference) and dro_march_fwd_f32_acc64 (the float32
+ * march composited in double: how far sequential float32 rounding takes the parity oracle).
  * Build: make -C oracle   (gcc -O2 -ffp-contract=off -fopenmp -shared)
  */
 #include <math.h>
@@ -62,7 +63,9 @@ float dro_pow_inv_sr(float base, float inv_sr) { return dro_pow_inv_sr_f32(base,
 #define R_FMAX fmaxf
 #define R_FMIN fminf
 #define R_FMA fmaf
+#define DRO_ACC64 1
 #include "dr_oracle_impl.inc"
+#undef DRO_ACC64
 #undef REAL
 #undef SUF
 #undef R_SQRT

@@ -294,6 +294,46 @@ int SUF(dro_march_fwd)(const REAL *vol, int VX, int VY, int VZ, const REAL *tf, 
     return 0;
 }
 
+#ifdef DRO_ACC64
+/* ---- the same march with C and A carried in double (f32 instantiation only): the samples, their shading and each
+ * contribution T * (L * rgb * op) are dro_march_fwd's float32 values; only the running composite is not rounded to float
+ * after every sample. What summing a segment's contributions first (the brick kernels' partials) comes close to: the gap to
+ * dro_march_fwd is the sequential float32 rounding the kernels must bound (DESIGN.md D4). The termination test is the
+ * reference's A < 0.99f. */
+int dro_march_fwd_f32_acc64(const float *vol, int VX, int VY, int VZ, const float *tf, int R, const float *cam,
+                            const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
+                            int W, int H, int S, float sr, int mode, float *out_rgba, int32_t *steps) {
+    SUF(scene) sc; SUF(scene_init)(&sc, vol, VX, VY, VZ, tf, R, cam, sr);
+    const long NP = (long)W * H;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long p = 0; p < NP; ++p) {
+        int n = nsamp[p];
+        SUF(v3) vd = SUF(v3_make)(rays[3 * p], rays[3 * p + 1], rays[3 * p + 2]);
+        double C0 = 0, C1 = 0, C2 = 0, A = 0; int cnt = 0;
+        int nmarch = (mode == 0 && n > S) ? S : n;
+        for (int s = 0; s < nmarch; ++s) {
+            if (!(A < (double)0.99f)) break;
+            SUF(sample) sm;
+            sm.pos = SUF(sample_pos)(&sc, entry[p], exit_[p], vd, n, s);
+            SUF(sample_classify)(&sc, &sm);
+            ++cnt;
+            if (mode == 1 && !(sm.a > 1e-3f)) continue;
+            SUF(sample_shade)(&sc, vd, &sm, mode == 0);
+            const double T = 1.0 - A;
+            C0 += T * (double)(sm.L * sm.r * sm.op);
+            C1 += T * (double)(sm.L * sm.g * sm.op);
+            C2 += T * (double)(sm.L * sm.b * sm.op);
+            A += T * (double)sm.op;
+        }
+        if (mode == 1) { C0 = fmin(1.0, C0); C1 = fmin(1.0, C1); C2 = fmin(1.0, C2); A = fmin(1.0, A); }
+        out_rgba[4 * p + 0] = (float)C0; out_rgba[4 * p + 1] = (float)C1; out_rgba[4 * p + 2] = (float)C2;
+        out_rgba[4 * p + 3] = (float)A;
+        if (steps) steps[p] = cnt;
+    }
+    return 0;
+}
+#endif
+
 /* ---- backward of the diff path: what raycast.grad + get_final_image.grad (VR.py:460-461,470-471)
  * compute, written as an explicit reverse sweep over a per-ray tape of prefix alphas (the reference's
  * render_tape, VR.py:82,102-103, restricted to what the adjoint needs).

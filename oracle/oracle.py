@@ -66,17 +66,20 @@ def ray_setup(cam, W, H, vol_shape, sr=1.0, fov_deg=30.0, near=0.1, jitter_seed=
     return entry, exit_, rays, n
 
 
-def march_fwd(vol, tf, cam, entry, exit_, rays, n, S, sr=1.0, mode=0):
+def march_fwd(vol, tf, cam, entry, exit_, rays, n, S, sr=1.0, mode=0, accum64=False):
     """mode 0: VR.py:261-306 + 363-372 (differentiable path); mode 1: VR.py:308-361 (nondiff).
+    accum64 (float32 only): the same float32 samples and contributions, composited in double.
     Returns rgba (W,H,4), steps (W,H) int32."""
     dt = vol.dtype
+    if accum64 and dt != np.float32:
+        raise ValueError("accum64 composites the float32 march: a float32 volume is required")
     vol = np.ascontiguousarray(vol); tf = np.ascontiguousarray(tf, dtype=dt)
     cam = np.ascontiguousarray(cam, dtype=dt)
     entry = np.ascontiguousarray(entry, dtype=dt); exit_ = np.ascontiguousarray(exit_, dtype=dt)
     rays = np.ascontiguousarray(rays, dtype=dt); n = np.ascontiguousarray(n, dtype=np.int32)
     W, H = n.shape
     out = np.empty((W, H, 4), dt); steps = np.empty((W, H), np.int32)
-    fn = getattr(lib(), "dro_march_fwd" + _suffix(dt))
+    fn = getattr(lib(), "dro_march_fwd" + _suffix(dt) + ("_acc64" if accum64 else ""))
     fn.restype = ctypes.c_int
     fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -187,3 +190,38 @@ def peaks_tf(R, dtype=np.float32):
 def in_circles(i, y=0.7, dist=2.5):
     """UT.py:80-83."""
     return np.array([math.cos(i) * dist, y, math.sin(i) * dist], np.float32)
+
+
+def dark_shell_scene(N, sr, body="flat", op=3e-4, c=4.7e-4, R=64, shell_vox=2.4, radius=0.75, seed=7):
+    """DESIGN.md D4, the dim-behind-bright case: a ball whose bright shell (intensity 0.9, TF rgb 1, alpha 0.25) is shell_vox
+    VOXELS thick -- the transmittance behind it stays near 0.75 ** shell_vox whatever N and sr are -- around a body (intensity 0.5)
+    whose TF colour c is nearly black at an ORDINARY opacity: its TF alpha is 1 - (1 - op) ** sr, so every body sample has the
+    per-sample opacity op (>= DR_D4_TINY_OP; the default keeps alpha above the non-differentiable march's 1e-3 cut from rate 4
+    on) at sampling rate sr. Behind the shell (T <~ 0.3 with the TF ramps on either side of it) each body sample adds
+    T * L * c * op to a running colour of ~0.8: with the defaults below 0.3 of an ulp, so sequential float32 compositing drops
+    every one of them.
+      body="flat":    constant intensity: zero gradient, ambient lighting only (L = 0.4);
+      body="noisy":   the intensity jitters voxel by voxel inside the body's TF range: lit and dim samples mixed in every
+                      segment (contributions from below half an ulp to a few ulps), c lowered to 0.75x;
+      body="rounded": flat, with c raised 2.5x: contributions up to ~0.7 ulp on the rays that see the most of the body -- each one
+                      rounded UP to a whole ulp there, dropped on the rays with less light behind the shell.
+    Returns vol (N, N, N) float32 and tf (R, 4) float32."""
+    ax = np.linspace(-1.0, 1.0, N, dtype=np.float32)   # (float32 throughout: 512^3 stays at a few 0.5 GB arrays)
+    X, Y, Z = np.meshgrid(ax, ax, ax, indexing="ij", sparse=True)
+    rad = np.sqrt(X * X + Y * Y + Z * Z)
+    inner = np.float32(radius - shell_vox * 2.0 / (N - 1))
+    if body == "noisy":
+        fill = np.float32(0.5) + np.random.RandomState(seed).uniform(-0.08, 0.08, size=(N, N, N)).astype(np.float32)
+    elif body in ("flat", "rounded"):
+        fill = 0.5
+    else:
+        raise ValueError(f"unknown body {body!r}")
+    vol = np.where(rad > np.float32(radius), np.float32(0.0), np.where(rad >= inner, np.float32(0.9), np.float32(fill)))
+    i = np.arange(R, dtype=np.float64) / (R - 1)
+    tf = np.zeros((R, 4), np.float64)
+    in_body = (i >= 0.3) & (i < 0.7)
+    tf[in_body, :3] = c * {"flat": 1.0, "noisy": 0.75, "rounded": 2.5}[body]
+    tf[in_body, 3] = 1.0 - (1.0 - op) ** sr
+    tf[i >= 0.7, :3] = 1.0
+    tf[i >= 0.7, 3] = 0.25
+    return vol.astype(np.float32), tf.astype(np.float32)

@@ -265,3 +265,79 @@ def test_ray_parallel_to_a_slab_it_misses_has_no_samples(oracle):
     assert n.min() >= 0
     bad = ~np.isfinite(x - e)
     assert bad.any() and (n[bad] == 0).all()
+
+
+# ---- the float32 march composited in double (oracle.march_fwd(accum64=True)): the yardstick of DESIGN.md D4 ----
+def _acc64_gap(oracle, vol, tf, cam, WH, sr, mode=0):
+    e, x, r, n = oracle.ray_setup(cam, *WH, vol.shape, sr=sr)
+    seq, s32 = oracle.march_fwd(vol, tf, cam, e, x, r, n, 1 << 20, sr, mode)
+    acc, s64 = oracle.march_fwd(vol, tf, cam, e, x, r, n, 1 << 20, sr, mode, accum64=True)
+    same = s32 == s64
+    assert same.mean() > 0.9
+    return float(np.abs(seq - acc).max(-1)[same].max())
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_accum64_is_the_float32_march_on_one_sample_rays(oracle, mode):
+    """With one sample there is nothing to round against: C = fma(1, c, 0) = c either way -- bit for bit, which pins the accum64
+    march to the very samples, shading and contributions of the float32 one (and the mode-1 clamp and alpha cut to its own)."""
+    vol = np.random.RandomState(3).uniform(0.1, 0.9, size=(2, 2, 2)).astype(np.float32)
+    tf = np.random.RandomState(4).uniform(0.0, 1.5, size=(8, 4)).astype(np.float32)   # (unclamped highlights: colours above 1)
+    tf[:, 3] = np.random.RandomState(5).uniform(0.0, 0.9, size=8)
+    tf[::3, 3] = 5e-4                                        # (some samples under the non-differentiable march's alpha cut)
+    cam = oracle.in_circles(0.7)
+    e, x, r, n = oracle.ray_setup(cam, 24, 20, vol.shape, sr=0.1)
+    assert n.max() == 1 and n.sum() > 100
+    a, sa = oracle.march_fwd(vol, tf, cam, e, x, r, n, 1 << 20, 0.1, mode)
+    b, sb = oracle.march_fwd(vol, tf, cam, e, x, r, n, 1 << 20, 0.1, mode, accum64=True)
+    assert np.array_equal(a, b) and np.array_equal(sa, sb) and np.abs(a).max() > 0
+    # ... and any ray cut to a single sample by max_samples (the differentiable march, H2)
+    vol, tf, cam = _scene(oracle, N=24, R=16, dtype=np.float32)
+    e, x, r, n = oracle.ray_setup(cam, 16, 16, vol.shape)
+    a, _ = oracle.march_fwd(vol, tf, cam, e, x, r, n, 1, 1.0, 0)
+    b, _ = oracle.march_fwd(vol, tf, cam, e, x, r, n, 1, 1.0, 0, accum64=True)
+    assert np.array_equal(a, b) and np.abs(a).max() > 0
+    with pytest.raises(ValueError):
+        oracle.march_fwd(vol.astype(np.float64), tf, cam, e, x, r, n, 1, 1.0, 0, accum64=True)
+
+
+@pytest.mark.parametrize("sr", [2.0, 4.0])
+def test_accum64_shows_the_sub_ulp_gap_of_the_D4_scene(oracle, sr):
+    """tf1 with 1e-6 in its transparent ranges (tests/test_gpu_parity.py::test_sub_ulp_contributions_behind_opaque_structures_D4):
+    behind the opaque peaks every such sample is below half an ulp, sequential float32 compositing drops them all -- 1.3e-5 (rate 2)
+    and 2.8e-5 (rate 4) on the worst pixel, the gap the brick kernels' partials had until their bound caught it."""
+    from differender_amd.utils import get_tf
+    vol = oracle.synth_volume(96)
+    tf = get_tf("tf1", 64).t().contiguous().numpy()
+    tf[:, 3] = np.where(tf[:, 3] == 0, np.float32(1e-6), tf[:, 3])
+    assert _acc64_gap(oracle, vol, tf, oracle.in_circles(2.1), (64, 56), sr) > 1e-5
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_accum64_gap_of_the_bench_tf_is_a_random_walk(oracle, mode):
+    """The bench's TF (sinusoidal colours, alpha 3 / n_max) at rate 1: contributions many ulps large that drift from sample to
+    sample round this way and that -- the gap stays below 1e-6, far under the bar."""
+    N = 96
+    vol = oracle.synth_volume(N)
+    tf = oracle.bench_tf(64, 3.0 / (2.0 * 3.0 * (N - 1)))
+    assert _acc64_gap(oracle, vol, tf, oracle.in_circles(2.1), (64, 56), 1.0, mode) < 1e-6
+
+
+@pytest.mark.parametrize("body", ["flat", "noisy", "rounded"])
+def test_dark_shell_scene(oracle, body):
+    """oracle.dark_shell_scene: the body's samples have the requested per-sample opacity at the requested rate (>= DR_D4_TINY_OP:
+    rule (1) of DESIGN.md D4 does not count them), the shell is a fixed number of voxels thick at every N, and the scene shows
+    the sequential rounding gap the GPU tests (tests/test_gpu_d4_dim_shell.py) are about."""
+    for N, sr in ((96, 8.0), (192, 4.0)):
+        vol, tf = oracle.dark_shell_scene(N, sr, body, op=3e-4)
+        body_tf = tf[(np.arange(64) / 63.0 >= 0.3) & (np.arange(64) / 63.0 < 0.7)]
+        op = 1.0 - (1.0 - body_tf[:, 3].astype(np.float64)) ** (1.0 / sr)
+        assert np.allclose(op, 3e-4, rtol=1e-4) and op.min() >= 1e-4
+        assert body_tf[:, :3].max() < 2e-3                  # nearly black
+        line = vol[N // 2, N // 2, N // 2:]                  # from the centre outwards: body, 2-3 voxels of shell, air
+        assert 2 <= (line == np.float32(0.9)).sum() <= 3, (N, line)
+        if body == "noisy":
+            inside = vol[N // 2 - 4:N // 2 + 4, N // 2 - 4:N // 2 + 4, N // 2 - 4:N // 2 + 4]
+            assert inside.std() > 0.02 and inside.min() >= 0.42 and inside.max() <= 0.58
+    vol, tf = oracle.dark_shell_scene(96, 8.0, body)
+    assert _acc64_gap(oracle, vol, tf, oracle.in_circles(2.1), (48, 48), 8.0) > 1e-5

@@ -1,8 +1,10 @@
 """DESIGN.md D4 at the sizes that matter: the fast path against the SEQUENTIAL kernels (DR_VARIANT_BASELINE: the oracle's
 float32 recurrence bit for bit, VR.py:300-302) on whole views, for transfer functions with tiny non-zero alphas.
-    python tools/d4_measure.py [N] [WH] [rates...]     (GPU box; one JSON line per case on stdout)
+    python tools/d4_measure.py [N] [WH] [rates...] [--shell]     (GPU box; one JSON line per case on stdout)
 TFs: bench (alpha 1e-3), tf1 (exact zeros), d4 (tf1 with 1e-6 in its transparent ranges), opt5 / opt3 (tf1 after three
-gradient steps whose largest alpha change is 1e-5 / 1e-3 -- what an optimised TF looks like)."""
+gradient steps whose largest alpha change is 1e-5 / 1e-3 -- what an optimised TF looks like).
+--shell: the dim-behind-bright scene instead (oracle.dark_shell_scene: ordinary-opacity samples of a nearly black TF colour
+behind a bright shell), its three bodies shell-flat / shell-noisy / shell-rounded."""
 import json
 import sys
 import time
@@ -30,24 +32,40 @@ def optimised_tf(vol, tf0, cam, WH, sr, step):
     return tf
 
 
+def shell_scenes(N, sr, dev):
+    from oracle import oracle as O
+    for body in ("flat", "noisy", "rounded"):
+        vol, tf = O.dark_shell_scene(N, sr, body)
+        yield "shell-" + body, torch.from_numpy(vol).to(dev), torch.from_numpy(tf).to(dev)
+
+
 def main():
-    N = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-    wh = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-    rates = [float(a) for a in sys.argv[3:]] or [1.0, 2.0]
-    WH, R = (wh, wh), 128
+    args = [a for a in sys.argv[1:] if a != "--shell"]
+    shell = len(args) < len(sys.argv) - 1
+    N = int(args[0]) if len(args) > 0 else 512
+    wh = int(args[1]) if len(args) > 1 else 512
+    rates = [float(a) for a in args[2:]] or [1.0, 2.0]
+    WH = (wh, wh)
     dev = torch.device("cuda:0")
-    vol = bench.synth_volume_torch(N, dev)
     cam = torch.tensor([bench.in_circles(2.1)], dtype=torch.float32, device=dev)
-    tf1 = get_tf("tf1", R).t().contiguous().to(dev)
-    d4 = tf1.clone()
-    d4[:, 3] = torch.where(d4[:, 3] == 0, torch.full_like(d4[:, 3], 1e-6), d4[:, 3])
-    tfs = {"bench": bench.bench_tf_torch(R, 1e-3, dev), "tf1": tf1, "d4": d4}
+    if not shell:
+        R = 128
+        vol = bench.synth_volume_torch(N, dev)
+        tf1 = get_tf("tf1", R).t().contiguous().to(dev)
+        d4 = tf1.clone()
+        d4[:, 3] = torch.where(d4[:, 3] == 0, torch.full_like(d4[:, 3], 1e-6), d4[:, 3])
+        tfs = {"bench": bench.bench_tf_torch(R, 1e-3, dev), "tf1": tf1, "d4": d4}
     for sr in rates:
-        tfs_sr = dict(tfs)
-        tfs_sr["opt5"] = optimised_tf(vol, tf1, cam, WH, sr, 1e-5)
-        tfs_sr["opt3"] = optimised_tf(vol, tf1, cam, WH, sr, 1e-3)
-        e, x, r, n = Fn.ray_setup(cam, WH, vol.shape, sr)
-        for name, tf in tfs_sr.items():
+        if shell:
+            scenes = list(shell_scenes(N, sr, dev))
+        else:
+            tfs_sr = dict(tfs)
+            tfs_sr["opt5"] = optimised_tf(vol, tf1, cam, WH, sr, 1e-5)
+            tfs_sr["opt3"] = optimised_tf(vol, tf1, cam, WH, sr, 1e-3)
+            scenes = [(name, vol, tf) for name, tf in tfs_sr.items()]
+        for name, vol, tf in scenes:
+            R = tf.shape[0]
+            e, x, r, n = Fn.ray_setup(cam, WH, vol.shape, sr)
             for mode in (Fn.N.DR_MODE_DIFF, Fn.N.DR_MODE_NONDIFF):
                 ws = Fn.alloc_workspace(1, WH, vol.shape, R, dev)
                 out, steps = Fn.march_fwd(vol, tf, cam, e, x, r, n, 1 << 20, sr, mode=mode, workspace=ws, hints=0)
