@@ -60,6 +60,10 @@ SIGNATURES = {
     "dr_msssim_mse_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _I, _D, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P]),
     "dr_tv3d_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _D, _P, _P]),
     "dr_tv3d_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _D, _P, _F, _P, _P, _I, _P]),
+    "dr_march_tf2d_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _I, _L, _F, _P, _P, _P, _P, _P,
+                               _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "dr_march_tf2d_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _I, _L, _F, _P, _P, _P, _P, _P,
+                               _I, _I, _I, _I, _F, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P]),
 }
 
 _lib = None

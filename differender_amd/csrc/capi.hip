@@ -398,6 +398,67 @@ int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, cons
     return launch_tv3d_bwd(a, (hipStream_t)stream);
 }
 
+static int fill_tf2d(Tf2dArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                     int64_t vol_view_stride, const float *tf2d, int RV, int RG, int64_t tf_view_stride, float g_scale,
+                     const float *cam, const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
+                     int n_views, int W, int H, int max_samples, float sampling_rate) {
+    if (!vol || !tf2d || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
+    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
+    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
+    if (RV < 1 || RG < 1 || (int64_t)RV * RG >= ((int64_t)1 << 31)) return DR_EINVAL;
+    if (!std::isfinite(g_scale) || !(g_scale > 0.0f)) return DR_EINVAL;
+    if (max_samples < 0 || !(sampling_rate > 0.0f)) return DR_EINVAL;
+    if (tf_view_stride % 4 != 0) return DR_EINVAL;
+    a = Tf2dArgs{};
+    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
+    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
+    a.tf = tf2d; a.RV = RV; a.RG = RG; a.tf_vs = tf_view_stride; a.g_scale = g_scale;
+    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
+    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate;
+    return 0;
+}
+
+int dr_march_tf2d_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                      int64_t vol_view_stride, const float *tf2d, int RV, int RG, int64_t tf_view_stride, float g_scale,
+                      const float *cam, const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
+                      int n_views, int W, int H, int max_samples, float sampling_rate, int mode, float *out_rgba,
+                      int32_t *steps, void *stream) {
+    Tf2dArgs a;
+    int rc = fill_tf2d(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf2d, RV, RG, tf_view_stride, g_scale, cam,
+                       entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!out_rgba) return DR_EINVAL;
+    if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
+    a.mode = mode; a.out = out_rgba; a.steps = steps;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_march_tf2d_fwd) return DR_EUNSUPPORTED;   // (a library linked without march_tf2d.o)
+    return launch_march_tf2d_fwd(a, (hipStream_t)stream);
+}
+
+int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                      int64_t vol_view_stride, const float *tf2d, int RV, int RG, int64_t tf_view_stride, float g_scale,
+                      const float *cam, const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
+                      int n_views, int W, int H, int max_samples, float sampling_rate, const float *grad_out,
+                      const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                      float *d_tf2d, int64_t dtf_view_stride, void *stream) {
+    Tf2dArgs a;
+    int rc = fill_tf2d(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf2d, RV, RG, tf_view_stride, g_scale, cam,
+                       entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!grad_out || !out_rgba) return DR_EINVAL;
+    if (dtf_view_stride % 4 != 0) return DR_EINVAL;
+    if (!d_vol && !d_tf2d) return 0;  // nothing requested
+    a.mode = DR_MODE_DIFF;
+    a.grad_out = grad_out; a.out_fwd = out_rgba;
+    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
+    a.d_tf = d_tf2d; a.dtf_vs = dtf_view_stride;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_march_tf2d_bwd) return DR_EUNSUPPORTED;
+    return launch_march_tf2d_bwd(a, (hipStream_t)stream);
+}
+
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,
                         void *stream) {
     if (!tf || !d_tf || !momentum || n <= 0 || !(max_grad >= 0.0f)) return DR_EINVAL;

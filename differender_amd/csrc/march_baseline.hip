@@ -10,6 +10,7 @@
 //   which needs only a forward-order walk and the saved forward output (no per-sample tape).
 #include "dr_device.h"
 #include "dr_kernels.h"
+#include "dr_tile.h"
 #include "../../include/differender_hip.h"
 
 namespace dr {
@@ -28,15 +29,6 @@ struct MarchParams {
     const unsigned int *ws_mark; unsigned int ws_mark_expect;  // see MarchArgs
     const unsigned int *ws_aux; unsigned int ws_aux_expect;
 };
-
-__device__ __forceinline__ bool tile_pixel(int W, int H, int &i, int &j) {
-    const int tiles_j = (H + 7) >> 3;
-    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    i = (wave / tiles_j) * 8 + (lane >> 3);
-    j = (wave % tiles_j) * 8 + (lane & 7);
-    return i < W && j < H;
-}
 
 // TF_LDS: the transfer function is staged in LDS (R <= 10176 entries = 159 KiB: what a workgroup is really granted, less headroom); a larger one is read where it lies, through the
 // caches -- the reference has no limit on the TF resolution, and neither have the plain kernels.
@@ -235,21 +227,7 @@ static MarchParams<VT> make_params(const MarchArgs &a) {
     return P;
 }
 
-hipError_t allow_lds_impl(const void *kernel, size_t bytes);  // capi.hip
-template <typename K>
-static hipError_t big_lds(K kernel, size_t bytes) {  // dynamic LDS above 64 KB needs an explicit opt-in (once per kernel)
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return allow_lds_impl(reinterpret_cast<const void *>(kernel), bytes);
-}
-
-// What one workgroup may really ask for: the runtime does not grant a CU's full 160 KiB (163 232 B launched, 163 616 B did not:
-// tools/lds_limit_probe.py, round 5) -- 1 KiB of headroom, as brick_path_supported keeps. A table that does not fit drops to the
-// next tier instead of failing at launch (R = 3409 .. 3413 and 10 227 .. 10 240 picked a tier the launch refused).
-constexpr size_t LDS_PER_CU = 159 * 1024;
-static dim3 tile_grid(const MarchArgs &a) {
-    const int tiles = ((a.W + 7) / 8) * ((a.H + 7) / 8);
-    return dim3((tiles + 3) / 4, a.n_views);
-}
+static dim3 tile_grid(const MarchArgs &a) { return tile_grid(a.W, a.H, a.n_views); }
 
 template <typename VT>
 static int fwd_dispatch(const MarchArgs &a, hipStream_t stream) {

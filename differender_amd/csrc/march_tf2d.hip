@@ -1,0 +1,353 @@
+// march_tf2d.hip -- the march with a 2-D (value, gradient-magnitude) transfer function, for gfx950.
+// The shape of march_baseline.hip: one lane per ray, a wave per 8x8 pixel tile, 256-thread workgroups, direct global
+// gathers, the sequential float32 recurrence and the tape-free adjoint (suffix = out - prefix). Only the classification
+// differs from the 1-D march: the six normal taps come first, and their length u = |grad| * g_scale is the second TF axis.
+//   xv = I (RV - 1), xg = u (RG - 1); low_high_frac and the H4/H5 clamp on each axis;
+//   rgba = mix(mix(T[v0][g0], T[v1][g0], fv), mix(T[v0][g1], T[v1][g1], fv), fg)   (value axis first, dr_device.h's mixf)
+// With RG == 1, fg = 0 and mix(x, x, 0) = x: a (RV, 1) table is bit for bit the 1-D TF of RV entries.
+#include "dr_device.h"
+#include "dr_kernels.h"
+#include "dr_tile.h"
+#include "../../include/differender_hip.h"
+
+namespace dr {
+
+template <typename VT>
+struct Tf2dParams {
+    VolView<VT> vol; int64_t vol_vs;
+    const float4 *tf; int64_t tf_vs; int RV, RG; float lv, lg, g_scale;   // lv = RV - 1, lg = RG - 1 (rounded from int)
+    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp;
+    int W, H, S; float inv_sr;
+    float *out; int32_t *steps;
+    const float *grad_out, *out_fwd;
+    GradView dvol; int64_t dvol_vs;
+    float *d_tf; int64_t dtf_vs;
+};
+
+// The classification of one sample: indices and fractions on both axes, the four texels and the two value-axis lerps.
+struct Tf2dSample {
+    float xv, xg, fv, fg;
+    int v0, v1, g0, g1;   // table rows (value) and columns (gradient)
+    float4 a, b, c, d;    // T[v0][g0], T[v1][g0], T[v0][g1], T[v1][g1]
+    float4 lo, hi;        // mix(a, b, fv), mix(c, d, fv)
+};
+
+__device__ __forceinline__ void axis_index(float x, int R, int &i0, int &i1, float &fr) {
+    low_high_frac(x, i0, fr);
+    i0 = min(i0, R - 1);
+    i1 = min(i0 + 1, R - 1);
+}
+
+__device__ __forceinline__ float4 mix4(float4 x, float4 y, float a) {
+    return make_float4(mixf(x.x, y.x, a), mixf(x.y, y.y, a), mixf(x.z, y.z, a), mixf(x.w, y.w, a));
+}
+
+// sm.I and sm.gnorm must be set; writes sm.r, g, b, a and sm.op
+template <typename VT>
+__device__ __forceinline__ void classify2d(const Tf2dParams<VT> &P, const float4 *tf, Sample &sm, Tf2dSample &t) {
+    const float u = sm.gnorm * P.g_scale;
+    t.xv = sm.I * P.lv;
+    t.xg = u * P.lg;
+    axis_index(t.xv, P.RV, t.v0, t.v1, t.fv);
+    axis_index(t.xg, P.RG, t.g0, t.g1, t.fg);
+    t.a = tf[t.v0 * P.RG + t.g0]; t.b = tf[t.v1 * P.RG + t.g0];
+    t.c = tf[t.v0 * P.RG + t.g1]; t.d = tf[t.v1 * P.RG + t.g1];
+    t.lo = mix4(t.a, t.b, t.fv);
+    t.hi = mix4(t.c, t.d, t.fv);
+    sm.r = mixf(t.lo.x, t.hi.x, t.fg); sm.g = mixf(t.lo.y, t.hi.y, t.fg);
+    sm.b = mixf(t.lo.z, t.hi.z, t.fg); sm.a = mixf(t.lo.w, t.hi.w, t.fg);
+    sm.op = opacity_of_alpha(sm.a, P.inv_sr);
+}
+
+// The non-differentiable march skips samples with alpha <= 1e-3 (VR.py:334). Every alpha a sample of value rows v0, v1 can
+// take is a convex combination of their texels, rounded four times: at most max(rowmax[v0], rowmax[v1]) (1 + 2^-21). Below
+// this bound the sample is certain to be skipped, so its six taps are never gathered; the image and steps are those of the
+// plain test (a NaN alpha is skipped either way).
+constexpr float TF2D_SKIP_BELOW = 9.9999e-4f;
+
+// TF_LDS: the table (and, for the non-differentiable mode, its per-row largest alpha) is staged in LDS; otherwise it is read
+// where it lies and every sample is classified.
+template <typename VT, int MODE, bool TF_LDS>
+__global__ __launch_bounds__(256) void march_tf2d_fwd_kernel(Tf2dParams<VT> P) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
+    const int view = blockIdx.y;
+    const int NT = P.RV * P.RG;
+    const float4 *tfg = P.tf + view * P.tf_vs;
+    float *rowmax = reinterpret_cast<float *>(lds_tf_ + NT);
+    constexpr bool SKIP = TF_LDS && MODE == DR_MODE_NONDIFF;
+    if (TF_LDS) {
+        for (int k = threadIdx.x; k < NT; k += 256) lds_tf_[k] = tfg[k];
+        __syncthreads();
+    }
+    if (SKIP) {
+        // one wave per row, its lanes across the row's texels, then a butterfly max (the row loop is wave-uniform, so the
+        // shuffles run converged): the work is spread alike for tall and for wide tables
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        for (int v = wave; v < P.RV; v += 4) {
+            float m = -__builtin_inff();
+            for (int g = lane; g < P.RG; g += 64) m = fmaxf(m, lds_tf_[v * P.RG + g].w);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+            if (lane == 0) rowmax[v] = m;
+        }
+        __syncthreads();
+    }
+    const float4 *tf = TF_LDS ? lds_tf_ : tfg;
+
+    int i, j;
+    if (!tile_pixel(P.W, P.H, i, j)) return;
+    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    VolView<VT> vol = P.vol;
+    vol.p += view * P.vol_vs;
+    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
+    const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
+
+    RayGeom rg;
+    rg.n = P.nsamp[p]; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
+    rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
+    rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+    const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+    const int nmarch = (MODE == DR_MODE_DIFF && rg.n > P.S) ? P.S : rg.n;
+
+    float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+    int cnt = 0;
+    for (int s = 0; s < nmarch; ++s) {
+        if (!(A < 0.99f)) break;
+        Sample sm;
+        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
+        sm.I = tri_sample(vol, sm.px, sm.py, sm.pz);
+        ++cnt;
+        if (SKIP) {
+            int v0, v1; float fv;
+            axis_index(sm.I * P.lv, P.RV, v0, v1, fv);
+            if (fmaxf(rowmax[v0], rowmax[v1]) <= TF2D_SKIP_BELOW) continue;
+        }
+        shade(vol, light, vd, MODE == DR_MODE_DIFF, sm);   // the taps: sm.gnorm
+        Tf2dSample t;
+        classify2d(P, tf, sm, t);
+        if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
+        const float T = 1.0f - A;
+        C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
+        C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
+        C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
+        A = fmaf(T, sm.op, A);
+    }
+    if (MODE == DR_MODE_NONDIFF) {
+        C0 = fminf(1.0f, C0); C1 = fminf(1.0f, C1); C2 = fminf(1.0f, C2); A = fminf(1.0f, A);
+    }
+    reinterpret_cast<float4 *>(P.out)[p] = make_float4(C0, C1, C2, A);
+    if (P.steps) P.steps[p] = cnt;
+}
+
+__device__ __forceinline__ float dot4(float4 x, const SampleAdj &ad) {
+    return x.x * ad.r_bar + x.y * ad.g_bar + x.z * ad.b_bar + x.w * ad.a_bar;
+}
+__device__ __forceinline__ float4 sub4(float4 x, float4 y) { return make_float4(x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w); }
+
+// d_tf2d contributions of a run of samples in one table cell (the four corner texels i..), summed in f32
+struct CellRun {
+    int i00 = -1, i10, i01, i11;
+    float s00[4], s10[4], s01[4], s11[4];
+    __device__ __forceinline__ void start(int a, int b, int c, int d) {
+        i00 = a; i10 = b; i01 = c; i11 = d;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s00[q] = s10[q] = s01[q] = s11[q] = 0.0f;
+    }
+    __device__ __forceinline__ void flush(float *dtf) const {
+        if (i00 < 0) return;
+        float *d00 = dtf + 4 * (size_t)i00, *d10 = dtf + 4 * (size_t)i10, *d01 = dtf + 4 * (size_t)i01, *d11 = dtf + 4 * (size_t)i11;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            unsafeAtomicAdd(d00 + q, s00[q]); unsafeAtomicAdd(d10 + q, s10[q]);
+            unsafeAtomicAdd(d01 + q, s01[q]); unsafeAtomicAdd(d11 + q, s11[q]);
+        }
+    }
+};
+
+// TABLES: what the workgroup keeps in LDS, by texel count P = RV * RG (march_baseline.hip's tiers) --
+//   2: the TF + its gradient table in double (48 P bytes: P <= 3392; only when d_tf2d is wanted);
+//   1: the TF only; d_tf2d by float atomics on the caller's tensor, one set per run of samples in a cell (16 P bytes: P <= 10176);
+//   0: nothing: the TF is read where it lies (d_tf2d as in tier 1).
+template <typename VT, int TABLES>
+__global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
+    const int view = blockIdx.y;
+    const int NT = P.RV * P.RG;
+    const float4 *tfg = P.tf + view * P.tf_vs;
+    double *lds_dtf = reinterpret_cast<double *>(lds_tf_ + NT);
+    if (TABLES >= 1) for (int k = threadIdx.x; k < NT; k += 256) lds_tf_[k] = tfg[k];
+    if (TABLES == 2) for (int k = threadIdx.x; k < 4 * NT; k += 256) lds_dtf[k] = 0.0;
+    if (TABLES >= 1) __syncthreads();
+    const float4 *tf = TABLES >= 1 ? lds_tf_ : tfg;
+    float *dtf_g = P.d_tf ? P.d_tf + view * P.dtf_vs * 4 : nullptr;
+
+    int i, j;
+    if (tile_pixel(P.W, P.H, i, j)) {
+        const size_t p = ((size_t)view * P.W + i) * P.H + j;
+        VolView<VT> vol = P.vol;
+        vol.p += view * P.vol_vs;
+        GradView dv = P.dvol;
+        const bool want_vol = dv.p != nullptr;
+        const bool want_tf = P.d_tf != nullptr;
+        if (want_vol) dv.p += view * P.dvol_vs;
+        const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
+        const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
+
+        RayGeom rg;
+        rg.n = P.nsamp[p]; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
+        rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
+        rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+        const int nmarch = rg.n > P.S ? P.S : rg.n;
+
+        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
+        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+        const float delta = 1e-3f;
+
+        float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+        CellRun run;
+        for (int s = 0; s < nmarch; ++s) {
+            if (!(A < 0.99f)) break;
+            Sample sm;
+            sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
+            sm.I = tri_sample(vol, sm.px, sm.py, sm.pz);
+            shade(vol, light, vd, true, sm);
+            Tf2dSample t;
+            classify2d(P, tf, sm, t);
+            const float T = 1.0f - A;
+            C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
+            C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
+            C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
+            A = fmaf(T, sm.op, A);
+            const bool last = (s == nmarch - 1) || !(A < 0.99f);
+            const float suffix = (go.x * (of.x - C0) + go.y * (of.y - C1) + go.z * (of.z - C2)) + go.w * (of.w - A);
+            SampleAdj ad;
+            sample_adjoint(sm, vd, T, suffix, last, go, P.inv_sr, ad);
+
+            if (want_tf) {
+                // d rgba / d T[.][.]: the four bilinear weights
+                const float w00 = (1.0f - t.fv) * (1.0f - t.fg), w10 = t.fv * (1.0f - t.fg);
+                const float w01 = (1.0f - t.fv) * t.fg, w11 = t.fv * t.fg;
+                const int i00 = t.v0 * P.RG + t.g0, i10 = t.v1 * P.RG + t.g0;   // texel indices (< 2^31)
+                const int i01 = t.v0 * P.RG + t.g1, i11 = t.v1 * P.RG + t.g1;
+                const float adj[4] = {ad.r_bar, ad.g_bar, ad.b_bar, ad.a_bar};
+                if (TABLES == 2) {   // (the products are f32, as in the 1-D backward)
+                    const int k00 = 4 * i00, k10 = 4 * i10, k01 = 4 * i01, k11 = 4 * i11;   // (P <= 3392)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        atomicAdd(lds_dtf + k00 + q, (double)(w00 * adj[q])); atomicAdd(lds_dtf + k10 + q, (double)(w10 * adj[q]));
+                        atomicAdd(lds_dtf + k01 + q, (double)(w01 * adj[q])); atomicAdd(lds_dtf + k11 + q, (double)(w11 * adj[q]));
+                    }
+                } else {
+                    // float atomics on the caller's tensor, one set per RUN of consecutive samples of the ray in one table cell:
+                    // neighbouring samples (air, a material's interior) mostly share their cell, and same-address atomics of
+                    // thousands of rays are what this tier's time is made of
+                    if (i00 != run.i00) { run.flush(dtf_g); run.start(i00, i10, i01, i11); }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        run.s00[q] += w00 * adj[q]; run.s10[q] += w10 * adj[q];
+                        run.s01[q] += w01 * adj[q]; run.s11[q] += w11 * adj[q];
+                    }
+                }
+            }
+            if (want_vol) {
+                // through I: the value-axis slope (1 - fg)(b - a) + fg (d - c), times RV - 1, iff 0 < xv
+                const float fv_bar = (1.0f - t.fg) * dot4(sub4(t.b, t.a), ad) + t.fg * dot4(sub4(t.d, t.c), ad);
+                const float I_bar = (0.0f < t.xv) ? fv_bar * P.lv : 0.0f;
+                tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz, I_bar);
+                if (!sm.flat) {
+                    // through u = |grad| g_scale: the gradient-axis slope hi - lo, times (RG - 1) g_scale, iff 0 < xg, onto the
+                    // taps along grad / |grad| -- beside the normal's own adjoint (sample_adjoint)
+                    const float fg_bar = dot4(sub4(t.hi, t.lo), ad);
+                    const float u_bar = (0.0f < t.xg) ? fg_bar * P.lg : 0.0f;
+                    const float k = (u_bar * P.g_scale) * sm.ginv;
+                    const float gx = fmaf(k, sm.grad.x, ad.gx), gy = fmaf(k, sm.grad.y, ad.gy), gz = fmaf(k, sm.grad.z, ad.gz);
+                    tri_scatter_global(vol, dv, sm.px + delta, sm.py, sm.pz, gx);
+                    tri_scatter_global(vol, dv, sm.px - delta, sm.py, sm.pz, -gx);
+                    tri_scatter_global(vol, dv, sm.px, sm.py + delta, sm.pz, gy);
+                    tri_scatter_global(vol, dv, sm.px, sm.py - delta, sm.pz, -gy);
+                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz + delta, gz);
+                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz - delta, -gz);
+                }
+            }
+        }
+        if (TABLES < 2 && want_tf) run.flush(dtf_g);
+    }
+    if (P.d_tf && TABLES == 2) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < 4 * NT; k += 256) {   // (NT <= 3392)
+            const float v = (float)lds_dtf[k];
+            if (v != 0.0f) unsafeAtomicAdd(dtf_g + k, v);
+        }
+    }
+}
+
+template <typename VT>
+static Tf2dParams<VT> make_tf2d_params(const Tf2dArgs &a) {
+    Tf2dParams<VT> P;
+    P.vol.p = static_cast<const VT *>(a.vol);
+    P.vol.sx = a.sx; P.vol.sy = a.sy; P.vol.sz = a.sz;
+    P.vol.VX = a.VX; P.vol.VY = a.VY; P.vol.VZ = a.VZ;
+    P.vol.scx = (float)((double)a.VX - 1.0 - 1e-4);
+    P.vol.scy = (float)((double)a.VY - 1.0 - 1e-4);
+    P.vol.scz = (float)((double)a.VZ - 1.0 - 1e-4);
+    P.vol_vs = a.vol_vs;
+    P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4;
+    P.RV = a.RV; P.RG = a.RG; P.lv = (float)(a.RV - 1); P.lg = (float)(a.RG - 1); P.g_scale = a.g_scale;
+    P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp;
+    P.W = a.W; P.H = a.H; P.S = a.S; P.inv_sr = 1.0f / a.sr;
+    P.out = a.out; P.steps = a.steps;
+    P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
+    P.dvol.p = a.d_vol; P.dvol.sx = a.dsx; P.dvol.sy = a.dsy; P.dvol.sz = a.dsz; P.dvol_vs = a.dvol_vs;
+    P.d_tf = a.d_tf; P.dtf_vs = a.dtf_vs / 4;
+    return P;
+}
+
+template <typename VT>
+static int tf2d_fwd_dispatch(const Tf2dArgs &a, hipStream_t stream) {
+    const size_t NT = (size_t)a.RV * a.RG;
+    size_t lds = NT * sizeof(float4) + (a.mode == DR_MODE_NONDIFF ? (size_t)a.RV * sizeof(float) : 0);
+    const bool tf_lds = lds <= LDS_PER_CU;
+    if (!tf_lds) lds = 0;
+    const Tf2dParams<VT> P = make_tf2d_params<VT>(a);
+    const dim3 grid = tile_grid(a.W, a.H, a.n_views);
+#define DR_TF2D_FWD(MODE_, LDS_)                                                                                  \
+    {                                                                                                             \
+        if (big_lds(march_tf2d_fwd_kernel<VT, MODE_, LDS_>, lds) != hipSuccess) return DR_EUNSUPPORTED;           \
+        hipLaunchKernelGGL((march_tf2d_fwd_kernel<VT, MODE_, LDS_>), grid, dim3(256), lds, stream, P);            \
+    }
+    if (a.mode == DR_MODE_DIFF) { if (tf_lds) DR_TF2D_FWD(DR_MODE_DIFF, true) else DR_TF2D_FWD(DR_MODE_DIFF, false) }
+    else { if (tf_lds) DR_TF2D_FWD(DR_MODE_NONDIFF, true) else DR_TF2D_FWD(DR_MODE_NONDIFF, false) }
+#undef DR_TF2D_FWD
+    return (int)hipGetLastError();
+}
+
+template <typename VT>
+static int tf2d_bwd_dispatch(const Tf2dArgs &a, hipStream_t stream) {
+    const size_t NT = (size_t)a.RV * a.RG;
+    // (a backward without d_tf2d keeps no gradient table: at 64 x 32 texels the f64 table alone would limit a CU to one
+    // workgroup)
+    const size_t lds2 = NT * (sizeof(float4) + 4 * sizeof(double)), lds1 = NT * sizeof(float4);
+    const int tables = (a.d_tf && lds2 <= LDS_PER_CU) ? 2 : (lds1 <= LDS_PER_CU ? 1 : 0);
+    const size_t lds = tables == 2 ? lds2 : (tables == 1 ? lds1 : 0);
+    const Tf2dParams<VT> P = make_tf2d_params<VT>(a);
+    const dim3 grid = tile_grid(a.W, a.H, a.n_views);
+#define DR_TF2D_BWD(T_)                                                                                           \
+    {                                                                                                             \
+        if (big_lds(march_tf2d_bwd_kernel<VT, T_>, lds) != hipSuccess) return DR_EUNSUPPORTED;                    \
+        hipLaunchKernelGGL((march_tf2d_bwd_kernel<VT, T_>), grid, dim3(256), lds, stream, P);                     \
+    }
+    if (tables == 2) DR_TF2D_BWD(2) else if (tables == 1) DR_TF2D_BWD(1) else DR_TF2D_BWD(0)
+#undef DR_TF2D_BWD
+    return (int)hipGetLastError();
+}
+
+int launch_march_tf2d_fwd(const Tf2dArgs &a, hipStream_t stream) {
+    return a.vol_dtype == DR_F16 ? tf2d_fwd_dispatch<__half>(a, stream) : tf2d_fwd_dispatch<float>(a, stream);
+}
+
+int launch_march_tf2d_bwd(const Tf2dArgs &a, hipStream_t stream) {
+    return a.vol_dtype == DR_F16 ? tf2d_bwd_dispatch<__half>(a, stream) : tf2d_bwd_dispatch<float>(a, stream);
+}
+
+}  // namespace dr

@@ -14,7 +14,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
+__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "march_tf2d_fwd", "march_tf2d_bwd", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 
@@ -426,6 +426,77 @@ def march_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampl
     N.check(rc, "dr_march_bwd_cam")
     d_cam = torch.nan_to_num(d_cam.float())   # D5: a sum beyond the float range saturates, as nan_to_num makes of d_tf
     return (d_cam, d_ray) if per_ray else d_cam
+
+
+def _tf2d_args(tf2d, n_views):
+    if tf2d.dtype != torch.float32 or not tf2d.is_contiguous():
+        raise TypeError("tf2d must be a contiguous float32 tensor")
+    if tf2d.ndim == 3 and tf2d.shape[2] == 4:
+        return tf2d.data_ptr(), tf2d.shape[0], tf2d.shape[1], 0
+    if tf2d.ndim == 4 and tf2d.shape[3] == 4 and tf2d.shape[0] == n_views:
+        return tf2d.data_ptr(), tf2d.shape[1], tf2d.shape[2], tf2d.stride(0)
+    raise ValueError("tf2d must be (RV,RG,4) or (views,RV,RG,4)")
+
+
+def _g_scale(g_scale):
+    g = float(g_scale)
+    if not (math.isfinite(g) and g > 0.0):
+        raise ValueError(f"g_scale must be finite and > 0, got {g_scale}")
+    return g
+
+
+def march_tf2d_fwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_rate, g_scale, mode=N.DR_MODE_DIFF,
+                   want_steps=True):
+    """The march with a 2-D (value, gradient-magnitude) transfer function (dr_march_tf2d_fwd): march_fwd with the
+    classification rgba = T[I (RV-1), u (RG-1)] (bilinear, value axis first), u = |central-difference taps| * g_scale.
+    tf2d: (RV, RG, 4) shared or (views, RV, RG, 4) float32 contiguous. Returns out (views,W,H,4) and steps (views,W,H) int32
+    (or None). A (RV, 1) table gives march_fwd's bits with the 1-D TF of RV entries."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    dev = vol.device
+    cam = cam.to(torch.float32).contiguous()
+    out = torch.empty((V, W, H, 4), dtype=torch.float32, device=dev)
+    steps = torch.empty((V, W, H), dtype=torch.int32, device=dev) if want_steps else None
+    vargs = _vol_args(vol, V)
+    targs = _tf2d_args(tf2d, V)
+    with torch.cuda.device(dev):
+        rc = N.lib().dr_march_tf2d_fwd(*vargs, *targs, _g_scale(g_scale), cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(),
+                                       rays.data_ptr(), n.data_ptr(), V, W, H, int(max_samples), float(sampling_rate), int(mode),
+                                       out.data_ptr(), steps.data_ptr() if want_steps else None, _stream())
+    N.check(rc, "dr_march_tf2d_fwd")
+    return out, steps
+
+
+def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_rate, g_scale, grad_out, out, want_vol=True,
+                   want_tf=True):
+    """Adjoint of the differentiable march_tf2d_fwd w.r.t. vol and tf2d (dr_march_tf2d_bwd). Returns (d_vol, d_tf2d), either
+    None when not wanted; a shared (un-batched) vol / tf2d receives one gradient accumulated over all views. NaN propagates (the
+    plain kernels' convention: the caller applies nan_to_num, as tf2d.Raycaster2D does)."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    cam = cam.to(torch.float32).contiguous()
+    grad_out = grad_out.to(torch.float32).contiguous()
+    out = out.contiguous()
+    vargs = _vol_args(vol, V)
+    targs = _tf2d_args(tf2d, V)
+    g = _g_scale(g_scale)
+    if not (want_vol or want_tf):
+        return None, None
+    d_vol = d_tf = None
+    dv = (None, 0, 0, 0, 0)
+    if want_vol:
+        d_vol = torch.zeros_like(vol, dtype=torch.float32, memory_format=torch.preserve_format)
+        dv = (d_vol.data_ptr(), *d_vol.stride(), 0) if vol.ndim == 3 else (d_vol.data_ptr(), *d_vol.stride()[1:], d_vol.stride(0))
+    dt = (None, 0)
+    if want_tf:
+        d_tf = torch.zeros_like(tf2d)
+        dt = (d_tf.data_ptr(), d_tf.stride(0) if tf2d.ndim == 4 else 0)
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_march_tf2d_bwd(*vargs, *targs, g, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(),
+                                       n.data_ptr(), V, W, H, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
+                                       out.data_ptr(), *dv, *dt, _stream())
+    N.check(rc, "dr_march_tf2d_bwd")
+    return d_vol, d_tf
 
 
 def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):

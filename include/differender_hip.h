@@ -327,6 +327,40 @@ int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, cons
                 int norm, double eps, const float *upstream, float scale, float *grad,
                 const int64_t *grad_strides4, int accumulate, void *stream);
 
+/* March with a 2-D (value, gradient-magnitude) transfer function (Levoy 1988, Kniss et al. 2002): a material
+ * boundary and the interior of a material of the same value classify differently. Everything is the 1-D march of
+ * dr_march_fwd (positions, jitter, sample count, max_samples clip, opacity correction, Phong shading, compositing, early
+ * termination at A >= 0.99, the non-differentiable mode's alpha > 1e-3 skip and final clamp) except the classification:
+ *   I = trilinear value; (dx, dy, dz) = the six central-difference taps of the shading normal (delta 1e-3);
+ *   u = sqrtf(dx^2 + dy^2 + dz^2) * g_scale;  xv = I (RV - 1), xg = u (RG - 1), split into index and fraction on each axis
+ *   (negative coordinates clamp to 0, indices to R - 1);
+ *   rgba = mix(mix(T[v0][g0], T[v1][g0], fv), mix(T[v0][g1], T[v1][g1], fv), fg)   (value axis first).
+ * A (RV, 1) table is bit for bit the 1-D TF of RV entries. One lane per ray (the shape of DR_VARIANT_BASELINE): no workspace,
+ * no brick path, no camera gradient.
+ *   tf2d     [n_views or 1][RV][RG][4] f32 (RG fastest), tf_view_stride in floats (0 = shared); RV, RG >= 1, RV * RG < 2^31
+ *   g_scale  finite, > 0: u = 1 is the last column of the table (differender_amd.tf2d.gradient_scale estimates one)
+ *   mode     DR_MODE_DIFF or DR_MODE_NONDIFF; out_rgba and steps as for dr_march_fwd
+ * The backward (DR_MODE_DIFF) is the reverse-mode derivative of this program with its branches frozen, hand-derived and
+ * tape-free like dr_march_bwd: d_vol through I, through the normal and through u (onto the same six taps; flat samples,
+ * |grad| = 0, send nothing through either), d_tf2d by the four bilinear weights. Both are ACCUMULATED (caller zeroes) and
+ * nullable; dtf_view_stride 0 = one gradient for a shared table. NaN propagates as in the plain 1-D kernels.
+ * Invalid arguments (null required pointers, extents <= 0, RV * RG >= 2^31, a non-finite or non-positive g_scale, an unknown
+ * mode or dtype) return DR_EINVAL before any HIP call. */
+int dr_march_tf2d_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                      int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                      const float *tf2d, int RV, int RG, int64_t tf_view_stride, float g_scale,
+                      const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                      int mode, float *out_rgba, int32_t *steps, void *stream);
+int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                      int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                      const float *tf2d, int RV, int RG, int64_t tf_view_stride, float g_scale,
+                      const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                      const float *grad_out, const float *out_rgba,
+                      float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                      float *d_tf2d, int64_t dtf_view_stride, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
