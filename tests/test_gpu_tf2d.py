@@ -116,10 +116,9 @@ def test_one_gradient_column_is_the_1d_baseline_bit_for_bit(hiplib, sr, jitter, 
 
 # --- 2. against the float64 transliteration -----------------------------------------------------------------------------------
 
-def _compare(vol, tf2d, cam, WH, S, sr, g_scale, jitter=0, seed=0, floor=1e-5):
-    """GPU forward + backward against the f64 transliteration on the GPU's own ray buffers; the bar is 3x the f32
-    transliteration's own error, with a floor of `floor` x the largest reference element. Rays whose f32 live-sample count
-    differs from the f64 one are masked (zero upstream gradient, not compared)."""
+def _reference(vol, tf2d, cam, WH, S, sr, g_scale, jitter=0, seed=0, count_flat=False):
+    """The GPU forward and the f64 / f32 transliterations on the GPU's own ray buffers, for _compare and _assert_close. Rays whose
+    f32 live-sample count differs from the f64 one are masked (zero upstream gradient `gm`, not compared)."""
     F = _F()
     V = cam.shape[0]
     e, x, r, n = F.ray_setup(cam, WH, vol.shape[-3:], sr, jitter_seed=jitter)
@@ -134,18 +133,34 @@ def _compare(vol, tf2d, cam, WH, S, sr, g_scale, jitter=0, seed=0, floor=1e-5):
     mask = (steps.cpu().numpy() == ref["steps"]) & (ref32["steps"] == ref["steps"]) & (host["n"] > 1)
     assert mask.sum() >= 0.8 * (host["n"] > 1).sum()
     gm = go * mask[..., None]
-    ref = R2.run(*args(gm), pixels=mask)
+    ref = R2.run(*args(gm), pixels=mask, count_flat=count_flat)
     ref32 = R2.run(*args(gm), dtype=torch.float32, pixels=mask)
-    d_vol, d_tf = F.march_tf2d_bwd(vol, tf2d, cam, e, x, r, n, S, sr, g_scale, torch.from_numpy(gm).float().to(DEV), out)
-    got = dict(rgba=C(out) * mask[..., None], dvol=C(d_vol), dtf=C(d_tf))
-    want = dict(rgba=ref["rgba"] * mask[..., None], dvol=ref["dvol"], dtf=ref["dtf"])
-    for k in ("rgba", "dvol", "dtf"):
-        err = np.abs(got[k] - want[k]).max()
-        err32 = np.abs(ref32[k] * (mask[..., None] if k == "rgba" else 1) - want[k]).max()
-        scale = np.abs(want[k]).max()
-        assert scale > 0, k
-        assert err <= 3.0 * err32 + floor * scale, (k, err / scale, err32 / scale)
-    return ref, mask, host
+    return dict(ref=ref, ref32=ref32, mask=mask, host=host, rays=(e, x, r, n), out=out,
+                gm=torch.from_numpy(gm).float().to(DEV))
+
+
+def _assert_close(got, st, k, floor=1e-5):
+    """got (a float64 numpy array) against st["ref"][k] ("rgba", "dvol" or "dtf"): the bar is 3x the f32 transliteration's own
+    error, with a floor of `floor` x the largest reference element."""
+    mask = st["mask"]
+    m = mask[..., None] if k == "rgba" else 1
+    want = st["ref"][k] * m
+    err = np.abs(got * m - want).max()
+    err32 = np.abs(st["ref32"][k] * m - want).max()
+    scale = np.abs(want).max()
+    assert scale > 0, k
+    assert err <= 3.0 * err32 + floor * scale, (k, err / scale, err32 / scale)
+
+
+def _compare(vol, tf2d, cam, WH, S, sr, g_scale, jitter=0, seed=0, floor=1e-5, count_flat=False):
+    """GPU forward + backward against the f64 transliteration on the GPU's own ray buffers (_reference, _assert_close)."""
+    F = _F()
+    st = _reference(vol, tf2d, cam, WH, S, sr, g_scale, jitter, seed, count_flat)
+    d_vol, d_tf = F.march_tf2d_bwd(vol, tf2d, cam, *st["rays"], S, sr, g_scale, st["gm"], st["out"])
+    C = lambda t: t.detach().double().cpu().numpy()
+    for k, got in (("rgba", C(st["out"])), ("dvol", C(d_vol)), ("dtf", C(d_tf))):
+        _assert_close(got, st, k, floor)
+    return st["ref"], st["mask"], st["host"]
 
 
 CASES = {
@@ -157,6 +172,8 @@ CASES = {
     "f16": ((20, 20, 20), (None, None), (16, 16), 8, 6, "opaque", 1.0, 4096, 0, torch.float16),
     "views3": ((16, 18, 20), (3, 3), (12, 12), 8, 6, "opaque", 1.0, 4096, 0, torch.float32),
     "shared_tf": ((16, 18, 20), (3, None), (12, 12), 8, 6, "thin", 1.0, 4096, 0, torch.float32),
+    # one volume, a table per view: d_vol sums over the views, d_tf2d stays per view
+    "shared_vol": ((16, 18, 20), (None, 3), (12, 12), 8, 6, "opaque", 1.0, 4096, 0, torch.float32),
 }
 
 
@@ -190,7 +207,6 @@ def test_nondiff_against_the_f64_transliteration(hiplib, RV, RG):
     1e-3: 0, 5e-4 or 9.9e-4 along u), beside live rows whose alphas grow with u; (128, 80) reads the table where it lies and
     skips nothing. The threshold's own bits are the anchor's (above); here rays with a sample within 1e-5 of alpha 1e-3 in f64
     are left out (f32 and f64 may take the threshold apart), as are rays whose live-sample counts differ."""
-    F, N = _F(), _N()
     vol = _volume((20, 18, 22), seed=15)
     tf = _tf2d(RV, RG, "opaque", seed=16)
     dead = torch.tensor([k % 4 in (0, 1) for k in range(RV)], device=DEV)
@@ -198,22 +214,29 @@ def test_nondiff_against_the_f64_transliteration(hiplib, RV, RG):
     tf[..., 3] = torch.where(dead[:, None], level[:, None].expand(RV, RG), tf[..., 3])
     tf[dead, 0, 3] = 0.0
     tf = tf.contiguous()
-    cam, sr, g_scale = _cams(2), 2.0, _g_scale(vol)
-    e, x, r, n = F.ray_setup(cam, (16, 14), vol.shape, sr)
-    out, steps = F.march_tf2d_fwd(vol, tf, cam, e, x, r, n, 64, sr, g_scale, mode=N.DR_MODE_NONDIFF)   # (no clip)
+    ref, mask = _compare_nondiff(vol, tf, _cams(2), (16, 14), 2.0, _g_scale(vol))
+    assert (ref["steps"] > 64).any()                  # the non-differentiable march has no max_samples clip
+
+
+def _compare_nondiff(vol, tf, cam, WH, sr, g_scale, S=64):
+    """The NONDIFF march against the transliteration's, on the GPU's own ray buffers. Rays with a sample within 1e-5 of alpha
+    1e-3 in f64 or f32 are left out, as are rays whose live-sample counts differ. Returns the f64 result and the compared rays."""
+    F, N = _F(), _N()
+    e, x, r, n = F.ray_setup(cam, WH, vol.shape, sr)
+    out, steps = F.march_tf2d_fwd(vol, tf, cam, e, x, r, n, S, sr, g_scale, mode=N.DR_MODE_NONDIFF)   # (no clip)
     C = lambda t: t.detach().double().cpu().numpy()
     host = (C(vol), C(tf), g_scale, C(cam), C(e), C(x), C(r), n.cpu().numpy())
-    go = np.zeros((2, 16, 14, 4))
-    ref = R2.run(*host, go, 64, sr, want_grad=False, nondiff=True)
-    ref32 = R2.run(*host, go, 64, sr, dtype=torch.float32, want_grad=False, nondiff=True)
+    go = np.zeros((cam.shape[0], *WH, 4))
+    ref = R2.run(*host, go, S, sr, want_grad=False, nondiff=True)
+    ref32 = R2.run(*host, go, S, sr, dtype=torch.float32, want_grad=False, nondiff=True)
     mask = (C(steps) == ref["steps"]) & (ref32["steps"] == ref["steps"]) & ~ref["near"] & ~ref32["near"] & (host[-1] > 1)
     assert mask.sum() >= 0.8 * (host[-1] > 1).sum()
-    assert (ref["steps"] > 64).any()                  # the non-differentiable march has no max_samples clip
     want = ref["rgba"][mask]
     assert (want[:, 3] > 0).any() and (want[:, 3] < 0.99).any()
     err = np.abs(C(out)[mask] - want).max()
     err32 = np.abs(ref32["rgba"][mask] - want).max()
     assert err <= 3.0 * err32 + 1e-5 * np.abs(want).max(), (err, err32)
+    return ref, mask
 
 
 # --- 4. the meaning of the gradient axis ------------------------------------------------------------------------------------

@@ -230,3 +230,39 @@ def test_nondiff_transliteration_with_one_gradient_column_is_the_oracle(oracle):
     assert live.sum() > 10 and (steps[live] > 4).any()
     assert (res["steps"][0][live] == steps[live]).all()
     assert np.abs(res["rgba"][0][live] - rgba[live]).max() <= 1e-10
+
+
+def test_power_of_two_plateaus_are_flat_in_both_precisions():
+    """The premise of the GPU plateau test (tests/test_gpu_tf2d_edges.py): in tf2d_reference.plateau_volume the air (0), the
+    plateaus (0.25, 0.5) and the out-of-range blocks (-0.25, 2.0) give samples whose six taps cancel exactly, in float64 and in
+    float32 alike, and nothing else does; a march through it meets the same flat samples in both precisions."""
+    from oracle import oracle as O
+    vol = R2.plateau_volume((24, 24, 24), seed=1)
+    pos = np.random.RandomState(0).uniform(-1.0, 1.0, size=(20000, 3))
+    flats = {}
+    for dt in (torch.float64, torch.float32):
+        v, p = torch.from_numpy(vol).to(dt), torch.from_numpy(pos).to(dt)
+        I = R2._trilinear(v, p, dt)
+        g = R2.taps(v, p)
+        flat = ((g * g).sum(1) == 0).numpy()
+        I = I.double().numpy()
+        on = np.zeros(len(pos), bool)
+        for level, least in ((0.0, 5000), (0.25, 500), (0.5, 100), (2.0, 100), (-0.25, 100)):
+            at = I == level
+            on |= at
+            assert (at & flat).sum() >= least, (dt, level, (at & flat).sum())
+        assert not (flat & ~on).any(), dt
+        flats[dt] = flat
+    assert (flats[torch.float64] == flats[torch.float32]).all()
+    cam = O.in_circles(0.9).astype(np.float64)
+    e, x, r, n = O.ray_setup(cam, 12, 12, vol.shape, sr=1.0, dtype=np.float64)
+    tf = np.random.RandomState(2).uniform(0.05, 0.95, size=(12, 7, 4))
+    tf[..., 3] = 0.03
+    args = (vol.astype(np.float64), tf, 40.0, cam[None], e[None], x[None], r[None], n[None], np.zeros((1, 12, 12, 4)), 4096,
+            1.0)
+    r64 = R2.run(*args, want_grad=False, count_flat=True)
+    r32 = R2.run(*args, dtype=torch.float32, want_grad=False, count_flat=True)
+    assert (r64["flat"] == r32["flat"]).all() and (r64["steps"] == r32["steps"]).all()
+    live = n > 1
+    assert r64["flat"][0][live].sum() >= 0.3 * r64["steps"][0][live].sum()
+    assert (r64["flat"][0][live] < r64["steps"][0][live]).mean() > 0.5   # and most rays meet structure as well

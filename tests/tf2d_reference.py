@@ -55,8 +55,9 @@ def classify_2d(tf2d, intensity, u):
 
 
 def raycast_tf2d(vol, tf2d, g_scale, cam, entry, exit_, rays, n, max_samples, sampling_rate, nondiff=False):
-    """G.raycast with the 2-D classification, for all pixels at once (one view). Returns (P, 4), the live-sample counts and
-    a mask of the rays with a live sample whose alpha lies within 1e-5 of 1e-3.
+    """G.raycast with the 2-D classification, for all pixels at once (one view). Returns (P, 4), the live-sample counts,
+    a mask of the rays with a live sample whose alpha lies within 1e-5 of 1e-3, and the per-ray count of live flat samples
+    (|grad| = 0 exactly).
     nondiff: the non-differentiable march (VR.py:308-361) -- no max_samples clip, samples with alpha <= 1e-3 are counted but
     not composited, unclamped lighting, the result clamped to <= 1."""
     dt = vol.dtype
@@ -64,6 +65,7 @@ def raycast_tf2d(vol, tf2d, g_scale, cam, entry, exit_, rays, n, max_samples, sa
     tape = torch.zeros((P, 4), dtype=dt)
     count = torch.zeros(P, dtype=torch.long)
     near = torch.zeros(P, dtype=torch.bool)
+    nflat = torch.zeros(P, dtype=torch.long)
     ambient, diffuse_k, specular_k, shininess = 0.4, 0.8, 0.3, 32.0
     light_pos = cam + torch.tensor([0.0, 1.0, 0.0], dtype=dt)
     nf = n.to(dt)
@@ -102,18 +104,21 @@ def raycast_tf2d(vol, tf2d, g_scale, cam, entry, exit_, rays, n, max_samples, sa
         lit = (active & (sample_color[:, 3] > 1e-3)) if nondiff else active
         tape = torch.where(lit[:, None], new, tape)
         count = count + active.long()
+        nflat = nflat + (active & flat).long()
     if nondiff:
         tape = torch.clamp(tape, max=1.0)
-    return tape, count, near
+    return tape, count, near, nflat
 
 
 def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, sampling_rate, dtype=torch.float64,
-        want_grad=True, pixels=None, want_vol=True, nondiff=False):
+        want_grad=True, pixels=None, want_vol=True, nondiff=False, count_flat=False):
     """The transliteration over views. vol (VX,VY,VZ) or (V,VX,VY,VZ), tf2d (RV,RG,4) or (V,RV,RG,4), cam (V,3), ray buffers
     (V,W,H[,3]) and grad_out (V,W,H,4): numpy arrays (the GPU's ray buffers, copied). Rays with n <= 1 are not marched (0/0 in
     the reference, H6) and `pixels` (a (V,W,H) mask) restricts the march further. Returns rgba, steps, d_vol, d_tf2d as float64
     numpy arrays in the shapes of the inputs (the gradients of sum(out * grad_out); want_vol=False leaves d_vol out), and `near`,
-    the (V,W,H) mask of rays with a sample whose alpha lies within 1e-5 of the non-differentiable march's 1e-3 threshold."""
+    the (V,W,H) mask of rays with a sample whose alpha lies within 1e-5 of the non-differentiable march's 1e-3 threshold.
+    count_flat: also return "flat", the (V,W,H) count of each ray's live samples whose six taps cancel exactly (|grad| = 0 in
+    `dtype`)."""
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
     V, W, H = n.shape
     volt = T(vol).requires_grad_(want_grad and want_vol)
@@ -121,6 +126,7 @@ def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, s
     rgba = np.zeros((V, W, H, 4))
     steps = np.zeros((V, W, H), np.int32)
     near = np.zeros((V, W, H), bool)
+    nflat = np.zeros((V, W, H), np.int64)
     total = 0.0
     for v in range(V):
         live = n[v].reshape(-1) > 1
@@ -129,7 +135,7 @@ def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, s
         sel = torch.from_numpy(np.nonzero(live)[0])
         if sel.numel() == 0:
             continue
-        out, cnt, nr = raycast_tf2d(volt[v] if vol.ndim == 4 else volt, tft[v] if tf2d.ndim == 4 else tft, float(g_scale),
+        out, cnt, nr, nf = raycast_tf2d(volt[v] if vol.ndim == 4 else volt, tft[v] if tf2d.ndim == 4 else tft, float(g_scale),
                                 T(cam[v]), T(entry[v]).reshape(-1)[sel], T(exit_[v]).reshape(-1)[sel],
                                 T(rays[v]).reshape(-1, 3)[sel], torch.from_numpy(n[v].astype(np.int64)).reshape(-1)[sel],
                                 int(max_samples), float(sampling_rate), nondiff)
@@ -139,8 +145,12 @@ def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, s
         steps[v] = st.reshape(W, H)
         nm = np.zeros(W * H, bool); nm[sel.numpy()] = nr.numpy()
         near[v] = nm.reshape(W, H)
+        fl = np.zeros(W * H, np.int64); fl[sel.numpy()] = nf.numpy()
+        nflat[v] = fl.reshape(W, H)
         total = total + (out * T(grad_out[v]).reshape(-1, 4)[sel]).sum()
     res = dict(rgba=rgba, steps=steps, near=near)
+    if count_flat:
+        res["flat"] = nflat
     if want_grad:
         if torch.is_tensor(total):
             total.backward()
@@ -148,3 +158,25 @@ def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, s
             res["dvol"] = volt.grad.double().numpy() if volt.grad is not None else np.zeros(vol.shape)
         res["dtf"] = tft.grad.double().numpy() if tft.grad is not None else np.zeros(tf2d.shape)
     return res
+
+
+def plateau_volume(shape, seed=0, lo=-0.25, hi=2.0):
+    """A field-order (VX, VY, VZ) float32 object in air with exact plateaus, by Chebyshev distance m = max(|x|, |y|, |z|) from
+    the centre ([-1, 1] on every axis): air exactly 0 (m >= 0.72), a plateau at exactly 0.25 (0.48 <= m < 0.72), a shell with
+    structure in [0.1, 0.9] (0.26 <= m < 0.48), a core plateau at exactly 0.5 (m < 0.26); and two blocks outside the value
+    range, `hi` (> 1) and `lo` (< 0), cut into the 0.25 plateau. No voxel lies in (0, 1e-3) or (-1e-3, 0).
+
+    The plateau values are powers of two: there mix(x, x, a) = x exactly both with an fma and with a product sum, so the six
+    taps of a sample whose eight voxels all hold x cancel exactly in float32 and float64 -- the kernel and the transliteration
+    see the same flat samples. (At a generic value such as 1.3 both give rounding-noise taps, each with its own direction; the
+    defaults of `lo` and `hi` are powers of two for that reason.)"""
+    rng = np.random.RandomState(seed)
+    axes = [np.linspace(-1.0, 1.0, s) for s in shape]
+    x, y, z = np.meshgrid(*axes, indexing="ij")
+    m = np.maximum(np.maximum(np.abs(x), np.abs(y)), np.abs(z))
+    shell = 0.5 + 0.3 * np.sin(5.1 * x + 0.7) * np.cos(4.3 * y - 0.2) * np.sin(3.7 * z + 1.1) + 0.08 * rng.standard_normal(shape)
+    shell = np.clip(shell, 0.1, 0.9)
+    vol = np.where(m < 0.26, 0.5, np.where(m < 0.48, shell, np.where(m < 0.72, 0.25, 0.0)))
+    vol = np.where((m >= 0.48) & (m < 0.72) & (x > 0.2) & (y > 0.2), hi, vol)
+    vol = np.where((m >= 0.48) & (m < 0.72) & (x < -0.2) & (y < -0.2), lo, vol)
+    return vol.astype(np.float32)
