@@ -6,7 +6,12 @@ One "step" = one pass of the hot path over one view per rank: ray setup -> forwa
 A voxel-step = one marched sample (sum of the per-pixel executed-step counters, VR.py:303,381).
 Inputs are synthetic and resident in HBM before the timed region. Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else. --full adds what
+the headline figure does not need, each untimed and after the timed steps: the evaluated-sample count, the live counter
+passes (--pmc auto), the CPU baseline with its parity check, and for N > 1 the synchronous steps, the all-reduce alone and
+the forwards alone. Fields of the line that those fill are null in a plain run.
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment, what the
 driver does), or started plainly -- then this process spawns the N ranks itself, before touching the GPU, and
@@ -128,13 +133,16 @@ def parse_args(argv=None):
                          "term runs through the torch restatement of pytorch_msssim.ssim (differender_amd/utils/losses.py): +2.7 ms "
                          "per iteration of torch convolutions outside the raycasting path -- rounds 1-5 quoted the loop without it "
                          "(tools/abn_opt.sh still does: same-device A/B of the raycasting path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline figure as well (see the module docstring): evaluated samples, "
+                         "live counters, CPU baseline, N > 1 extras; off: only what value and ms_per_step need")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-tape", action="store_true", help="--grads tf: the brick-centric TF-only backward instead of the per-sample tape (DR_TAPE_TF)")
     ap.add_argument("--cpu-img", type=int, default=None,
                     help="image edge of the CPU-baseline sample (default: the whole view, capped at 512: ~20 s on 16 cores)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "live", "off"],
                     help="roofline.traffic: 'live' collects FETCH_SIZE / WRITE_SIZE with rocprofv3 around short child runs of "
-                         "this very command; 'auto' = live for the default single-GPU headline, else off")
+                         "this very command; 'auto' = live for the default single-GPU headline under --full, else off")
     ap.add_argument("--pmc-json", default=None, help="use this per-launch counter file (tools/profile_round.sh) instead")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the outputs of the last timed step as DIR/<name>.npy (see dump_outputs)")
@@ -222,7 +230,8 @@ PMC_PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",),
 
 def measure_traffic_live(argv_workload):
     """roofline.traffic and roofline_valu, measured in THIS job: rocprofv3 --pmc around short child runs of the same
-    command, one pass per entry of PMC_PASSES, --kernel-trace only.
+    command, one pass per entry of PMC_PASSES, --kernel-trace only. The children run with --full (its evaluated-sample step
+    included) and without the CPU baseline or counters of their own.
     Returns ({kernel: {counter: average per launch, "launches": n}}, note)."""
     exe = shutil.which("rocprofv3")
     if exe is None:
@@ -245,7 +254,7 @@ def measure_traffic_live(argv_workload):
         for counters in PMC_PASSES:
             out = os.path.join(work, counters[0])
             cmd = [exe, "--pmc", *counters, "--kernel-trace", "--output-format", "csv", "-d", out, "--",
-                   sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                   sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                    "--pmc", "off"] + argv_workload
             p = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=420)
             files = glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True)
@@ -611,9 +620,10 @@ def main():
 
     # N > 1: the number an OPTIMISATION loop would see, next to the overlapped one -- the same steps once more with every
     # step's gradient all-reduce awaited before the next forward starts (a throughput benchmark may hide the
-    # exchange behind the next forward, backward -> optimiser step -> next forward cannot)
+    # exchange behind the next forward, backward -> optimiser step -> next forward cannot). This and every other untimed
+    # measurement below run under --full only (the same argv on every rank: all ranks take the same branches).
     ms_per_step_sync, sync_steps = None, 0
-    if dist is not None and want_bwd:
+    if args.full and dist is not None and want_bwd:
         sync_steps = min(max(args.steps, 1), 10)
         barrier()
         ts = time.perf_counter()
@@ -629,7 +639,7 @@ def main():
     # still count as marched, and a roofline priced with the marched count would credit a kernel with bytes it never touched
     # (profiles/r05_bench_lines.jsonl carried frac = 8.93 for a 0.34 ms backward).
     evaluated = None
-    if ws is not None:
+    if args.full and ws is not None:
         barrier()
         try:
             marched_one = step(args.warmup + max(args.steps, 1) - 1, False, count=True)
@@ -646,7 +656,7 @@ def main():
     # the exchange step on its own (not overlapped): K synchronous all-reduces of the gradient buffers
     allreduce_ms = None
     allreduce_bytes = None
-    if dist is not None and want_bwd:
+    if args.full and dist is not None and want_bwd:
         grads = [g for g in last[2:] if g is not None]
         allreduce_bytes = int(sum(g.numel() * g.element_size() for g in grads))
         barrier()
@@ -660,7 +670,7 @@ def main():
     # the previous step's gradient all-reduce in flight on RCCL's stream. The same forwards once more with nothing in
     # flight, per rank, so that ONE run shows what the collective's channels take from the march.
     fwd_alone_ms = None
-    if dist is not None and want_bwd:
+    if args.full and dist is not None and want_bwd:
         barrier()
         pairs = []
         for k in range(min(max(args.steps, 1), 5)):
@@ -739,7 +749,7 @@ def main():
     default_cmd = world == 1 and args.variant == 0
     if args.pmc_json:
         pm = json.load(open(args.pmc_json)); traffic_source = f"counter file {args.pmc_json}"
-    elif args.pmc == "live" or (args.pmc == "auto" and default_cmd and N == 512 and IMG == 512 and args.tf == "bench"
+    elif args.pmc == "live" or (args.pmc == "auto" and args.full and default_cmd and N == 512 and IMG == 512 and args.tf == "bench"
                                 and args.grads == "vol+tf" and V == 1):
         wl = ["--vol", str(N), "--img", str(IMG), "--tf-res", str(R), "--grads", args.grads, "--tf", args.tf,
               "--views", str(V), "--vol-dtype", args.vol_dtype, "--cam", args.cam] + (["--jitter"] if args.jitter else [])
@@ -761,7 +771,7 @@ def main():
             rf["bound"] = observed_bound(vr, rf.get("hbm_frac_measured"))
 
     cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = run_cpu_baseline(vol, tf, args, sr, want_vol, want_tf, gpu=(F, dev, ws))
 
     workload = {"vol+tf": "C4: fwd+bwd w.r.t. volume and TF", "tf": "C3: fwd+bwd w.r.t. TF",
@@ -786,8 +796,8 @@ def main():
                    "tf_only_backward": (("per-sample tape (DR_TAPE_TF)" if use_tape else "brick-centric") if (want_tf and not want_vol) else None)},
         "voxel_steps_per_step": int(vsteps / max(args.steps, 1)),
         "planned_steps_per_step": int(int(planned_steps.item()) / max(args.steps, 1)),  # executed/planned < 1 = early termination
-        "evaluated_voxel_steps": evaluated,   # one untimed step under DR_COUNT_EVALUATED: marched samples vs samples whose taps were evaluated
-        "ms_per_step_sync": None if ms_per_step_sync is None else round(ms_per_step_sync, 4),   # N > 1: every step's all-reduce awaited before the next forward
+        "evaluated_voxel_steps": evaluated,   # --full: one untimed step under DR_COUNT_EVALUATED: marched samples vs samples whose taps were evaluated
+        "ms_per_step_sync": None if ms_per_step_sync is None else round(ms_per_step_sync, 4),   # N > 1, --full: every step's all-reduce awaited before the next forward
         "sync_steps": sync_steps or None,
         "build_flags": int(F.N.lib().dr_build_flags()),   # 0 = the shipped kernels; 4 = built without a tuned compiler flag (csrc/Makefile)
         "ms_per_step_ranks": [round(v, 4) for v in rank_ms],

@@ -33,6 +33,13 @@ def test_allreduce_model_matches_the_survey_figures():
     assert B.allreduce_model(512 * 2 ** 20, 1) is None and B.allreduce_model(None, 8) is None
 
 
+def test_extras_are_off_unless_full_is_asked_for():
+    B = _bench()
+    a = B.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.steps == 3 and a.warmup == 1 and a.pmc == "auto" and not a.no_cpu_baseline
+    assert B.parse_args(["--full"]).full
+
+
 def test_host_cores_reports_what_the_process_may_use():
     B = _bench()
     n, note = B.host_cores()

@@ -1,6 +1,6 @@
 """bench.py --dump-outputs on a small configuration: the files hold what the LAST timed step computed (its image, sample counts and
 gradients, recomputed here through the same calls for that step's camera -- every step has its own camera), and the result line
-reports the timed steps it was asked for."""
+reports the timed steps it was asked for. A plain run leaves the untimed extras out; --full runs them."""
 import json
 import math
 import os
@@ -63,3 +63,27 @@ def test_dump_outputs_hold_the_last_timed_step(hiplib, tmp_path):
     # ... and not an earlier step's: the camera of step k - 1 renders a visibly different image
     prev = render(k - 1)[2].cpu().numpy()
     assert float(np.abs(got["image"] - prev).max()) > 100 * max(err, 1e-6)
+
+
+def test_plain_run_stops_at_the_headline_and_full_adds_the_rest(hiplib, tmp_path):
+    """A plain run times its steps and prints the line, nothing more; --full adds the evaluated-sample step and the CPU
+    baseline with its parity check (at this size --pmc auto collects no counters either way). Both time the same work."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--vol", str(N), "--img", str(IMG), "--tf-res", str(R),
+            "--steps", str(STEPS), "--warmup", str(WARMUP)]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        p = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, p.stdout
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == STEPS and line["warmup"] == WARMUP and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["roofline_fwd"]["avg_launch_ms"] > 0 and line["roofline_bwd"]["avg_launch_ms"] > 0
+    assert plain["voxel_steps_per_step"] == full["voxel_steps_per_step"] > 0
+    assert plain["evaluated_voxel_steps"] is None and plain["cpu_baseline"] is None and plain["traffic_source"] is None
+    ev = full["evaluated_voxel_steps"]
+    assert ev["marched"] > 0 and ev["march_fwd"] > 0 and ev["march_bwd"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["parity_vs_gpu"]["within_north_star_bars"]
+    assert full["traffic_source"] is None
