@@ -18,21 +18,16 @@
 // adjoint needs the composite in front of the sample, which the sequential walk has for free; the wave-per-ray alternative
 // (DPP scans over 64 samples) would be faster on long rays but needs its own tap/adjoint pipeline. Sums: f32 per ray, f64 per
 // workgroup (LDS), then ONE f64 atomic per component per workgroup into d_cam[view][3] (no per-sample or per-ray atomics).
-#include "dr_device.h"
-#include "dr_kernels.h"
-#include "../../include/differender_hip.h"
+#include "dr_tile.h"
 
 namespace dr {
 
 template <typename VT>
-struct CamParams {
-    VolView<VT> vol; int64_t vol_vs;
-    const float4 *tf; int64_t tf_vs; int R; float tf_len;
-    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp, *steps;
-    int W, H, S, img_W, row0; float inv_sr;
+struct CamParams : RayParams<VT> {
+    const int32_t *fwd_steps;   // the forward's live samples per ray
+    int img_W, row0;
     float near_, near_w, near_h;
     uint32_t jitter_seed, view_base;
-    const float *grad_out, *out_fwd;
     double *d_cam; float *d_cam_ray;
 };
 
@@ -104,49 +99,35 @@ __device__ __forceinline__ f3 slab_grad(int axis, float t, float inv_vda, const 
     return f3_fma(-inv_vda, make_f3(w0, w1, w2), f3_scale(-t * inv_vda, row));
 }
 
-__device__ __forceinline__ float cam_finite(float x) { return (x == x) ? fminf(fmaxf(x, -1.0e30f), 1.0e30f) : 0.0f; }
-
 template <typename VT, bool TF_LDS>
 __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     __shared__ double red[3][256];
     const int view = blockIdx.y;
-    const float4 *tfg = P.tf + view * P.tf_vs;
-    if (TF_LDS) {
-        for (int k = threadIdx.x; k < P.R; k += 256) lds_tf_[k] = tfg[k];
-        __syncthreads();
-    }
-    const float4 *tf = TF_LDS ? lds_tf_ : tfg;
+    const float4 *tf = stage_table<TF_LDS>(lds_tf_, P.tf + view * P.tf_vs, P.R);
 
     f3 dcam = make_f3(0.f, 0.f, 0.f);
-    const int tiles_j = (P.H + 7) >> 3;
-    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const int i = (wave / tiles_j) * 8 + (lane >> 3);
-    const int j = (wave % tiles_j) * 8 + (lane & 7);
+    int i, j;
+    const bool in_img = tile_pixel(P.W, P.H, i, j);
     const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    const bool in_img = i < P.W && j < P.H;
-    const int n = in_img ? P.nsamp[p] : 0;
     // H6: a single-sample ray sits at 0/0 in the reference and contributes nothing
-    if (in_img && n > 1) {
+    if (in_img && P.nsamp[p] > 1) {
         VolView<VT> vol = P.vol;
         vol.p += view * P.vol_vs;
         const f3 lf = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
         const f3 light = make_f3(lf.x + 0.0f, lf.y + 1.0f, lf.z + 0.0f);
         RayGeom rg;
-        rg.n = n; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
-        rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
-        rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
         const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
         int nmarch = rg.n > P.S ? P.S : rg.n;
-        nmarch = min(nmarch, P.steps[p]);   // the forward's live samples (early termination frozen)
+        nmarch = min(nmarch, P.fwd_steps[p]);   // the forward's live samples (early termination frozen)
 
         const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
         const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
         const float delta = 1e-3f;
         f3 sP = make_f3(0.f, 0.f, 0.f), sTG = make_f3(0.f, 0.f, 0.f);
         float s0 = 0.f, s1 = 0.f;
-        float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+        Composite c;
         for (int s = 0; s < nmarch; ++s) {
             Sample sm;
             sample_pos(rg, lf.x, lf.y, lf.z, s, sm.px, sm.py, sm.pz);
@@ -163,15 +144,10 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
             const float dz = vp - vm;
             ddz = make_f3(gp.x - gm.x, gp.y - gm.y, gp.z - gm.z);
             shade_from_grad<false>(dx, dy, dz, light, vd, true, sm);
-            const float T = 1.0f - A;
-            C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
-            C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
-            C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
-            A = fmaf(T, sm.op, A);
+            const float T = c.add(sm);
             const bool last = s == nmarch - 1;
-            const float suffix = (go.x * (of.x - C0) + go.y * (of.y - C1) + go.z * (of.z - C2)) + go.w * (of.w - A);
             SampleAdj ad;
-            sample_adjoint(sm, vd, T, suffix, last, go, P.inv_sr, ad);
+            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
             const float I_bar = intensity_adjoint(sm, tf[sm.lo], tf[sm.hi], ad, P.tf_len);
             // dL/dpos through the taps: the intensity tap and the central differences of the normal (0 when flat, D1)
             f3 Ps = f3_scale(I_bar, gI);
@@ -227,7 +203,7 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
         dcam = f3_fma(s0, g_t0, dcam);
         dcam = f3_fma(s1, g_tmax, dcam);
         // D5: a NaN ray (NaN upstream gradient) contributes nothing, infinities are clamped
-        dcam = make_f3(cam_finite(dcam.x), cam_finite(dcam.y), cam_finite(dcam.z));
+        dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
     }
     if (in_img && P.d_cam_ray) {
         P.d_cam_ray[3 * p] = dcam.x; P.d_cam_ray[3 * p + 1] = dcam.y; P.d_cam_ray[3 * p + 2] = dcam.z;
@@ -247,30 +223,17 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
 
 template <typename VT>
 static int cam_dispatch(const MarchArgs &a, const CamArgs &c, hipStream_t stream) {
-    CamParams<VT> P;
-    P.vol.p = static_cast<const VT *>(a.vol);
-    P.vol.sx = a.sx; P.vol.sy = a.sy; P.vol.sz = a.sz;
-    P.vol.VX = a.VX; P.vol.VY = a.VY; P.vol.VZ = a.VZ;
-    P.vol.scx = (float)((double)a.VX - 1.0 - 1e-4);
-    P.vol.scy = (float)((double)a.VY - 1.0 - 1e-4);
-    P.vol.scz = (float)((double)a.VZ - 1.0 - 1e-4);
-    P.vol_vs = a.vol_vs;
-    P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4; P.R = a.R; P.tf_len = (float)(a.R - 1);
-    P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp; P.steps = c.steps;
-    P.W = a.W; P.H = a.H; P.S = a.S; P.img_W = a.img_W; P.row0 = a.row0; P.inv_sr = 1.0f / a.sr;
+    CamParams<VT> P{make_ray_params<VT>(a)};
+    P.fwd_steps = c.steps; P.img_W = a.img_W; P.row0 = a.row0;
     // VR.py:146-147 as ray_setup.hip forms them: doubles, rounded once
     const double near_h = 2.0 * tan(a.fov_rad) * a.near_plane;
     const double near_w = near_h * ((double)a.img_W / (double)a.H);
     P.near_ = (float)a.near_plane; P.near_w = (float)near_w; P.near_h = (float)near_h;
     P.jitter_seed = c.jitter_seed; P.view_base = c.view_base;
-    P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
     P.d_cam = c.d_cam; P.d_cam_ray = c.d_cam_ray;
-    const int tiles = ((a.W + 7) / 8) * ((a.H + 7) / 8);
-    const dim3 grid((tiles + 3) / 4, a.n_views);
     const size_t lds = (size_t)a.R * sizeof(float4);
-    if (lds <= 48 * 1024) hipLaunchKernelGGL((camera_grad_kernel<VT, true>), grid, dim3(256), lds, stream, P);
-    else hipLaunchKernelGGL((camera_grad_kernel<VT, false>), grid, dim3(256), 0, stream, P);   // a large TF is read where it lies
-    return (int)hipGetLastError();
+    if (lds <= 48 * 1024) return launch_tiles(camera_grad_kernel<VT, true>, a, lds, stream, P);
+    return launch_tiles(camera_grad_kernel<VT, false>, a, 0, stream, P);   // a large TF is read where it lies
 }
 
 int launch_camera_grad(const MarchArgs &a, const CamArgs &c, hipStream_t stream) {

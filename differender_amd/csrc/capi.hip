@@ -113,9 +113,22 @@ static int fill_common(MarchArgs &a, const void *vol, int vol_dtype, int VX, int
     a = MarchArgs{};
     a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
     a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
-    a.tf = tf; a.R = R; a.tf_vs = tf_view_stride;
+    a.tf = tf; a.R = R; a.tf_vs = tf_view_stride; a.RG = 1;
     a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
     a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate;
+    return 0;
+}
+
+// the fields of a backward over the forward's output out_rgba (grad_out: its upstream gradient), shared by the 1-D and the
+// 2-D TF march
+static int fill_bwd(MarchArgs &a, const float *grad_out, const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy,
+                    int64_t dsz, int64_t dvol_view_stride, float *d_tf, int64_t dtf_view_stride) {
+    if (!grad_out || !out_rgba) return DR_EINVAL;
+    if (dtf_view_stride % 4 != 0) return DR_EINVAL;
+    a.mode = DR_MODE_DIFF;
+    a.grad_out = grad_out; a.out_fwd = out_rgba;
+    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
+    a.d_tf = d_tf; a.dtf_vs = dtf_view_stride;
     return 0;
 }
 
@@ -187,7 +200,8 @@ int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
                          entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
-    if (!grad_out || !out_rgba) return DR_EINVAL;
+    rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf, dtf_view_stride);
+    if (rc) return rc;
     if (row0 < 0 || img_W < W || row0 > img_W - W) return DR_EINVAL;
     a.img_W = img_W; a.row0 = row0;
     const int bwd_flags = variant & ~0xff;
@@ -195,14 +209,10 @@ int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     if (bwd_flags & ~(DR_COUNT_EVALUATED | DR_TAPE_TF)) return DR_EINVAL;
     if ((bwd_flags & DR_TAPE_TF) && d_vol) return DR_EINVAL;   // the tape serves the TF-only backward
     if (variant < DR_VARIANT_AUTO || variant > DR_VARIANT_BASELINE) return DR_EINVAL;
-    if (dtf_view_stride % 4 != 0) return DR_EINVAL;
     if (!d_vol && !d_tf) return 0;  // nothing requested
     DeviceOf guard(vol);
     if (guard.err != hipSuccess) return (int)guard.err;
-    a.mode = DR_MODE_DIFF; a.hints = bwd_flags;
-    a.grad_out = grad_out; a.out_fwd = out_rgba;
-    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
-    a.d_tf = d_tf; a.dtf_vs = dtf_view_stride;
+    a.hints = bwd_flags;
     a.fov_rad = fov_rad; a.near_plane = near_plane; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
     if (dr_march_bwd_variant(n_views, W, H, VX, VY, VZ, R, sx, sy, sz, dsx, dsy, dsz, d_vol != nullptr, variant,
                              workspace != nullptr) == DR_VARIANT_AUTO) {
@@ -398,23 +408,17 @@ int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, cons
     return launch_tv3d_bwd(a, (hipStream_t)stream);
 }
 
-static int fill_tf2d(Tf2dArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+// fill_common with R = RV, and what only the 2-D TF checks: the texel index RV * RG stays below 2^31, g_scale
+static int fill_tf2d(MarchArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                      int64_t vol_view_stride, const float *tf2d, int RV, int RG, int64_t tf_view_stride, float g_scale,
                      const float *cam, const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
                      int n_views, int W, int H, int max_samples, float sampling_rate) {
-    if (!vol || !tf2d || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
-    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
-    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
-    if (RV < 1 || RG < 1 || (int64_t)RV * RG >= ((int64_t)1 << 31)) return DR_EINVAL;
+    const int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf2d, RV, tf_view_stride, cam, entry,
+                               exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (RG < 1 || (int64_t)RV * RG >= ((int64_t)1 << 31)) return DR_EINVAL;
     if (!std::isfinite(g_scale) || !(g_scale > 0.0f)) return DR_EINVAL;
-    if (max_samples < 0 || !(sampling_rate > 0.0f)) return DR_EINVAL;
-    if (tf_view_stride % 4 != 0) return DR_EINVAL;
-    a = Tf2dArgs{};
-    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
-    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
-    a.tf = tf2d; a.RV = RV; a.RG = RG; a.tf_vs = tf_view_stride; a.g_scale = g_scale;
-    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
-    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate;
+    a.RG = RG; a.g_scale = g_scale;
     return 0;
 }
 
@@ -423,7 +427,7 @@ int dr_march_tf2d_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
                       const float *cam, const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
                       int n_views, int W, int H, int max_samples, float sampling_rate, int mode, float *out_rgba,
                       int32_t *steps, void *stream) {
-    Tf2dArgs a;
+    MarchArgs a;
     int rc = fill_tf2d(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf2d, RV, RG, tf_view_stride, g_scale, cam,
                        entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
@@ -442,17 +446,13 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
                       int n_views, int W, int H, int max_samples, float sampling_rate, const float *grad_out,
                       const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
                       float *d_tf2d, int64_t dtf_view_stride, void *stream) {
-    Tf2dArgs a;
+    MarchArgs a;
     int rc = fill_tf2d(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf2d, RV, RG, tf_view_stride, g_scale, cam,
                        entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
-    if (!grad_out || !out_rgba) return DR_EINVAL;
-    if (dtf_view_stride % 4 != 0) return DR_EINVAL;
+    rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf2d, dtf_view_stride);
+    if (rc) return rc;
     if (!d_vol && !d_tf2d) return 0;  // nothing requested
-    a.mode = DR_MODE_DIFF;
-    a.grad_out = grad_out; a.out_fwd = out_rgba;
-    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
-    a.d_tf = d_tf2d; a.dtf_vs = dtf_view_stride;
     DeviceOf guard(vol);
     if (guard.err != hipSuccess) return (int)guard.err;
     if (!launch_march_tf2d_bwd) return DR_EUNSUPPORTED;

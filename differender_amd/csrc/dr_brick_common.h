@@ -4,6 +4,7 @@
 #pragma once
 #include "dr_brick.h"
 #include "dr_kernels.h"
+#include "dr_tile.h"
 #include "../../include/differender_hip.h"
 #include <string.h>
 
@@ -556,12 +557,6 @@ __device__ __forceinline__ bool sample_coords_at(const VolView<VT> &vol, const B
     sample_normal_coords_at(vol, c, sm, t);
     return true;
 }
-__device__ __forceinline__ void load_ray(const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
-                                         size_t p, RayGeom &rg) {
-    rg.n = nsamp[p]; rg.entry = entry[p]; rg.exit_ = exit_[p];
-    rg.vx = rays[3 * p]; rg.vy = rays[3 * p + 1]; rg.vz = rays[3 * p + 2];
-    rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
-}
 
 // ---- LDS gradient accumulators --------------------------------------------------------------------------
 // ds_add_f32 is serialised on gfx950 (193 cycles per wave-instruction whatever the addresses), ds_add_u64 takes 9-12 and
@@ -727,13 +722,7 @@ static inline size_t ws_layout(void *base, int n_views, int NP, const BrickGrid 
 template <typename VT>
 static inline BrickParams<VT> make_brick_params(const MarchArgs &a, const Workspace &w) {
     BrickParams<VT> P;
-    P.vol.p = static_cast<const VT *>(a.vol);
-    P.vol.sx = a.sx; P.vol.sy = a.sy; P.vol.sz = a.sz;
-    P.vol.VX = a.VX; P.vol.VY = a.VY; P.vol.VZ = a.VZ;
-    P.vol.scx = (float)((double)a.VX - 1.0 - 1e-4);
-    P.vol.scy = (float)((double)a.VY - 1.0 - 1e-4);
-    P.vol.scz = (float)((double)a.VZ - 1.0 - 1e-4);
-    P.vol_vs = a.vol_vs;
+    P.vol = make_vol_view<VT>(a); P.vol_vs = a.vol_vs;
     P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4; P.R = a.R; P.tf_len = (float)(a.R - 1);
     P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp;
     P.W = a.W; P.H = a.H; P.S = a.S; P.sr = a.sr; P.inv_sr = 1.0f / a.sr;

@@ -219,6 +219,13 @@ struct RayGeom {
     float inv_nm1; // unused by the baseline (kept exact: division per sample)
 };
 
+__device__ __forceinline__ void load_ray(const float *entry, const float *exit_, const float *rays, const int32_t *nsamp,
+                                         size_t p, RayGeom &rg) {
+    rg.n = nsamp[p]; rg.entry = entry[p]; rg.exit_ = exit_[p];
+    rg.vx = rays[3 * p]; rg.vy = rays[3 * p + 1]; rg.vz = rays[3 * p + 2];
+    rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+}
+
 // VR.py:277-280: pos = cam + mix(t0, exit, s/(n-1)) * vd
 __device__ __forceinline__ void sample_pos(const RayGeom &rg, float cx, float cy, float cz, int s, float &px, float &py,
                                            float &pz) {
@@ -437,6 +444,32 @@ __device__ __forceinline__ void sample_adjoint(const Sample &sm, f3 vd, float T,
     ad.gy = inv * (n_bar.y - sm.nrm.y * nn);
     ad.gz = inv * (n_bar.z - sm.nrm.z * nn);
 }
+// The front-to-back composite of the sequential march, in the D2 order.
+struct Composite {
+    float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+    // composites one shaded sample; returns T = 1 - A in front of it
+    __device__ __forceinline__ float add(const Sample &sm) {
+        const float T = 1.0f - A;
+        C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
+        C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
+        C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
+        A = fmaf(T, sm.op, A);
+        return T;
+    }
+    // the pixel; the non-differentiable march clamps every channel to 1 (VR.py:358)
+    __device__ __forceinline__ float4 pixel(bool clamp) const {
+        if (!clamp) return make_float4(C0, C1, C2, A);
+        return make_float4(fminf(1.0f, C0), fminf(1.0f, C1), fminf(1.0f, C2), fminf(1.0f, A));
+    }
+    // what the samples after this prefix contribute to the loss: gC.(C_final - C_s) + gA.(A_final - A_s)
+    __device__ __forceinline__ float suffix(float4 go, float4 of) const {
+        return (go.x * (of.x - C0) + go.y * (of.y - C1) + go.z * (of.z - C2)) + go.w * (of.w - A);
+    }
+};
+
+// D5: a NaN contributes nothing, infinities are clamped
+__device__ __forceinline__ float finite_or_zero(float x) { return (x == x) ? fminf(fmaxf(x, -1.0e30f), 1.0e30f) : 0.0f; }
+
 // adjoint of the intensity tap given the TF texels around it
 __device__ __forceinline__ float intensity_adjoint(const Sample &sm, float4 t0, float4 t1, const SampleAdj &ad,
                                                    float tf_len) {

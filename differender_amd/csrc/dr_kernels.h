@@ -10,6 +10,7 @@ namespace dr {
 struct MarchArgs {
     const void *vol; int vol_dtype; int VX, VY, VZ; int64_t sx, sy, sz, vol_vs;
     const float *tf; int R; int64_t tf_vs;
+    int RG; float g_scale;  // 2-D TF (march_tf2d.hip): [R][RG] texels, R its value rows; RG = 1 for the 1-D TF
     const float *cam, *entry, *exit_, *rays; const int32_t *nsamp;
     int n_views, W, H, S; float sr; int mode;
     int img_W, row0;  // the W rows of the buffers are rows [row0, row0 + W) of an image img_W rows wide (bands)
@@ -145,22 +146,10 @@ struct TVArgs {
 __attribute__((weak)) int launch_tv3d_fwd(const TVArgs &a, hipStream_t stream);
 __attribute__((weak)) int launch_tv3d_bwd(const TVArgs &a, hipStream_t stream);
 
-// March with a 2-D (value, gradient-magnitude) transfer function (march_tf2d.hip): the arguments of
-// dr_march_tf2d_fwd / dr_march_tf2d_bwd
-struct Tf2dArgs {
-    const void *vol; int vol_dtype; int VX, VY, VZ; int64_t sx, sy, sz, vol_vs;
-    const float *tf; int RV, RG; int64_t tf_vs; float g_scale;   // [n_views or 1][RV][RG][4], tf_vs in floats
-    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp;
-    int n_views, W, H, S; float sr; int mode;
-    float *out; int32_t *steps;
-    // backward only
-    const float *grad_out; const float *out_fwd;
-    float *d_vol; int64_t dsx, dsy, dsz, dvol_vs;
-    float *d_tf; int64_t dtf_vs;
-};
+// March with a 2-D (value, gradient-magnitude) transfer function (march_tf2d.hip): dr_march_tf2d_fwd / _bwd.
 // weak, as launch_camera_grad: capi.o must load in a library linked without march_tf2d.o
-__attribute__((weak)) int launch_march_tf2d_fwd(const Tf2dArgs &a, hipStream_t stream);
-__attribute__((weak)) int launch_march_tf2d_bwd(const Tf2dArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_march_tf2d_fwd(const MarchArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_march_tf2d_bwd(const MarchArgs &a, hipStream_t stream);
 
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,

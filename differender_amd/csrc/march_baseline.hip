@@ -8,23 +8,12 @@
 //   With T_s = 1 - A_{s-1} and q_s = gC.(L_s rgb_s) + gA the adjoint of the sample opacity is
 //   d/d op_s = T_s q_s - [gC.(C_final - C_s) + gA.(A_final - A_s)] / (1 - op_s)   (C_s, A_s = composite up to s),
 //   which needs only a forward-order walk and the saved forward output (no per-sample tape).
-#include "dr_device.h"
-#include "dr_kernels.h"
 #include "dr_tile.h"
-#include "../../include/differender_hip.h"
 
 namespace dr {
 
 template <typename VT>
-struct MarchParams {
-    VolView<VT> vol; int64_t vol_vs;
-    const float4 *tf; int64_t tf_vs; int R; float tf_len;
-    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp;
-    int W, H, S; float sr, inv_sr;
-    float *out; int32_t *steps;
-    const float *grad_out, *out_fwd;
-    GradView dvol; int64_t dvol_vs;
-    float *d_tf; int64_t dtf_vs;
+struct MarchParams : RayParams<VT> {
     const uint8_t *only_flagged;
     const unsigned int *ws_mark; unsigned int ws_mark_expect;  // see MarchArgs
     const unsigned int *ws_aux; unsigned int ws_aux_expect;
@@ -36,12 +25,7 @@ template <typename VT, int MODE, bool TF_LDS>
 __global__ __launch_bounds__(256) void march_fwd_baseline_kernel(MarchParams<VT> P) {
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     const int view = blockIdx.y;
-    const float4 *tfg = P.tf + view * P.tf_vs;
-    if (TF_LDS) {
-        for (int k = threadIdx.x; k < P.R; k += 256) lds_tf_[k] = tfg[k];
-        __syncthreads();
-    }
-    const float4 *lds_tf = TF_LDS ? lds_tf_ : tfg;
+    const float4 *lds_tf = stage_table<TF_LDS>(lds_tf_, P.tf + view * P.tf_vs, P.R);
 
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
@@ -52,36 +36,25 @@ __global__ __launch_bounds__(256) void march_fwd_baseline_kernel(MarchParams<VT>
     const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
 
     RayGeom rg;
-    rg.n = P.nsamp[p]; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
-    rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
-    rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
     const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
     const int nmarch = (MODE == DR_MODE_DIFF && rg.n > P.S) ? P.S : rg.n;
 
-    float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+    Composite c;
     int cnt = 0;
     for (int s = 0; s < nmarch; ++s) {
-        if (!(A < 0.99f)) break;
+        if (!(c.A < 0.99f)) break;
         Sample sm;
         sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
         classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
         ++cnt;
         if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
         shade(vol, light, vd, MODE == DR_MODE_DIFF, sm);
-        const float T = 1.0f - A;
-        C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
-        C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
-        C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
-        A = fmaf(T, sm.op, A);
+        c.add(sm);
     }
-    if (MODE == DR_MODE_NONDIFF) {
-        C0 = fminf(1.0f, C0); C1 = fminf(1.0f, C1); C2 = fminf(1.0f, C2); A = fminf(1.0f, A);
-    }
-    reinterpret_cast<float4 *>(P.out)[p] = make_float4(C0, C1, C2, A);
+    reinterpret_cast<float4 *>(P.out)[p] = c.pixel(MODE == DR_MODE_NONDIFF);
     if (P.steps) P.steps[p] = cnt;
 }
-
-__device__ __forceinline__ float finite_or_zero(float x) { return (x == x) ? fminf(fmaxf(x, -1.0e30f), 1.0e30f) : 0.0f; }
 
 // TABLES: what the workgroup keeps in LDS --
 //   2: [R] TF + [R][4] d_tf accumulators in double (48 R bytes: R <= 3392);
@@ -96,12 +69,8 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
     // round 4); the oracle sums d_tf in double for the same reason (its d_tf accumulators), so this keeps the twin a twin
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     const int view = blockIdx.y;
-    const float4 *tfg = P.tf + view * P.tf_vs;
     double *lds_dtf = reinterpret_cast<double *>(lds_tf_ + P.R);
-    if (TABLES >= 1) for (int k = threadIdx.x; k < P.R; k += 256) lds_tf_[k] = tfg[k];
-    if (TABLES == 2) for (int k = threadIdx.x; k < 4 * P.R; k += 256) lds_dtf[k] = 0.0;
-    if (TABLES >= 1) __syncthreads();
-    const float4 *lds_tf = TABLES >= 1 ? lds_tf_ : tfg;
+    const float4 *lds_tf = stage_table<TABLES >= 1>(lds_tf_, P.tf + view * P.tf_vs, P.R, lds_dtf, TABLES == 2 ? 4 * P.R : 0);
     float *dtf_g = P.d_tf ? P.d_tf + view * P.dtf_vs * 4 : nullptr;
 
     int i, j;
@@ -125,9 +94,7 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
         const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
 
         RayGeom rg;
-        rg.n = P.nsamp[p]; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
-        rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
-        rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
         const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
         const int nmarch = rg.n > P.S ? P.S : rg.n;
 
@@ -135,23 +102,17 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
         const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
         const float delta = 1e-3f;
 
-        float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+        Composite c;
         for (int s = 0; s < nmarch; ++s) {
-            if (!(A < 0.99f)) break;
+            if (!(c.A < 0.99f)) break;
             Sample sm;
             sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
             classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
             shade(vol, light, vd, true, sm);
-            const float T = 1.0f - A;
-            C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
-            C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
-            C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
-            A = fmaf(T, sm.op, A);
-            const bool last = (s == nmarch - 1) || !(A < 0.99f);
-            // what the samples after s contribute to the loss: gC.(C_final - C_s) + gA.(A_final - A_s)
-            const float suffix = (go.x * (of.x - C0) + go.y * (of.y - C1) + go.z * (of.z - C2)) + go.w * (of.w - A);
+            const float T = c.add(sm);
+            const bool last = (s == nmarch - 1) || !(c.A < 0.99f);
             SampleAdj ad;
-            sample_adjoint(sm, vd, T, suffix, last, go, P.inv_sr, ad);
+            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
             float I_bar = want_vol ? intensity_adjoint(sm, lds_tf[sm.lo], lds_tf[sm.hi], ad, P.tf_len) : 0.0f;
             if (P.only_flagged) {
                 // second pass of the brick-centric backward (irregular rays): that path promises finite gradients, so a NaN
@@ -206,44 +167,24 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
 
 template <typename VT>
 static MarchParams<VT> make_params(const MarchArgs &a) {
-    MarchParams<VT> P;
-    P.vol.p = static_cast<const VT *>(a.vol);
-    P.vol.sx = a.sx; P.vol.sy = a.sy; P.vol.sz = a.sz;
-    P.vol.VX = a.VX; P.vol.VY = a.VY; P.vol.VZ = a.VZ;
-    P.vol.scx = (float)((double)a.VX - 1.0 - 1e-4);
-    P.vol.scy = (float)((double)a.VY - 1.0 - 1e-4);
-    P.vol.scz = (float)((double)a.VZ - 1.0 - 1e-4);
-    P.vol_vs = a.vol_vs;
-    P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4; P.R = a.R; P.tf_len = (float)(a.R - 1);
-    P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp;
-    P.W = a.W; P.H = a.H; P.S = a.S; P.sr = a.sr; P.inv_sr = 1.0f / a.sr;
-    P.out = a.out; P.steps = a.steps;
-    P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
-    P.dvol.p = a.d_vol; P.dvol.sx = a.dsx; P.dvol.sy = a.dsy; P.dvol.sz = a.dsz; P.dvol_vs = a.dvol_vs;
-    P.d_tf = a.d_tf; P.dtf_vs = a.dtf_vs / 4;
+    MarchParams<VT> P{make_ray_params<VT>(a)};
     P.only_flagged = a.only_flagged;
     P.ws_mark = a.ws_mark; P.ws_mark_expect = a.ws_mark_expect;
     P.ws_aux = a.ws_aux; P.ws_aux_expect = a.ws_aux_expect;
     return P;
 }
 
-static dim3 tile_grid(const MarchArgs &a) { return tile_grid(a.W, a.H, a.n_views); }
-
 template <typename VT>
 static int fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     size_t lds = (size_t)a.R * sizeof(float4);
     const bool tf_lds = lds <= LDS_PER_CU;   // (R <= 10176; a larger TF is read from global memory)
     if (!tf_lds) lds = 0;
-    MarchParams<VT> P = make_params<VT>(a);
-#define DR_FWD_BASE(MODE_, LDS_)                                                                                             \
-    {                                                                                                                        \
-        if (big_lds(march_fwd_baseline_kernel<VT, MODE_, LDS_>, lds) != hipSuccess) return DR_EUNSUPPORTED;                  \
-        hipLaunchKernelGGL((march_fwd_baseline_kernel<VT, MODE_, LDS_>), tile_grid(a), dim3(256), lds, stream, P);           \
-    }
-    if (a.mode == DR_MODE_DIFF) { if (tf_lds) DR_FWD_BASE(DR_MODE_DIFF, true) else DR_FWD_BASE(DR_MODE_DIFF, false) }
-    else { if (tf_lds) DR_FWD_BASE(DR_MODE_NONDIFF, true) else DR_FWD_BASE(DR_MODE_NONDIFF, false) }
-#undef DR_FWD_BASE
-    return (int)hipGetLastError();
+    const MarchParams<VT> P = make_params<VT>(a);
+    if (a.mode == DR_MODE_DIFF)
+        return launch_tiles(tf_lds ? march_fwd_baseline_kernel<VT, DR_MODE_DIFF, true> : march_fwd_baseline_kernel<VT, DR_MODE_DIFF, false>,
+                            a, lds, stream, P);
+    return launch_tiles(tf_lds ? march_fwd_baseline_kernel<VT, DR_MODE_NONDIFF, true> : march_fwd_baseline_kernel<VT, DR_MODE_NONDIFF, false>,
+                        a, lds, stream, P);
 }
 
 int launch_march_fwd_baseline(const MarchArgs &a, hipStream_t stream) {
@@ -256,15 +197,9 @@ static int bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     const size_t lds2 = (size_t)a.R * (sizeof(float4) + 4 * sizeof(double)), lds1 = (size_t)a.R * sizeof(float4);
     const int tables = lds2 <= LDS_PER_CU ? 2 : (lds1 <= LDS_PER_CU ? 1 : 0);
     const size_t lds = tables == 2 ? lds2 : (tables == 1 ? lds1 : 0);
-    MarchParams<VT> P = make_params<VT>(a);
-#define DR_BWD_BASE(T_)                                                                                          \
-    {                                                                                                            \
-        if (big_lds(march_bwd_baseline_kernel<VT, T_>, lds) != hipSuccess) return DR_EUNSUPPORTED;               \
-        hipLaunchKernelGGL((march_bwd_baseline_kernel<VT, T_>), tile_grid(a), dim3(256), lds, stream, P);        \
-    }
-    if (tables == 2) DR_BWD_BASE(2) else if (tables == 1) DR_BWD_BASE(1) else DR_BWD_BASE(0)
-#undef DR_BWD_BASE
-    return (int)hipGetLastError();
+    const MarchParams<VT> P = make_params<VT>(a);
+    return launch_tiles(tables == 2 ? march_bwd_baseline_kernel<VT, 2> : (tables == 1 ? march_bwd_baseline_kernel<VT, 1> : march_bwd_baseline_kernel<VT, 0>),
+                        a, lds, stream, P);
 }
 
 int launch_march_bwd_baseline(const MarchArgs &a, hipStream_t stream) {

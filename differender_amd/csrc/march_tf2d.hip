@@ -5,24 +5,14 @@
 //   xv = I (RV - 1), xg = u (RG - 1); low_high_frac and the H4/H5 clamp on each axis;
 //   rgba = mix(mix(T[v0][g0], T[v1][g0], fv), mix(T[v0][g1], T[v1][g1], fv), fg)   (value axis first, dr_device.h's mixf)
 // With RG == 1, fg = 0 and mix(x, x, 0) = x: a (RV, 1) table is bit for bit the 1-D TF of RV entries.
-#include "dr_device.h"
-#include "dr_kernels.h"
 #include "dr_tile.h"
-#include "../../include/differender_hip.h"
 
 namespace dr {
 
+// RayParams is all the 2-D TF reads: the table is [RV][RG] with RV = R, and lv = RV - 1 is tf_len (a type of its own all
+// the same: the kernels' signatures, which profiles name, stay as they were)
 template <typename VT>
-struct Tf2dParams {
-    VolView<VT> vol; int64_t vol_vs;
-    const float4 *tf; int64_t tf_vs; int RV, RG; float lv, lg, g_scale;   // lv = RV - 1, lg = RG - 1 (rounded from int)
-    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp;
-    int W, H, S; float inv_sr;
-    float *out; int32_t *steps;
-    const float *grad_out, *out_fwd;
-    GradView dvol; int64_t dvol_vs;
-    float *d_tf; int64_t dtf_vs;
-};
+struct Tf2dParams : RayParams<VT> {};
 
 // The classification of one sample: indices and fractions on both axes, the four texels and the two value-axis lerps.
 struct Tf2dSample {
@@ -46,9 +36,9 @@ __device__ __forceinline__ float4 mix4(float4 x, float4 y, float a) {
 template <typename VT>
 __device__ __forceinline__ void classify2d(const Tf2dParams<VT> &P, const float4 *tf, Sample &sm, Tf2dSample &t) {
     const float u = sm.gnorm * P.g_scale;
-    t.xv = sm.I * P.lv;
+    t.xv = sm.I * P.tf_len;
     t.xg = u * P.lg;
-    axis_index(t.xv, P.RV, t.v0, t.v1, t.fv);
+    axis_index(t.xv, P.R, t.v0, t.v1, t.fv);
     axis_index(t.xg, P.RG, t.g0, t.g1, t.fg);
     t.a = tf[t.v0 * P.RG + t.g0]; t.b = tf[t.v1 * P.RG + t.g0];
     t.c = tf[t.v0 * P.RG + t.g1]; t.d = tf[t.v1 * P.RG + t.g1];
@@ -71,19 +61,15 @@ template <typename VT, int MODE, bool TF_LDS>
 __global__ __launch_bounds__(256) void march_tf2d_fwd_kernel(Tf2dParams<VT> P) {
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     const int view = blockIdx.y;
-    const int NT = P.RV * P.RG;
-    const float4 *tfg = P.tf + view * P.tf_vs;
+    const int NT = P.R * P.RG;
     float *rowmax = reinterpret_cast<float *>(lds_tf_ + NT);
     constexpr bool SKIP = TF_LDS && MODE == DR_MODE_NONDIFF;
-    if (TF_LDS) {
-        for (int k = threadIdx.x; k < NT; k += 256) lds_tf_[k] = tfg[k];
-        __syncthreads();
-    }
+    const float4 *tf = stage_table<TF_LDS>(lds_tf_, P.tf + view * P.tf_vs, NT);
     if (SKIP) {
         // one wave per row, its lanes across the row's texels, then a butterfly max (the row loop is wave-uniform, so the
         // shuffles run converged): the work is spread alike for tall and for wide tables
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        for (int v = wave; v < P.RV; v += 4) {
+        for (int v = wave; v < P.R; v += 4) {
             float m = -__builtin_inff();
             for (int g = lane; g < P.RG; g += 64) m = fmaxf(m, lds_tf_[v * P.RG + g].w);
 #pragma unroll
@@ -92,7 +78,6 @@ __global__ __launch_bounds__(256) void march_tf2d_fwd_kernel(Tf2dParams<VT> P) {
         }
         __syncthreads();
     }
-    const float4 *tf = TF_LDS ? lds_tf_ : tfg;
 
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
@@ -103,39 +88,30 @@ __global__ __launch_bounds__(256) void march_tf2d_fwd_kernel(Tf2dParams<VT> P) {
     const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
 
     RayGeom rg;
-    rg.n = P.nsamp[p]; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
-    rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
-    rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
     const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
     const int nmarch = (MODE == DR_MODE_DIFF && rg.n > P.S) ? P.S : rg.n;
 
-    float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+    Composite c;
     int cnt = 0;
     for (int s = 0; s < nmarch; ++s) {
-        if (!(A < 0.99f)) break;
+        if (!(c.A < 0.99f)) break;
         Sample sm;
         sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
         sm.I = tri_sample(vol, sm.px, sm.py, sm.pz);
         ++cnt;
         if (SKIP) {
             int v0, v1; float fv;
-            axis_index(sm.I * P.lv, P.RV, v0, v1, fv);
+            axis_index(sm.I * P.tf_len, P.R, v0, v1, fv);
             if (fmaxf(rowmax[v0], rowmax[v1]) <= TF2D_SKIP_BELOW) continue;
         }
         shade(vol, light, vd, MODE == DR_MODE_DIFF, sm);   // the taps: sm.gnorm
         Tf2dSample t;
         classify2d(P, tf, sm, t);
         if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
-        const float T = 1.0f - A;
-        C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
-        C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
-        C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
-        A = fmaf(T, sm.op, A);
+        c.add(sm);
     }
-    if (MODE == DR_MODE_NONDIFF) {
-        C0 = fminf(1.0f, C0); C1 = fminf(1.0f, C1); C2 = fminf(1.0f, C2); A = fminf(1.0f, A);
-    }
-    reinterpret_cast<float4 *>(P.out)[p] = make_float4(C0, C1, C2, A);
+    reinterpret_cast<float4 *>(P.out)[p] = c.pixel(MODE == DR_MODE_NONDIFF);
     if (P.steps) P.steps[p] = cnt;
 }
 
@@ -172,13 +148,9 @@ template <typename VT, int TABLES>
 __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     const int view = blockIdx.y;
-    const int NT = P.RV * P.RG;
-    const float4 *tfg = P.tf + view * P.tf_vs;
+    const int NT = P.R * P.RG;
     double *lds_dtf = reinterpret_cast<double *>(lds_tf_ + NT);
-    if (TABLES >= 1) for (int k = threadIdx.x; k < NT; k += 256) lds_tf_[k] = tfg[k];
-    if (TABLES == 2) for (int k = threadIdx.x; k < 4 * NT; k += 256) lds_dtf[k] = 0.0;
-    if (TABLES >= 1) __syncthreads();
-    const float4 *tf = TABLES >= 1 ? lds_tf_ : tfg;
+    const float4 *tf = stage_table<TABLES >= 1>(lds_tf_, P.tf + view * P.tf_vs, NT, lds_dtf, TABLES == 2 ? 4 * NT : 0);
     float *dtf_g = P.d_tf ? P.d_tf + view * P.dtf_vs * 4 : nullptr;
 
     int i, j;
@@ -194,9 +166,7 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
         const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
 
         RayGeom rg;
-        rg.n = P.nsamp[p]; rg.entry = P.entry[p]; rg.exit_ = P.exit_[p];
-        rg.vx = P.rays[3 * p]; rg.vy = P.rays[3 * p + 1]; rg.vz = P.rays[3 * p + 2];
-        rg.t0 = rg.entry + 0.5f * (rg.exit_ - rg.entry) / (float)rg.n;
+        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
         const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
         const int nmarch = rg.n > P.S ? P.S : rg.n;
 
@@ -204,25 +174,20 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
         const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
         const float delta = 1e-3f;
 
-        float C0 = 0.f, C1 = 0.f, C2 = 0.f, A = 0.f;
+        Composite c;
         CellRun run;
         for (int s = 0; s < nmarch; ++s) {
-            if (!(A < 0.99f)) break;
+            if (!(c.A < 0.99f)) break;
             Sample sm;
             sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
             sm.I = tri_sample(vol, sm.px, sm.py, sm.pz);
             shade(vol, light, vd, true, sm);
             Tf2dSample t;
             classify2d(P, tf, sm, t);
-            const float T = 1.0f - A;
-            C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
-            C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
-            C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
-            A = fmaf(T, sm.op, A);
-            const bool last = (s == nmarch - 1) || !(A < 0.99f);
-            const float suffix = (go.x * (of.x - C0) + go.y * (of.y - C1) + go.z * (of.z - C2)) + go.w * (of.w - A);
+            const float T = c.add(sm);
+            const bool last = (s == nmarch - 1) || !(c.A < 0.99f);
             SampleAdj ad;
-            sample_adjoint(sm, vd, T, suffix, last, go, P.inv_sr, ad);
+            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
 
             if (want_tf) {
                 // d rgba / d T[.][.]: the four bilinear weights
@@ -253,7 +218,7 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
             if (want_vol) {
                 // through I: the value-axis slope (1 - fg)(b - a) + fg (d - c), times RV - 1, iff 0 < xv
                 const float fv_bar = (1.0f - t.fg) * dot4(sub4(t.b, t.a), ad) + t.fg * dot4(sub4(t.d, t.c), ad);
-                const float I_bar = (0.0f < t.xv) ? fv_bar * P.lv : 0.0f;
+                const float I_bar = (0.0f < t.xv) ? fv_bar * P.tf_len : 0.0f;
                 tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz, I_bar);
                 if (!sm.flat) {
                     // through u = |grad| g_scale: the gradient-axis slope hi - lo, times (RG - 1) g_scale, iff 0 < xg, onto the
@@ -283,70 +248,37 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
 }
 
 template <typename VT>
-static Tf2dParams<VT> make_tf2d_params(const Tf2dArgs &a) {
-    Tf2dParams<VT> P;
-    P.vol.p = static_cast<const VT *>(a.vol);
-    P.vol.sx = a.sx; P.vol.sy = a.sy; P.vol.sz = a.sz;
-    P.vol.VX = a.VX; P.vol.VY = a.VY; P.vol.VZ = a.VZ;
-    P.vol.scx = (float)((double)a.VX - 1.0 - 1e-4);
-    P.vol.scy = (float)((double)a.VY - 1.0 - 1e-4);
-    P.vol.scz = (float)((double)a.VZ - 1.0 - 1e-4);
-    P.vol_vs = a.vol_vs;
-    P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4;
-    P.RV = a.RV; P.RG = a.RG; P.lv = (float)(a.RV - 1); P.lg = (float)(a.RG - 1); P.g_scale = a.g_scale;
-    P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp;
-    P.W = a.W; P.H = a.H; P.S = a.S; P.inv_sr = 1.0f / a.sr;
-    P.out = a.out; P.steps = a.steps;
-    P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
-    P.dvol.p = a.d_vol; P.dvol.sx = a.dsx; P.dvol.sy = a.dsy; P.dvol.sz = a.dsz; P.dvol_vs = a.dvol_vs;
-    P.d_tf = a.d_tf; P.dtf_vs = a.dtf_vs / 4;
-    return P;
-}
-
-template <typename VT>
-static int tf2d_fwd_dispatch(const Tf2dArgs &a, hipStream_t stream) {
-    const size_t NT = (size_t)a.RV * a.RG;
-    size_t lds = NT * sizeof(float4) + (a.mode == DR_MODE_NONDIFF ? (size_t)a.RV * sizeof(float) : 0);
+static int tf2d_fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
+    const size_t NT = (size_t)a.R * a.RG;
+    size_t lds = NT * sizeof(float4) + (a.mode == DR_MODE_NONDIFF ? (size_t)a.R * sizeof(float) : 0);
     const bool tf_lds = lds <= LDS_PER_CU;
     if (!tf_lds) lds = 0;
-    const Tf2dParams<VT> P = make_tf2d_params<VT>(a);
-    const dim3 grid = tile_grid(a.W, a.H, a.n_views);
-#define DR_TF2D_FWD(MODE_, LDS_)                                                                                  \
-    {                                                                                                             \
-        if (big_lds(march_tf2d_fwd_kernel<VT, MODE_, LDS_>, lds) != hipSuccess) return DR_EUNSUPPORTED;           \
-        hipLaunchKernelGGL((march_tf2d_fwd_kernel<VT, MODE_, LDS_>), grid, dim3(256), lds, stream, P);            \
-    }
-    if (a.mode == DR_MODE_DIFF) { if (tf_lds) DR_TF2D_FWD(DR_MODE_DIFF, true) else DR_TF2D_FWD(DR_MODE_DIFF, false) }
-    else { if (tf_lds) DR_TF2D_FWD(DR_MODE_NONDIFF, true) else DR_TF2D_FWD(DR_MODE_NONDIFF, false) }
-#undef DR_TF2D_FWD
-    return (int)hipGetLastError();
+    const Tf2dParams<VT> P{make_ray_params<VT>(a)};
+    if (a.mode == DR_MODE_DIFF)
+        return launch_tiles(tf_lds ? march_tf2d_fwd_kernel<VT, DR_MODE_DIFF, true> : march_tf2d_fwd_kernel<VT, DR_MODE_DIFF, false>,
+                            a, lds, stream, P);
+    return launch_tiles(tf_lds ? march_tf2d_fwd_kernel<VT, DR_MODE_NONDIFF, true> : march_tf2d_fwd_kernel<VT, DR_MODE_NONDIFF, false>,
+                        a, lds, stream, P);
 }
 
 template <typename VT>
-static int tf2d_bwd_dispatch(const Tf2dArgs &a, hipStream_t stream) {
-    const size_t NT = (size_t)a.RV * a.RG;
+static int tf2d_bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
+    const size_t NT = (size_t)a.R * a.RG;
     // (a backward without d_tf2d keeps no gradient table: at 64 x 32 texels the f64 table alone would limit a CU to one
     // workgroup)
     const size_t lds2 = NT * (sizeof(float4) + 4 * sizeof(double)), lds1 = NT * sizeof(float4);
     const int tables = (a.d_tf && lds2 <= LDS_PER_CU) ? 2 : (lds1 <= LDS_PER_CU ? 1 : 0);
     const size_t lds = tables == 2 ? lds2 : (tables == 1 ? lds1 : 0);
-    const Tf2dParams<VT> P = make_tf2d_params<VT>(a);
-    const dim3 grid = tile_grid(a.W, a.H, a.n_views);
-#define DR_TF2D_BWD(T_)                                                                                           \
-    {                                                                                                             \
-        if (big_lds(march_tf2d_bwd_kernel<VT, T_>, lds) != hipSuccess) return DR_EUNSUPPORTED;                    \
-        hipLaunchKernelGGL((march_tf2d_bwd_kernel<VT, T_>), grid, dim3(256), lds, stream, P);                     \
-    }
-    if (tables == 2) DR_TF2D_BWD(2) else if (tables == 1) DR_TF2D_BWD(1) else DR_TF2D_BWD(0)
-#undef DR_TF2D_BWD
-    return (int)hipGetLastError();
+    const Tf2dParams<VT> P{make_ray_params<VT>(a)};
+    return launch_tiles(tables == 2 ? march_tf2d_bwd_kernel<VT, 2> : (tables == 1 ? march_tf2d_bwd_kernel<VT, 1> : march_tf2d_bwd_kernel<VT, 0>),
+                        a, lds, stream, P);
 }
 
-int launch_march_tf2d_fwd(const Tf2dArgs &a, hipStream_t stream) {
+int launch_march_tf2d_fwd(const MarchArgs &a, hipStream_t stream) {
     return a.vol_dtype == DR_F16 ? tf2d_fwd_dispatch<__half>(a, stream) : tf2d_fwd_dispatch<float>(a, stream);
 }
 
-int launch_march_tf2d_bwd(const Tf2dArgs &a, hipStream_t stream) {
+int launch_march_tf2d_bwd(const MarchArgs &a, hipStream_t stream) {
     return a.vol_dtype == DR_F16 ? tf2d_bwd_dispatch<__half>(a, stream) : tf2d_bwd_dispatch<float>(a, stream);
 }
 

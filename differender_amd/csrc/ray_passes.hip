@@ -139,23 +139,20 @@ __global__ __launch_bounds__(256) void ray_compose_kernel(BrickParams<VT> P) {
         if (!regular) {
             // single-sample rays (and repaired ones): the sequential march of the baseline kernels
             flag = 1;
-            C0 = C1 = C2 = A = 0.f;
             steps = 0;
             atomicAdd(&P.stats[ST_BASELINE_RAYS], 1u);
+            Composite c;
             for (int s = 0; s < nmarch; ++s) {
-                if (!(A < 0.99f)) break;
+                if (!(c.A < 0.99f)) break;
                 Sample sm;
                 sample_pos(rg, cam.x, cam.y, cam.z, s, sm.px, sm.py, sm.pz);
                 classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
                 ++steps;
                 if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
                 shade(vol, light, vd, MODE == DR_MODE_DIFF, sm);
-                const float T = 1.0f - A;
-                C0 = fmaf(T, sm.L * sm.r * sm.op, C0);
-                C1 = fmaf(T, sm.L * sm.g * sm.op, C1);
-                C2 = fmaf(T, sm.L * sm.b * sm.op, C2);
-                A = fmaf(T, sm.op, A);
+                c.add(sm);
             }
+            C0 = c.C0; C1 = c.C1; C2 = c.C2; A = c.A;
         }
     }
     if (MODE == DR_MODE_NONDIFF) {

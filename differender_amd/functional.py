@@ -358,6 +358,17 @@ def march_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, m
     return out, steps
 
 
+def _d_vol(vol, want):
+    """The backward's d_volume (zeros, float32, vol's layout) and its C-ABI arguments (pointer, x/y/z strides, view stride);
+    (None, (None, 0, 0, 0, 0)) when not wanted."""
+    if not want:
+        return None, (None, 0, 0, 0, 0)
+    d_vol = torch.zeros_like(vol, dtype=torch.float32, memory_format=torch.preserve_format)
+    if vol.ndim == 3:
+        return d_vol, (d_vol.data_ptr(), *d_vol.stride(), 0)
+    return d_vol, (d_vol.data_ptr(), *d_vol.stride()[1:], d_vol.stride(0))
+
+
 def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, grad_out, out, want_vol=True,
               want_tf=True, variant=N.DR_VARIANT_AUTO, fov_deg=30.0, near=0.1, workspace=None, rows=None, count_evaluated=False,
               tape=False):
@@ -375,14 +386,8 @@ def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, g
     out = out.contiguous()
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
-    d_vol = d_tf = None
-    dv = (None, 0, 0, 0, 0)
-    if want_vol:
-        d_vol = torch.zeros_like(vol, dtype=torch.float32, memory_format=torch.preserve_format)
-        if vol.ndim == 3:
-            dv = (d_vol.data_ptr(), *d_vol.stride(), 0)
-        else:
-            dv = (d_vol.data_ptr(), *d_vol.stride()[1:], d_vol.stride(0))
+    d_vol, dv = _d_vol(vol, want_vol)
+    d_tf = None
     dt = (None, 0)
     if want_tf:
         d_tf = torch.zeros_like(tf)
@@ -482,11 +487,8 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
     g = _g_scale(g_scale)
     if not (want_vol or want_tf):
         return None, None
-    d_vol = d_tf = None
-    dv = (None, 0, 0, 0, 0)
-    if want_vol:
-        d_vol = torch.zeros_like(vol, dtype=torch.float32, memory_format=torch.preserve_format)
-        dv = (d_vol.data_ptr(), *d_vol.stride(), 0) if vol.ndim == 3 else (d_vol.data_ptr(), *d_vol.stride()[1:], d_vol.stride(0))
+    d_vol, dv = _d_vol(vol, want_vol)
+    d_tf = None
     dt = (None, 0)
     if want_tf:
         d_tf = torch.zeros_like(tf2d)

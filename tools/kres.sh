@@ -19,5 +19,5 @@ for line in sys.stdin:
         import subprocess
         name = subprocess.run(['c++filt', cur['name']], capture_output=True, text=True).stdout.strip()
         name = re.sub(r'\(dr::BrickParams.*', '', name).replace('void dr::', '')
-        print('%-78s vgpr %3s sgpr %3s scratch %3s occ %s' % (name[:78], cur.get('VGPRs'), cur.get('SGPRs'), cur.get('ScratchSize [bytes/lane]'), cur.get('Occupancy [waves/SIMD]')))
+        print('%-78s vgpr %3s sgpr %3s scratch %3s occ %s' % (name[:78], cur.get('VGPRs'), cur.get('TotalSGPRs'), cur.get('ScratchSize [bytes/lane]'), cur.get('Occupancy [waves/SIMD]')))
 "
