@@ -21,6 +21,7 @@ DR_TAPE_TF = 0x800           # forward (DIFF) + the TF-only backward of the same
 DR_SSIM_NONNEGATIVE = 1      # flags of dr_dssim_mse_fwd / _bwd: relu on the per-plane SSIM
 DR_MSSSIM_MAX_LEVELS = 5     # levels of dr_msssim_mse_fwd / _bwd
 DR_TV_L1, DR_TV_ISO, DR_TV_SQ = 0, 1, 2   # norm of dr_tv3d_fwd / _bwd
+DR_PROJ_SUM, DR_PROJ_MAX = 0, 1           # mode of dr_project_fwd / _bwd / _bwd_cam
 
 _c = ctypes
 _P, _I, _L, _F, _D, _U, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_double, _c.c_uint32, _c.c_size_t
@@ -64,6 +65,11 @@ SIGNATURES = {
                                _I, _I, _I, _I, _F, _I, _P, _P, _P]),
     "dr_march_tf2d_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _I, _L, _F, _P, _P, _P, _P, _P,
                                _I, _I, _I, _I, _F, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P]),
+    "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
+                            _P, _L, _L, _L, _L, _I, _P]),
+    "dr_project_bwd_cam": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _U, _U,
+                                _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -459,6 +459,88 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     return launch_march_tf2d_bwd(a, (hipStream_t)stream);
 }
 
+// what the three projection entries check: fill_common's volume and ray checks without a table, max_samples >= 1, the mode,
+// and arg_max for DR_PROJ_MAX
+static int fill_proj(MarchArgs &a, ProjArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
+                     int64_t sz, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,
+                     const float *rays, const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
+                     const int32_t *arg_max) {
+    if (!vol || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
+    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
+    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
+    if (max_samples < 1) return DR_EINVAL;
+    if (mode != DR_PROJ_SUM && mode != DR_PROJ_MAX) return DR_EINVAL;
+    if (mode == DR_PROJ_MAX && !arg_max) return DR_EINVAL;
+    a = MarchArgs{};
+    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
+    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
+    a.R = 1; a.RG = 1; a.sr = 1.0f;
+    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
+    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.img_W = W;
+    q = ProjArgs{};
+    q.mode = mode; q.variant = DR_VARIANT_AUTO; q.arg_max = const_cast<int32_t *>(arg_max);
+    return 0;
+}
+
+int dr_project_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                   int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                   const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, float *out, int32_t *arg_max,
+                   void *stream) {
+    MarchArgs a;
+    ProjArgs q;
+    int rc = fill_proj(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                       W, H, max_samples, mode, arg_max);
+    if (rc) return rc;
+    if (!out) return DR_EINVAL;
+    a.out = out;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_project_fwd) return DR_EUNSUPPORTED;   // (a library linked without projection.o)
+    return launch_project_fwd(a, q, (hipStream_t)stream);
+}
+
+int dr_project_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                   int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                   const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, const float *grad_out,
+                   const int32_t *arg_max, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                   int variant, void *stream) {
+    MarchArgs a;
+    ProjArgs q;
+    int rc = fill_proj(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                       W, H, max_samples, mode, arg_max);
+    if (rc) return rc;
+    if (!grad_out) return DR_EINVAL;
+    if (variant != DR_VARIANT_AUTO && variant != DR_VARIANT_BASELINE) return DR_EINVAL;
+    if (!d_vol) return 0;  // nothing requested
+    a.grad_out = grad_out; a.mode = DR_MODE_DIFF;
+    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
+    q.variant = variant;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_project_bwd) return DR_EUNSUPPORTED;
+    return launch_project_bwd(a, q, (hipStream_t)stream);
+}
+
+int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                       int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, double fov_rad,
+                       double near_plane, uint32_t jitter_seed, uint32_t view_base, const float *grad_out,
+                       const int32_t *arg_max, double *d_cam, float *d_cam_ray, void *stream) {
+    MarchArgs a;
+    ProjArgs q;
+    int rc = fill_proj(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                       W, H, max_samples, mode, arg_max);
+    if (rc) return rc;
+    if (!grad_out || !d_cam) return DR_EINVAL;
+    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
+    a.grad_out = grad_out; a.mode = DR_MODE_DIFF; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    q.jitter_seed = jitter_seed; q.view_base = view_base; q.d_cam = d_cam; q.d_cam_ray = d_cam_ray;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_project_bwd_cam) return DR_EUNSUPPORTED;
+    return launch_project_bwd_cam(a, q, (hipStream_t)stream);
+}
+
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,
                         void *stream) {
     if (!tf || !d_tf || !momentum || n <= 0 || !(max_grad >= 0.0f)) return DR_EINVAL;

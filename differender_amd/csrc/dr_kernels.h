@@ -151,6 +151,21 @@ __attribute__((weak)) int launch_tv3d_bwd(const TVArgs &a, hipStream_t stream);
 __attribute__((weak)) int launch_march_tf2d_fwd(const MarchArgs &a, hipStream_t stream);
 __attribute__((weak)) int launch_march_tf2d_bwd(const MarchArgs &a, hipStream_t stream);
 
+// X-ray line-integral and maximum-intensity projections (projection.hip): the arguments of dr_project_fwd /
+// _bwd / _bwd_cam beside their MarchArgs (volume, ray buffers, extents, max_samples S; the camera's fov_rad / near_plane; the
+// backward's d_vol and grad_out, a [view][W][H] f32 image)
+struct ProjArgs {
+    int mode, variant;                 // DR_PROJ_*; DR_VARIANT_AUTO (windowed SUM backward) or DR_VARIANT_BASELINE
+    int32_t *arg_max;                  // MAX: [view][W][H], written by the forward, read by the backwards
+    uint32_t jitter_seed, view_base;   // camera backward
+    double *d_cam;                     // [n_views][3], accumulated
+    float *d_cam_ray;                  // [n_views][W][H][3] per-ray contributions, nullable
+};
+// weak, as launch_camera_grad: capi.o must load in a library linked without projection.o
+__attribute__((weak)) int launch_project_fwd(const MarchArgs &a, const ProjArgs &q, hipStream_t stream);
+__attribute__((weak)) int launch_project_bwd(const MarchArgs &a, const ProjArgs &q, hipStream_t stream);
+__attribute__((weak)) int launch_project_bwd_cam(const MarchArgs &a, const ProjArgs &q, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -14,7 +14,8 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "march_tf2d_fwd", "march_tf2d_bwd", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
+__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "march_tf2d_fwd", "march_tf2d_bwd", "project_fwd", "project_bwd",
+           "project_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 
@@ -499,6 +500,92 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
                                        out.data_ptr(), *dv, *dt, _stream())
     N.check(rc, "dr_march_tf2d_bwd")
     return d_vol, d_tf
+
+
+_PROJ_MODES = {"sum": N.DR_PROJ_SUM, "max": N.DR_PROJ_MAX}
+NO_SAMPLE_LIMIT = 2 ** 31 - 1   # a max_samples no ray reaches
+
+
+def _proj_mode(mode):
+    if mode in _PROJ_MODES:
+        return _PROJ_MODES[mode]
+    if mode in _PROJ_MODES.values():
+        return int(mode)
+    raise ValueError(f"projection mode must be 'sum' or 'max', got {mode!r}")
+
+
+def _max_samples(max_samples):
+    return NO_SAMPLE_LIMIT if max_samples is None else int(max_samples)
+
+
+def project_fwd(vol, cam, entry, exit_, rays, n, max_samples=None, mode="sum"):
+    """X-ray line integral (mode "sum": D * sum of the trilinear samples, D = (exit - entry) / n) or maximum intensity projection
+    ("max") of vol along the rays of ray_setup (dr_project_fwd). Returns out (views, W, H) float32 and, for "max",
+    arg_max (views, W, H) int32, the index of the first maximal sample (-1: none) -- None for "sum". max_samples None: no limit."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    dev = vol.device
+    md = _proj_mode(mode)
+    cam = cam.to(torch.float32).contiguous()
+    out = torch.empty((V, W, H), dtype=torch.float32, device=dev)
+    arg = torch.empty((V, W, H), dtype=torch.int32, device=dev) if md == N.DR_PROJ_MAX else None
+    vargs = _vol_args(vol, V)
+    with torch.cuda.device(dev):
+        rc = N.lib().dr_project_fwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
+                                    V, W, H, _max_samples(max_samples), md, out.data_ptr(),
+                                    arg.data_ptr() if arg is not None else None, _stream())
+    N.check(rc, "dr_project_fwd")
+    return out, arg
+
+
+def project_bwd(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None, mode="sum", arg_max=None,
+                variant=N.DR_VARIANT_AUTO):
+    """d_vol of sum(project_fwd(...) * grad_out) (dr_project_bwd): a back-projection. A shared (un-batched) vol receives one
+    gradient summed over the views. variant DR_VARIANT_AUTO: the windowed "sum" kernel; DR_VARIANT_BASELINE: per-tap global
+    atomics. "max" needs the forward's arg_max."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    md = _proj_mode(mode)
+    cam = cam.to(torch.float32).contiguous()
+    grad_out = grad_out.to(torch.float32).contiguous()
+    if md == N.DR_PROJ_MAX and arg_max is None:
+        raise ValueError("mode 'max' needs the forward's arg_max")
+    arg = arg_max.to(torch.int32).contiguous() if arg_max is not None else None
+    vargs = _vol_args(vol, V)
+    d_vol, dv = _d_vol(vol, True)
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_project_bwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
+                                    V, W, H, _max_samples(max_samples), md, grad_out.data_ptr(),
+                                    arg.data_ptr() if arg is not None else None, *dv, int(variant), _stream())
+    N.check(rc, "dr_project_bwd")
+    return d_vol
+
+
+def project_bwd_cam(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None, mode="sum", arg_max=None, fov_deg=30.0,
+                    near=0.1, jitter_seed=0, view_base=0, per_ray=False):
+    """d look_from of sum(project_fwd(...) * grad_out) (dr_project_bwd_cam): cam (views, 3), the ray buffers, jitter_seed and
+    view_base those of the forward's ray_setup. Returns d_cam (views, 3) float32 -- and, with per_ray=True, each ray's
+    contribution (views, W, H, 3) as well."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    md = _proj_mode(mode)
+    cam = cam.to(torch.float32).contiguous()
+    grad_out = grad_out.to(torch.float32).contiguous()
+    if md == N.DR_PROJ_MAX and arg_max is None:
+        raise ValueError("mode 'max' needs the forward's arg_max")
+    arg = arg_max.to(torch.int32).contiguous() if arg_max is not None else None
+    vargs = _vol_args(vol, V)
+    d_cam = torch.zeros((V, 3), dtype=torch.float64, device=vol.device)
+    d_ray = torch.empty((V, W, H, 3), dtype=torch.float32, device=vol.device) if per_ray else None
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_project_bwd_cam(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(),
+                                        n.data_ptr(), V, W, H, _max_samples(max_samples), md, float(np.radians(fov_deg)),
+                                        float(near), int(jitter_seed) & 0xFFFFFFFF, int(view_base), grad_out.data_ptr(),
+                                        arg.data_ptr() if arg is not None else None, d_cam.data_ptr(),
+                                        d_ray.data_ptr() if per_ray else None, _stream())
+    N.check(rc, "dr_project_bwd_cam")
+    d_cam = torch.nan_to_num(d_cam.float())
+    return (d_cam, d_ray) if per_ray else d_cam
 
 
 def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):

@@ -361,6 +361,48 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                       float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
                       float *d_tf2d, int64_t dtf_view_stride, void *stream);
 
+/* X-ray line-integral and maximum-intensity projections: the two standard projections of a scalar volume beside
+ * compositing, differentiable w.r.t. the volume and the camera position. The samples are exactly those of the march, from the
+ * ray buffers of dr_ray_setup (jitter included): s < m = min(n, max_samples), pos_s = look_from + mix(t0, exit, s/(n-1)) vd,
+ * t0 = entry + 0.5 (exit - entry)/n, mu(pos) the trilinear value (f32 arithmetic also for DR_F16 volumes). A ray with n <= 1
+ * gives 0.
+ *   DR_PROJ_SUM  out = D sum_{s<m} mu(pos_s), D = (exit - entry)/n in world units of the [-1, 1]^3 box: the line integral (a
+ *                constant volume c gives c (exit - entry) for 2 <= n <= max_samples). Sequential f32 sum, times D once.
+ *   DR_PROJ_MAX  out = max_{s<m} mu(pos_s); the first maximum wins (strict >), its index goes to arg_max (-1: none; out 0).
+ *   vol       as for dr_march_fwd;  out [n_views][W][H] f32;  arg_max [n_views][W][H] int32 (required for MAX, nullable for SUM)
+ * The backwards are the reverse-mode derivatives with n, the jitter draw, the slab faces, the trilinear cells and the MAX index
+ * frozen. dr_project_bwd ACCUMULATES d_vol (caller zeroes; element strides, dvol_view_stride 0 = one summed gradient for a shared
+ * volume): g D w_tap for every SUM sample, g w_tap for the MAX sample. variant DR_VARIANT_AUTO = the windowed SUM backward (a
+ * pixel tile's taps of one depth window summed in LDS, then added to d_vol row by row), DR_VARIANT_BASELINE = one lane per ray,
+ * global atomics per tap (MAX always). The two differ only in the order of the float additions. d_vol NULL: nothing is
+ * requested, 0 is returned before any HIP call.
+ * dr_project_bwd_cam ACCUMULATES d look_from into d_cam [n_views][3] (f64) -- the D8 chain of dr_march_bwd_cam without lighting,
+ * and for SUM also through D -- and writes each ray's contribution to d_cam_ray [n_views][W][H][3] (nullable). fov_rad,
+ * near_plane, jitter_seed and view_base must be those of the dr_ray_setup call that made the buffers.
+ * A NaN upstream gradient contributes nothing and infinities are clamped to +-1e30 (D5). Bands of image rows (img_W, row0) are
+ * not supported: the buffers are whole images.
+ * Invalid arguments (null required pointers, extents <= 0, max_samples < 1, an unknown mode, variant or dtype, MAX without
+ * arg_max) return DR_EINVAL before any HIP call. */
+enum { DR_PROJ_SUM = 0, DR_PROJ_MAX = 1 };
+int dr_project_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                   int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                   const float *cam, const float *entry, const float *exit_, const float *rays,
+                   const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
+                   float *out, int32_t *arg_max, void *stream);
+int dr_project_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                   int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                   const float *cam, const float *entry, const float *exit_, const float *rays,
+                   const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
+                   const float *grad_out, const int32_t *arg_max,
+                   float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                   int variant, void *stream);
+int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                       int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                       const float *cam, const float *entry, const float *exit_, const float *rays,
+                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
+                       double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                       const float *grad_out, const int32_t *arg_max, double *d_cam, float *d_cam_ray, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
