@@ -267,18 +267,26 @@ int dr_mse_loss_grad(const float *out_rgba, const float *reference, int64_t n, f
     return (int)launch_mse_loss_grad(out_rgba, reference, n, inv_norm, grad_out, loss, (hipStream_t)stream);
 }
 
-static int fill_loss(LossArgs &a, const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
-                     double data_range, int win_size, double win_sigma, double K1, double K2, int flags, double *stats) {
+// what the four image-loss entries check and copy alike
+static int fill_image(ImageArgs &a, const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                      double data_range, int win_size, double win_sigma, double K1, double K2, double *stats) {
     if (!x || !y || !strides4 || !stats) return DR_EINVAL;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return DR_EINVAL;
     if (win_size < 1 || win_size > 31 || win_size % 2 == 0) return DR_EINVAL;
     if (!std::isfinite(data_range) || !(data_range > 0.0) || !std::isfinite(win_sigma) || !(win_sigma > 0.0)) return DR_EINVAL;
-    if (!std::isfinite(K1) || !std::isfinite(K2) || (flags & ~DR_SSIM_NONNEGATIVE)) return DR_EINVAL;
+    if (!std::isfinite(K1) || !std::isfinite(K2)) return DR_EINVAL;
     a.x = x; a.y = y; a.N = N; a.C = C; a.H = H; a.W = W;
     for (int i = 0; i < 4; ++i) a.strides[i] = strides4[i];
-    a.data_range = data_range; a.win_sigma = win_sigma; a.K1 = K1; a.K2 = K2; a.win_size = win_size; a.flags = flags;
+    a.data_range = data_range; a.win_sigma = win_sigma; a.K1 = K1; a.K2 = K2; a.win_size = win_size;
     a.stats = stats; a.upstream = nullptr; a.grad_x = a.grad_y = nullptr;
     return 0;
+}
+
+static int fill_loss(LossArgs &a, const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
+                     double data_range, int win_size, double win_sigma, double K1, double K2, int flags, double *stats) {
+    if (flags & ~DR_SSIM_NONNEGATIVE) return DR_EINVAL;
+    a.flags = flags;
+    return fill_image(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, stats);
 }
 
 int dr_dssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
@@ -321,20 +329,16 @@ size_t dr_msssim_workspace_bytes(int N, int C, int H, int W, int levels, int wan
 static int fill_msssim(MSArgs &a, const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4,
                        double data_range, int win_size, double win_sigma, double K1, double K2, const double *weights,
                        int levels, void *workspace, double *stats) {
-    if (!x || !y || !strides4 || !stats || !weights) return DR_EINVAL;
-    if (!msssim_shape_ok(N, C, H, W, levels)) return DR_EINVAL;
-    if (win_size < 1 || win_size > 31 || win_size % 2 == 0) return DR_EINVAL;
+    const int rc = fill_image(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, stats);
+    if (rc) return rc;
+    if (!weights || !msssim_shape_ok(N, C, H, W, levels)) return DR_EINVAL;
     if (std::min(H, W) <= (win_size - 1) * 16) return DR_EINVAL;   // the window fits every level of a 5-level pyramid
-    if (!std::isfinite(data_range) || !(data_range > 0.0) || !std::isfinite(win_sigma) || !(win_sigma > 0.0)) return DR_EINVAL;
-    if (!std::isfinite(K1) || !std::isfinite(K2)) return DR_EINVAL;
     for (int l = 0; l < levels; ++l)
         if (!std::isfinite(weights[l]) || !(weights[l] > 0.0)) return DR_EINVAL;
     if (!workspace && levels > 1) return DR_EINVAL;
-    a.x = x; a.y = y; a.N = N; a.C = C; a.H = H; a.W = W;
-    for (int i = 0; i < 4; ++i) a.strides[i] = strides4[i];
-    a.data_range = data_range; a.win_sigma = win_sigma; a.K1 = K1; a.K2 = K2; a.win_size = win_size; a.levels = levels;
+    a.levels = levels;
     for (int l = 0; l < levels; ++l) a.weights[l] = weights[l];
-    a.workspace = workspace; a.stats = stats; a.upstream = nullptr; a.grad_x = a.grad_y = nullptr;
+    a.workspace = workspace;
     return 0;
 }
 

@@ -71,16 +71,20 @@ struct CamArgs {
 // weak: the C entry (capi.o) must load in a library linked from the other objects alone (tests/test_abi.py's what-if build)
 __attribute__((weak)) int launch_camera_grad(const MarchArgs &a, const CamArgs &c, hipStream_t stream);
 
-// DSSIM + MSE image loss (image_loss.hip): the arguments of dr_dssim_mse_fwd / dr_dssim_mse_bwd
-struct LossArgs {
+// The image losses: what dr_dssim_mse_fwd / _bwd and dr_msssim_mse_fwd / _bwd both take (checked and copied once, capi.hip)
+struct ImageArgs {
     const float *x, *y;
     int N, C, H, W;
     int64_t strides[4];        // element strides of the logical NCHW, shared by x, y and the gradients
     double data_range, win_sigma, K1, K2;
-    int win_size, flags;       // flags: DR_SSIM_NONNEGATIVE
-    double *stats;             // [N*C] S_nc, then loss, dssim, mse (the forward writes, the backward reads)
-    const float *upstream;     // backward: (d loss, d dssim, d mse) on the device, nullable = (1, 0, 0)
+    int win_size;
+    double *stats;             // the forward writes, the backward reads
+    const float *upstream;     // backward: (d loss, d dssim or d dms, d mse) on the device, nullable = (1, 0, 0)
     float *grad_x, *grad_y;    // backward; grad_y nullable
+};
+// DSSIM + MSE image loss (image_loss.hip); stats: [N*C] S_nc, then loss, dssim, mse
+struct LossArgs : ImageArgs {
+    int flags;                 // DR_SSIM_NONNEGATIVE
 };
 // weak, as launch_camera_grad: capi.o must load in a library linked without image_loss.o
 __attribute__((weak)) int launch_dssim_mse_fwd(const LossArgs &a, hipStream_t stream);
@@ -88,17 +92,10 @@ __attribute__((weak)) int launch_dssim_mse_bwd(const LossArgs &a, hipStream_t st
 
 // MS-SSIM + MSE image loss (msssim.hip): the arguments of dr_msssim_mse_fwd / dr_msssim_mse_bwd
 constexpr int MS_MAX_LEVELS = 5;   // DR_MSSSIM_MAX_LEVELS of the public header (checked in capi.hip)
-struct MSArgs {
-    const float *x, *y;
-    int N, C, H, W;
-    int64_t strides[4];        // element strides of the logical NCHW, shared by x, y and the gradients
-    double data_range, win_sigma, K1, K2;
+struct MSArgs : ImageArgs {   // stats: v[levels][N*C], ms[N*C], loss, dms, mse
     double weights[MS_MAX_LEVELS];
-    int win_size, levels;
+    int levels;
     void *workspace;           // msssim_layout(...).bytes
-    double *stats;             // v[levels][N*C], ms[N*C], loss, dms, mse (the forward writes, the backward reads)
-    const float *upstream;     // backward: (d loss, d dms, d mse) on the device, nullable = (1, 0, 0)
-    float *grad_x, *grad_y;    // backward; grad_y nullable
 };
 // The workspace: levels 1..L-1 of X and Y (pyramid), and for the backward dX_l (and dY_l), each a dense [N*C][H_l][W_l] f32
 // block at a 256-byte aligned offset. H_{l+1} = ceil(H_l / 2) (avg_pool2d(2, padding=H_l % 2)).

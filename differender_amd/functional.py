@@ -637,6 +637,20 @@ def _loss_inputs(out, reference):
     return out, reference, (ctypes.c_int64 * 4)(*out.stride())
 
 
+def _loss_bwd_buffers(x, stats, numel, stats_msg, upstream, middle, want_ref_grad):
+    """What both loss backwards check and allocate: `stats` is the forward's (numel float64 on x's device), `upstream` three
+    float32 on the device or None; returns (upstream, d out, d reference or None), the gradients with x's strides."""
+    if stats.dtype != torch.float64 or stats.numel() != numel or stats.device != x.device or not stats.is_contiguous():
+        raise ValueError(stats_msg)
+    if upstream is not None:
+        upstream = upstream.to(device=x.device, dtype=torch.float32).contiguous()
+        if upstream.numel() != 3:
+            raise ValueError(f"upstream holds the gradients of (loss, {middle}, mse): 3 elements")
+    gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
+    gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device) if want_ref_grad else None
+    return upstream, gx, gy
+
+
 def _loss_config(data_range, win_size, win_sigma, K, nonnegative_ssim):
     return (float(data_range), int(win_size), float(win_sigma), float(K[0]), float(K[1]),
             N.DR_SSIM_NONNEGATIVE if nonnegative_ssim else 0)
@@ -664,14 +678,8 @@ def dssim_mse_bwd(out, reference, stats, upstream=None, want_ref_grad=False, dat
     Returns (d out, d reference or None); bitwise deterministic."""
     x, y, strides = _loss_inputs(out, reference)
     n, c, h, w = x.shape
-    if stats.dtype != torch.float64 or stats.numel() != n * c + 3 or stats.device != x.device or not stats.is_contiguous():
-        raise ValueError("stats must be the float64 output of dssim_mse_fwd for these images")
-    if upstream is not None:
-        upstream = upstream.to(device=x.device, dtype=torch.float32).contiguous()
-        if upstream.numel() != 3:
-            raise ValueError("upstream holds the gradients of (loss, dssim, mse): 3 elements")
-    gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
-    gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device) if want_ref_grad else None
+    upstream, gx, gy = _loss_bwd_buffers(x, stats, n * c + 3, "stats must be the float64 output of dssim_mse_fwd for these images",
+                                         upstream, "dssim", want_ref_grad)
     with torch.cuda.device(x.device):
         rc = N.lib().dr_dssim_mse_bwd(x.data_ptr(), y.data_ptr(), n, c, h, w, strides,
                                       *_loss_config(data_range, win_size, win_sigma, K, nonnegative_ssim),
@@ -729,15 +737,9 @@ def msssim_mse_bwd(out, reference, stats, upstream=None, want_ref_grad=False, da
     x, y, strides = _loss_inputs(out, reference)
     n, c, h, w = x.shape
     cfg = _msssim_config(data_range, win_size, win_sigma, K, weights)
-    if stats.dtype != torch.float64 or stats.numel() != (cfg[-1] + 1) * n * c + 3 or stats.device != x.device \
-            or not stats.is_contiguous():
-        raise ValueError("stats must be the float64 output of msssim_mse_fwd for these images and levels")
-    if upstream is not None:
-        upstream = upstream.to(device=x.device, dtype=torch.float32).contiguous()
-        if upstream.numel() != 3:
-            raise ValueError("upstream holds the gradients of (loss, dms, mse): 3 elements")
-    gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
-    gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device) if want_ref_grad else None
+    upstream, gx, gy = _loss_bwd_buffers(x, stats, (cfg[-1] + 1) * n * c + 3,
+                                         "stats must be the float64 output of msssim_mse_fwd for these images and levels",
+                                         upstream, "dms", want_ref_grad)
     ws = _msssim_workspace(x, cfg[-1], want_ref_grad)
     with torch.cuda.device(x.device):
         rc = N.lib().dr_msssim_mse_bwd(x.data_ptr(), y.data_ptr(), n, c, h, w, strides, *cfg, stats.data_ptr(),

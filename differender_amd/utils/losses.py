@@ -69,39 +69,43 @@ def dssim_mse_loss(res, gt):
     return torch.nan_to_num(dssim) + mse, dssim, mse
 
 
-class _FusedDSSIMMSE(torch.autograd.Function):
-    """(loss, dssim, mse) as one 3-element float32 tensor; the caller unbinds it, so autograd hands backward the three upstream
-    gradients stacked on the device and the kernel reads them there (no host read)."""
+class _FusedImageLoss(torch.autograd.Function):
+    """(loss, dssim or dms, mse) of one of the fused image losses (`fwd`, `bwd`: its pair of differender_amd.functional) as one
+    3-element float32 tensor; the caller unbinds it, so autograd hands backward the three upstream gradients stacked on the
+    device and the kernel reads them there (no host read)."""
 
     @staticmethod
-    def forward(ctx, res, gt, cfg):
-        from differender_amd import functional as DF
-        stats = DF.dssim_mse_fwd(res, gt, **cfg)
+    def forward(ctx, res, gt, fwd, bwd, cfg):
+        stats = fwd(res, gt, **cfg)
         ctx.save_for_backward(res, gt, stats)
-        ctx.cfg = cfg
+        ctx.bwd, ctx.cfg = bwd, cfg
         return stats[-3:].float()
 
     @staticmethod
     def backward(ctx, g3):
-        from differender_amd import functional as DF
         res, gt, stats = ctx.saved_tensors
-        gx, gy = DF.dssim_mse_bwd(res, gt, stats, upstream=g3, want_ref_grad=ctx.needs_input_grad[1], **ctx.cfg)
-        return (gx if ctx.needs_input_grad[0] else None), gy, None
+        gx, gy = ctx.bwd(res, gt, stats, upstream=g3, want_ref_grad=ctx.needs_input_grad[1], **ctx.cfg)
+        return (gx if ctx.needs_input_grad[0] else None), gy, None, None, None
+
+
+def _fused_image_loss(name, res, gt, fwd, bwd, cfg):
+    """The input check of both fused_*_loss front-ends (`name`: the one in the messages), then the loss as (loss, d, mse)."""
+    if res.ndim != 4 or gt.shape != res.shape:
+        raise ValueError(f"{name} expects two (N, C, H, W) tensors of the same shape")
+    if res.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise TypeError(f"{name} expects float32 tensors")
+    if not (res.is_cuda and gt.is_cuda):
+        raise RuntimeError(f"{name} runs on a ROCm GPU only: there is no CPU path")
+    return _FusedImageLoss.apply(res, gt, fwd, bwd, cfg).unbind(0)
 
 
 def fused_dssim_mse_loss(res, gt, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03), nonnegative_ssim=True):
     """dssim_mse_loss on the HIP kernels: returns (loss, dssim, mse), 0-d float32 tensors, with
     loss = nan_to_num(1 - ssim2d(res, gt, data_range, ..., nonnegative_ssim)) + mse_loss(res, gt). Differentiable w.r.t. res
     and, when it requires a gradient, gt. res and gt: (N, C, H, W) float32 on a ROCm GPU (there is no CPU path)."""
-    if res.ndim != 4 or gt.shape != res.shape:
-        raise ValueError("fused_dssim_mse_loss expects two (N, C, H, W) tensors of the same shape")
-    if res.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise TypeError("fused_dssim_mse_loss expects float32 tensors")
-    if not (res.is_cuda and gt.is_cuda):
-        raise RuntimeError("fused_dssim_mse_loss runs on a ROCm GPU only: there is no CPU path")
+    from differender_amd import functional as DF
     cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma, K=tuple(K), nonnegative_ssim=nonnegative_ssim)
-    loss, dssim, mse = _FusedDSSIMMSE.apply(res, gt, cfg).unbind(0)
-    return loss, dssim, mse
+    return _fused_image_loss("fused_dssim_mse_loss", res, gt, DF.dssim_mse_fwd, DF.dssim_mse_bwd, cfg)
 
 
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -156,39 +160,14 @@ def ms_dssim_mse_loss(res, gt, win_size=11, win_sigma=1.5, weights=None, K=(0.01
     return torch.nan_to_num(dms) + mse, dms, mse
 
 
-class _FusedMSDSSIMMSE(torch.autograd.Function):
-    """(loss, dms, mse) as one 3-element float32 tensor, as _FusedDSSIMMSE: the upstream gradients are read on the device."""
-
-    @staticmethod
-    def forward(ctx, res, gt, cfg):
-        from differender_amd import functional as DF
-        stats = DF.msssim_mse_fwd(res, gt, **cfg)
-        ctx.save_for_backward(res, gt, stats)
-        ctx.cfg = cfg
-        return stats[-3:].float()
-
-    @staticmethod
-    def backward(ctx, g3):
-        from differender_amd import functional as DF
-        res, gt, stats = ctx.saved_tensors
-        gx, gy = DF.msssim_mse_bwd(res, gt, stats, upstream=g3, want_ref_grad=ctx.needs_input_grad[1], **ctx.cfg)
-        return (gx if ctx.needs_input_grad[0] else None), gy, None
-
-
 def fused_ms_dssim_mse_loss(res, gt, data_range=1.0, win_size=11, win_sigma=1.5, weights=None, K=(0.01, 0.03)):
     """ms_dssim_mse_loss on the HIP kernels: returns (loss, dms, mse), 0-d float32 tensors, with
     loss = nan_to_num(1 - ms_ssim2d(res, gt, data_range, ...)) + mse_loss(res, gt). Differentiable w.r.t. res and, when it
     requires a gradient, gt. res and gt: (N, C, H, W) float32 on a ROCm GPU (there is no CPU path)."""
-    if res.ndim != 4 or gt.shape != res.shape:
-        raise ValueError("fused_ms_dssim_mse_loss expects two (N, C, H, W) tensors of the same shape")
-    if res.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise TypeError("fused_ms_dssim_mse_loss expects float32 tensors")
-    if not (res.is_cuda and gt.is_cuda):
-        raise RuntimeError("fused_ms_dssim_mse_loss runs on a ROCm GPU only: there is no CPU path")
+    from differender_amd import functional as DF
     cfg = dict(data_range=data_range, win_size=win_size, win_sigma=win_sigma,
                weights=tuple(float(w) for w in (MS_SSIM_WEIGHTS if weights is None else weights)), K=tuple(K))
-    loss, dms, mse = _FusedMSDSSIMMSE.apply(res, gt, cfg).unbind(0)
-    return loss, dms, mse
+    return _fused_image_loss("fused_ms_dssim_mse_loss", res, gt, DF.msssim_mse_fwd, DF.msssim_mse_bwd, cfg)
 
 
 TV_NORMS = ("l1", "iso", "sq")

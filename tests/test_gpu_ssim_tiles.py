@@ -382,3 +382,11 @@ def test_non_finite(where, ms):
         assert torch.allclose(g[~bad], sign * e[~bad], rtol=1e-6, atol=0)
         finite = torch.isfinite(a)
         assert torch.allclose(g.cpu().double()[finite], a[finite], rtol=1e-5, atol=1e-12)
+    # ... and of which kind at the infinite pixel of x: D9 runs the chain through its zero maps,
+    # 2 (x - shift) 0 = NaN in both gradients; D10 skips the chain, and the mse term's +-inf stays
+    if where == "inf_in_x":
+        at = (0, 1, shape[2] // 2, shape[3] // 4)
+        if ms:
+            assert float(gx[at]) == math.inf and float(gy[at]) == -math.inf
+        else:
+            assert math.isnan(float(gx[at])) and math.isnan(float(gy[at]))
