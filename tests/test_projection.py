@@ -1,5 +1,7 @@
 """X-ray line-integral and maximum intensity projections without a GPU: the float64 transliteration against
-central differences and the chord length, the C ABI's argument checks, Projector's shape checks."""
+central differences and the chord length, the C ABI's argument checks, Projector's shape checks; the reference's helpers for
+tests/test_gpu_projection_edges.py (sample_at, window_plan, layout_volume) and that file's case tables: the window paths, the
+clipping and the compared shares each case is there for."""
 import ctypes
 import math
 import os
@@ -189,3 +191,146 @@ def test_projector_rejects_malformed_arguments(hiplib):
                  (torch.zeros(1, 2, 8, 6, 7), lf)):
         with pytest.raises(ValueError):
             pj(v, c)
+
+
+# ---- the reference's helpers for tests/test_gpu_projection_edges.py and that file's choice of cases ----------------------------
+
+CG = PR.CG   # tests/golden/make_camgrad_golden.py: the transliterated ray setup
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_sample_at_the_argmax_is_the_maximum(case):
+    vshape, (W, H), sr, S, seed, cp = CASES[case]
+    vol = _volume(vshape, 21, lo=-0.4).detach()
+    cam = _cam(*cp)
+    out, arg, (e, x, r, n) = PR.project_camera(vol, cam, W, H, sr, S, "max", jitter_seed=seed, view=1)
+    assert (arg >= 0).any()
+    assert torch.equal(PR.sample_at(vol, cam, e, x, r, n, arg), out)
+    # any other sample of a ray is no larger, an earlier one is smaller; the gap of project_top2 is that to the runner-up
+    best, arg2, gap = PR.project_top2(vol, cam, e, x, r, n, S)
+    assert torch.equal(best, out) and torch.equal(arg2, arg)
+    m = torch.where(n > 1, torch.clamp(n, max=S if S is not None else 1 << 30), torch.zeros_like(n))
+    runner_up = torch.full_like(out, -math.inf)
+    for s in range(int(m.max())):
+        v = PR.sample_at(vol, cam, e, x, r, n, torch.full_like(n, s))
+        live = s < m
+        assert (v[live] <= out[live]).all() and (v[live & (s < arg)] < out[live & (s < arg)]).all()
+        runner_up = torch.where(live & (s != arg), torch.maximum(runner_up, v), runner_up)
+    assert torch.equal(gap, out - runner_up) and (gap[arg >= 0] >= 0).all()
+    # differentiable in the volume: the 8 trilinear weights of one sample sum to 1 per live ray
+    v = vol.clone().requires_grad_(True)
+    PR.sample_at(v, cam, e, x, r, n, arg).sum().backward()
+    assert abs(float(v.grad.sum()) - int((arg >= 0).sum())) <= 1e-9 * W * H
+
+
+def test_window_constants_are_read_from_the_kernel_source():
+    K = PR.window_constants()
+    assert set(K) == {"PW_TILE", "PW_BOX", "PW_WIN_VOX", "PW_MIN_VOX"}
+    assert K["PW_TILE"] == 16 and K["PW_BOX"] * 4 <= 64 * 1024 and K["PW_WIN_VOX"] > K["PW_MIN_VOX"] >= 1
+
+
+def _plan(case):
+    """window_plan over the case's views on float32 rays of the transliterated ray setup, and the clipped share of live rays."""
+    W, H = case["WH"]
+    total, clipped = np.zeros(5, dtype=np.int64), []
+    for v, c in enumerate(case["cams"]):
+        e, x, r, n = CG.ray_setup(torch.tensor(c, dtype=torch.float32), W, H, case["vshape"], case["sr"], case["fov"], 0.1,
+                                  case["seed"], v)
+        total += np.array(PR.window_plan(c, e, x, r, n, case["vshape"], case["S"], W, H))
+        if case["S"] is not None:
+            clipped.append(float((n[n > 1] > case["S"]).float().mean()))
+    return PR.WindowPlan(*(int(t) for t in total)), clipped
+
+
+def test_edge_cases_reach_the_window_paths_they_claim():
+    claimed = {}
+    for name, case in PR.EDGE_CASES.items():
+        plan, clipped = _plan(case)
+        windows = plan.lds_full + plan.lds_halved + plan.fallback
+        for path in case["paths"]:
+            count = getattr(plan, path)
+            assert count >= 3 and count >= 0.05 * windows, (name, path, plan)
+            claimed.setdefault(path, set()).add(case["dtype"])
+        if case.get("dead_tiles"):
+            assert plan.dead_tiles >= 1 and plan.live_tiles >= 1, (name, plan)
+        assert all(c > 1 / 3 for c in clipped), (name, clipped)
+        W, H = case["WH"]
+        assert W % 16 and H % 16 and W > 32 and H > 32, name   # 3 x 3 tiles or more, the last ones partly filled
+    for path in ("lds_full", "lds_halved", "fallback"):
+        assert claimed.get(path) == {torch.float32, torch.float16}, (path, claimed.get(path))
+    cases = PR.EDGE_CASES.values()
+    assert {c["layout"] for c in cases} == {"x", "y", "z", "strided"}
+    assert sum(c["S"] is not None for c in cases) >= 2 and sum(c["dtype"] == torch.float16 for c in cases) >= 2
+    assert any(c["S"] is not None and c["dtype"] == torch.float16 for c in cases)
+    assert any(c["S"] is not None and "lds_halved" in c["paths"] for c in cases)
+    assert any(c["own"] and len(c["cams"]) == 3 and c["seed"] for c in cases)
+    assert any(max(c["vshape"]) >= 3 * min(c["vshape"]) for c in cases)
+    assert any(max(abs(v) for v in c["cams"][0]) < 1 for c in cases)   # a camera inside the box
+
+
+def test_window_plan_counts_a_single_tile_by_hand():
+    # one ray along z through the middle of a 40^3 volume: 39 voxels of depth in windows of 16 -> 3 windows, a 2x2xN box each
+    vs = (40, 40, 40)
+    e, x = np.full((1, 1), 1.0, np.float32), np.full((1, 1), 3.0, np.float32)
+    r = np.array([[[0.0, 0.0, -1.0]]], np.float32)
+    plan = PR.window_plan([0.01, 0.01, 2.0], e, x, r, np.array([[40]]), vs, None, 1, 1)
+    assert plan == PR.WindowPlan(3, 0, 0, 0, 1), plan
+    assert PR.window_plan([0.01, 0.01, 2.0], e, x, r, np.array([[1]]), vs, None, 1, 1) == PR.WindowPlan(0, 0, 0, 1, 0)
+    # clipped to 10 samples: the walk still covers the depth range, only the first window has samples
+    assert PR.window_plan([0.01, 0.01, 2.0], e, x, r, np.array([[40]]), vs, 10, 1, 1) == PR.WindowPlan(1, 0, 0, 0, 1)
+
+
+def test_layout_volume_keeps_values_and_gives_the_strides():
+    vals = torch.rand(2, 5, 6, 7)
+    for v in (vals, vals[0]):
+        for layout, unit in (("z", -1), ("x", -3), ("y", -2), ("strided", None)):
+            t = PR.layout_volume(v, layout)
+            assert t.shape == v.shape and torch.equal(t, v), layout
+            assert all(s != 1 for s in t.stride()) if unit is None else t.stride(unit) == 1
+    t = PR.layout_volume(vals[0], "strided")
+    assert torch.zeros_like(t, memory_format=torch.preserve_format).stride() != t.stride()
+
+
+@pytest.mark.parametrize("mode", ["sum", "max"])
+@pytest.mark.parametrize("name", sorted(PR.CAM_CASES))
+def test_camera_cases_keep_nine_rays_in_ten(name, mode):
+    """The share of rays on which the GPU test compares d look_from per ray: those whose sample count (and argmax) the float64
+    and the float32 program agree on. Also the clipping the "clipped" case is there for."""
+    case = PR.CAM_CASES[name]
+    W, H = case["WH"]
+    for v, c in enumerate(case["cams"]):
+        vol = PR.case_values(case, 8, lo=-0.3 if mode == "max" else 0.0)
+        res = {}
+        for dt in (F64, torch.float32):
+            _, a, (_, _, _, n) = PR.project_camera(vol.to(dt), torch.tensor(c, dtype=dt), W, H, case["sr"], case["S"], mode,
+                                                   fov_deg=case["fov"], jitter_seed=case["seed"], view=case["view_base"] + v)
+            res[dt] = (n, a)
+        same = res[F64][0] == res[torch.float32][0]
+        if mode == "max":
+            same &= res[F64][1] == res[torch.float32][1]
+        assert same.float().mean() >= 0.9, (name, v, float(same.float().mean()))
+        n = res[F64][0]
+        assert (n > 1).any()
+        if case["S"] is not None:
+            assert (n[n > 1] > case["S"]).float().mean() > 1 / 3
+    if name == "odd_missed":
+        assert W % 8 and H % 8 and (n == 0).any()
+
+
+@pytest.mark.parametrize("name", sorted(PR.MIP_CASES))
+def test_mip_cases_have_a_clear_maximum_on_most_rays(name):
+    """The share of live rays whose float64 top-two gap exceeds 1e-4 of the image's scale: where the GPU test asks the
+    kernel's arg_max to equal the reference's exactly."""
+    case = PR.MIP_CASES[name]
+    W, H = case["WH"]
+    V = len(case["cams"])
+    vols = PR.case_values(case, 11, V if case["own"] else None, lo=-0.3).double()
+    for v, c in enumerate(case["cams"]):
+        cam = torch.tensor(c, dtype=F64)
+        e, x, r, n = CG.ray_setup(cam, W, H, case["vshape"], case["sr"], case["fov"], 0.1, case["seed"], v)
+        best, arg, gap = PR.project_top2(vols[v] if case["own"] else vols, cam, e, x, r, n, case["S"])
+        live = arg >= 0
+        assert live.sum() >= 50
+        assert (gap[live] > 1e-4 * float(best.abs().max())).float().mean() >= 0.95, (name, v)
+        if case["S"] is not None:
+            assert (n[live] > case["S"]).float().mean() > 1 / 3
