@@ -63,6 +63,7 @@ def test_torch_ray_setup_matches_the_oracle(oracle, path):
 
 
 def test_cases_cover_what_they_are_named_for():
+    import make_camgrad_golden as CG
     d = {os.path.basename(p)[8:-4]: np.load(p) for p in FIXTURES}
     live = lambda c: d[c]["n"] > 1
     assert ((d["b_sr2_ert"]["steps"] < d["b_sr2_ert"]["n"]) & live("b_sr2_ert")).sum() > 20
@@ -72,6 +73,32 @@ def test_cases_cover_what_they_are_named_for():
     f = d["f_near_face"]
     t = np.minimum((-1 - f["cam"]) / f["rays"], (1 - f["cam"]) / f["rays"]).argmax(-1)[live("f_near_face")]
     assert len(np.unique(t)) >= 2   # tmin switches faces across the image
+    # rays along a coordinate plane: a direction component of exactly 0 (two on the centre ray of the camera on the x axis)
+    axial = lambda c: (d[c]["rays"] == 0).sum(-1) * live(c)
+    assert (axial("g_plane_y0") > 0).sum() > 0 and (d["g_plane_y0"]["rays"][..., 1] == 0)[live("g_plane_y0")].sum() > 0
+    assert (axial("h_plane_x0") > 0).sum() > 0 and (d["h_plane_x0"]["rays"][..., 0] == 0)[live("h_plane_x0")].sum() > 0
+    assert (axial("i_on_x_axis") > 0).sum() > 0 and axial("i_on_x_axis").max() == 2
+    for c in ("g_plane_y0", "h_plane_x0", "i_on_x_axis"):
+        assert np.isfinite(d[c]["dcam_ray"]).all() and np.abs(d[c]["dcam_ray"][axial(c) > 0]).min() > 0
+    for c in ("j_inside", "k_inside_sr2_ert"):   # the camera inside the box
+        assert live(c).sum() > 0 and (d[c]["entry"][live(c)] < 0).all()
+    k = d["k_inside_sr2_ert"]
+    assert ((k["steps"] < k["n"]) & live("k_inside_sr2_ert")).sum() > 20 and int(k["jitter_seed"]) != 0 and float(k["sr"]) == 2.0
+    sc = d["l_anisotropic"]["vol"].shape
+    assert max(sc) >= 3 * min(sc)
+    flat, _ = CG.sample_stats(d["m_object_in_air"], d["m_object_in_air"])
+    m_live = live("m_object_in_air")
+    assert flat[m_live].sum() > 0.2 * d["m_object_in_air"]["steps"][m_live].sum()
+    assert (flat[m_live] < d["m_object_in_air"]["steps"][m_live]).mean() > 0.5   # and most rays meet structure as well
+    assert float(d["m_object_in_air"]["tf"][0, 3]) == 0.0
+    o = d["o_edge_grazing"]
+    last = o["cam"] + o["exit"][..., None] * o["rays"]   # the last sample: on one face, and within a tap (1e-3) of a second
+    grazing = ((1.0 - np.abs(last) < 1e-3).sum(-1) >= 2) & (np.abs(last).max(-1) - np.sort(np.abs(last), -1)[..., 1] > 2e-4)
+    assert (grazing & live("o_edge_grazing")).sum() >= 6
+    _, outside = CG.sample_stats(d["n_out_of_range"], d["n_out_of_range"])
+    assert outside[live("n_out_of_range")].sum() > 0
+    v = d["n_out_of_range"]["vol"]
+    assert (v > 1).sum() >= 12 and (v < 0).sum() >= 12 and np.array_equal(np.clip(v, 0, 1)[(v >= 0) & (v <= 1)], d["a_orbit_sr1"]["vol"][(v >= 0) & (v <= 1)])
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[8:-4])

@@ -13,28 +13,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, GOLDEN)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "camgrad_*.npz")))
 
+from camgrad_gpu import hip_per_ray as _hip_per_ray  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-
-
-def _hip_per_ray(inp, ref, vol_dtype, keep):
-    """(per-ray d_cam (W,H,3), total (3,), mask of the compared rays) of F.march_bwd_cam on the reference's ray buffers; only
-    the rays in `keep` get an upstream gradient."""
-    from differender_amd import functional as F
-    dev = torch.device("cuda")
-    T = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)
-    vol = T(inp["vol"]).to(vol_dtype)
-    tf, cam = T(inp["tf"]), T(inp["cam"])[None]
-    e, x, r, n = T(ref["entry"])[None], T(ref["exit"])[None], T(ref["rays"])[None], T(ref["n"], torch.int32)[None]
-    S, sr = int(inp["max_samples"]), float(inp["sr"])
-    out, steps = F.march_fwd(vol, tf, cam, e, x, r, n, S, sr)
-    mask = (steps[0].cpu().numpy() == ref["steps"]) & (ref["n"] > 1) & keep
-    g = T(inp["grad_out"] * mask[..., None])[None]   # rays whose f32 march stops elsewhere, and n == 1 rays: zero upstream
-    d, d_ray = F.march_bwd_cam(vol, tf, cam, e, x, r, n, steps, S, sr, g, out, jitter_seed=int(inp["jitter_seed"]),
-                               view_base=int(inp["view"]), per_ray=True)
-    torch.cuda.synchronize()
-    return d_ray[0].double().cpu().numpy(), d[0].double().cpu().numpy(), mask
 
 
 @pytest.mark.parametrize("vol_dtype", [torch.float32, torch.float16], ids=["f32", "f16"])
