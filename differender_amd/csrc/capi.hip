@@ -463,6 +463,65 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     return launch_march_tf2d_bwd(a, (hipStream_t)stream);
 }
 
+// what the two RGBA-volume entries check before any HIP call, and the MarchArgs they share
+static int fill_rgba(MarchArgs &a, RgbaArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
+                     int64_t sz, int64_t sc, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,
+                     const float *rays, const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate) {
+    if (!vol || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
+    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
+    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
+    if (max_samples < 1 || !std::isfinite(sampling_rate) || !(sampling_rate > 0.0f)) return DR_EINVAL;
+    a = MarchArgs{};
+    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
+    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
+    a.R = 1; a.RG = 1;
+    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
+    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate; a.img_W = W;
+    q = RgbaArgs{};
+    q.sc = sc;
+    return 0;
+}
+
+int dr_march_rgba_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                      int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate, int mode,
+                      float *out_rgba, int32_t *steps, void *stream) {
+    MarchArgs a;
+    RgbaArgs q;
+    const int rc = fill_rgba(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp,
+                             n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!out_rgba) return DR_EINVAL;
+    if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
+    a.mode = mode; a.out = out_rgba; a.steps = steps;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_march_rgba_fwd) return DR_EUNSUPPORTED;   // (a library linked without march_rgba.o)
+    return launch_march_rgba_fwd(a, q, (hipStream_t)stream);
+}
+
+int dr_march_rgba_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                      int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                      const float *grad_out, const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz,
+                      int64_t dsc, int64_t dvol_view_stride, void *stream) {
+    MarchArgs a;
+    RgbaArgs q;
+    const int rc = fill_rgba(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp,
+                             n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!grad_out || !out_rgba) return DR_EINVAL;
+    if (!d_vol) return 0;  // nothing requested
+    a.mode = DR_MODE_DIFF;
+    a.grad_out = grad_out; a.out_fwd = out_rgba;
+    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
+    q.dsc = dsc;
+    DeviceOf guard(vol);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch_march_rgba_bwd) return DR_EUNSUPPORTED;
+    return launch_march_rgba_bwd(a, q, (hipStream_t)stream);
+}
+
 // what the three projection entries check: fill_common's volume and ray checks without a table, max_samples >= 1, the mode,
 // and arg_max for DR_PROJ_MAX
 static int fill_proj(MarchArgs &a, ProjArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,

@@ -163,6 +163,16 @@ __attribute__((weak)) int launch_project_fwd(const MarchArgs &a, const ProjArgs 
 __attribute__((weak)) int launch_project_bwd(const MarchArgs &a, const ProjArgs &q, hipStream_t stream);
 __attribute__((weak)) int launch_project_bwd_cam(const MarchArgs &a, const ProjArgs &q, hipStream_t stream);
 
+// March through a pre-classified RGBA volume (march_rgba.hip): what dr_march_rgba_fwd / _bwd take beside their
+// MarchArgs (volume and its x/y/z and view strides, ray buffers, extents, max_samples S, sr, mode; the backward's grad_out,
+// out_fwd and d_vol with its strides): the channel strides of the volume and of d_vol, in elements
+struct RgbaArgs {
+    int64_t sc, dsc;
+};
+// weak, as launch_camera_grad: capi.o must load in a library linked without march_rgba.o
+__attribute__((weak)) int launch_march_rgba_fwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream);
+__attribute__((weak)) int launch_march_rgba_bwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

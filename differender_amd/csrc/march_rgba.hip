@@ -1,0 +1,221 @@
+// march_rgba.hip -- the march through a pre-classified RGBA volume, for gfx950.
+// The shape of march_baseline.hip / march_tf2d.hip: one lane per ray, a wave per 8x8 pixel tile, 256-thread workgroups, direct
+// global gathers, the sequential float32 recurrence and the tape-free adjoint (suffix = out - prefix). There is no table and no
+// shading: a sample is the trilinear interpolation of the volume's four channels (one cell, eight corners, x -> y -> z through
+// mixf, per channel), its opacity opacity_of_alpha(a, 1/sr), and it composites with L = 1.
+//   VEC: the channels of a voxel are neighbours in memory and every voxel is 16-B (f32) / 8-B (f16) aligned: a corner is ONE
+//   load instead of four. The host decides once per launch (rgba_vec_ok); both paths read the same values and do the same
+//   arithmetic in the same order, so their images are the same bits.
+#include "dr_tile.h"
+
+namespace dr {
+
+// The 4-channel view: the scalar kernels' view (extents, x/y/z strides, the cell scale) plus the channel stride.
+template <typename VT>
+struct RgbaParams {
+    VolView<VT> vol; int64_t sc, vol_vs;
+    const float *cam, *entry, *exit_, *rays; const int32_t *nsamp;
+    int W, H, S; float inv_sr;
+    float *out; int32_t *steps;
+    const float *grad_out, *out_fwd;
+    GradView dvol; int64_t dsc, dvol_vs;
+};
+
+template <typename VT>
+static inline RgbaParams<VT> make_rgba_params(const MarchArgs &a, const RgbaArgs &q) {
+    RgbaParams<VT> P;
+    P.vol = make_vol_view<VT>(a); P.sc = q.sc; P.vol_vs = a.vol_vs;
+    P.cam = a.cam; P.entry = a.entry; P.exit_ = a.exit_; P.rays = a.rays; P.nsamp = a.nsamp;
+    P.W = a.W; P.H = a.H; P.S = a.S; P.inv_sr = 1.0f / a.sr;
+    P.out = a.out; P.steps = a.steps;
+    P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
+    P.dvol.p = a.d_vol; P.dvol.sx = a.dsx; P.dvol.sy = a.dsy; P.dvol.sz = a.dsz; P.dsc = q.dsc; P.dvol_vs = a.dvol_vs;
+    return P;
+}
+
+struct __attribute__((aligned(8))) Half4 { unsigned short r, g, b, a; };
+
+// the four channels of one voxel
+template <bool VEC>
+__device__ __forceinline__ float4 ld_voxel4(const float *p, int64_t sc) {
+    if (VEC) return *reinterpret_cast<const float4 *>(p);
+    return make_float4(p[0], p[sc], p[2 * sc], p[3 * sc]);
+}
+template <bool VEC>
+__device__ __forceinline__ float4 ld_voxel4(const __half *p, int64_t sc) {
+    if (VEC) {
+        const Half4 q = *reinterpret_cast<const Half4 *>(p);
+        return make_float4(__half2float(__ushort_as_half(q.r)), __half2float(__ushort_as_half(q.g)),
+                           __half2float(__ushort_as_half(q.b)), __half2float(__ushort_as_half(q.a)));
+    }
+    return make_float4(__half2float(p[0]), __half2float(p[sc]), __half2float(p[2 * sc]), __half2float(p[3 * sc]));
+}
+
+__device__ __forceinline__ float4 mix4(float4 x, float4 y, float a) {
+    return make_float4(mixf(x.x, y.x, a), mixf(x.y, y.y, a), mixf(x.z, y.z, a), mixf(x.w, y.w, a));
+}
+
+// tri_sample (dr_device.h) on four channels: one cell, eight corner fetches, the lerps x -> y -> z per channel
+template <typename VT, bool VEC>
+__device__ __forceinline__ float4 tri_sample4(const VolView<VT> &v, int64_t sc, const Cell &c) {
+    const VT *b00 = v.p + c.x0 * v.sx + c.y0 * v.sy, *b10 = v.p + c.x1 * v.sx + c.y0 * v.sy;
+    const VT *b01 = v.p + c.x0 * v.sx + c.y1 * v.sy, *b11 = v.p + c.x1 * v.sx + c.y1 * v.sy;
+    const int64_t o0 = c.z0 * v.sz, o1 = c.z1 * v.sz;
+    float4 a = mix4(ld_voxel4<VEC>(b00 + o0, sc), ld_voxel4<VEC>(b10 + o0, sc), c.fx);
+    float4 b = mix4(ld_voxel4<VEC>(b01 + o0, sc), ld_voxel4<VEC>(b11 + o0, sc), c.fx);
+    const float4 zl = mix4(a, b, c.fy);
+    a = mix4(ld_voxel4<VEC>(b00 + o1, sc), ld_voxel4<VEC>(b10 + o1, sc), c.fx);
+    b = mix4(ld_voxel4<VEC>(b01 + o1, sc), ld_voxel4<VEC>(b11 + o1, sc), c.fx);
+    const float4 zh = mix4(a, b, c.fy);
+    return mix4(zl, zh, c.fz);
+}
+
+// samples of a ray (n <= 1: none, H6); the non-differentiable march has no max_samples clip
+__device__ __forceinline__ int rgba_samples(int n, int S, bool nondiff) { return n > 1 ? (nondiff || n < S ? n : S) : 0; }
+
+template <typename VT, bool VEC, bool NONDIFF>
+__global__ __launch_bounds__(256) void march_rgba_fwd_kernel(RgbaParams<VT> P) {
+    int i, j;
+    if (!tile_pixel(P.W, P.H, i, j)) return;
+    const int view = blockIdx.y;
+    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    VolView<VT> vol = P.vol;
+    vol.p += view * P.vol_vs;
+    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
+
+    RayGeom rg;
+    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
+    const int m = rgba_samples(rg.n, P.S, NONDIFF);
+
+    Composite c;
+    int cnt = 0;
+    for (int s = 0; s < m; ++s) {
+        if (!(c.A < 0.99f)) break;
+        Sample sm;
+        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
+        Cell cell;
+        tri_cell(vol, sm.px, sm.py, sm.pz, cell);
+        const float4 v = tri_sample4<VT, VEC>(vol, P.sc, cell);
+        ++cnt;
+        if (NONDIFF && !(v.w > 1e-3f)) continue;
+        sm.r = v.x; sm.g = v.y; sm.b = v.z; sm.a = v.w; sm.L = 1.0f;
+        sm.op = opacity_of_alpha(sm.a, P.inv_sr);
+        c.add(sm);
+    }
+    reinterpret_cast<float4 *>(P.out)[p] = c.pixel(NONDIFF);
+    if (P.steps) P.steps[p] = cnt;
+}
+
+// d_vol contributions of a run of consecutive live samples of one ray in one cell: 8 corners x 4 channels, summed in f32 and
+// sent as 32 atomics when the ray leaves the cell (march_tf2d.hip's CellRun, on the volume). Measured against 32 atomics per
+// sample (tools/patches/rgba_per_sample.patch, profiles/rgba_time.jsonl): 2.1-2.7x less time at sampling rate 1, 4.5-9.4x
+// at rate 4, for 21-33 VGPRs more.
+struct VoxelRun {
+    int x0 = -1, y0, z0;
+    float s[8][4];   // corners in tri_scatter_global's order: (x0,y0,z0) (x1,y0,z0) (x0,y1,z0) (x1,y1,z0), then z1
+    __device__ __forceinline__ bool same(const Cell &c) const { return c.x0 == x0 && c.y0 == y0 && c.z0 == z0; }
+    __device__ __forceinline__ void start(const Cell &c) {
+        x0 = c.x0; y0 = c.y0; z0 = c.z0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) s[k][q] = 0.0f;
+    }
+    __device__ __forceinline__ void add(const Cell &c, const float adj[4]) {
+        const float gx = 1.0f - c.fx, gy = 1.0f - c.fy, gz = 1.0f - c.fz;
+        const float w[8] = {gx * gy * gz, c.fx * gy * gz, gx * c.fy * gz, c.fx * c.fy * gz,
+                            gx * gy * c.fz, c.fx * gy * c.fz, gx * c.fy * c.fz, c.fx * c.fy * c.fz};
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) s[k][q] += w[k] * adj[q];
+    }
+    // (the high indices as tri_cell clamps them)
+    __device__ __forceinline__ void flush(const GradView &g, int64_t dsc, int VX, int VY, int VZ) const {
+        if (x0 < 0) return;
+        const int x1 = min(x0 + 1, VX - 1), y1 = min(y0 + 1, VY - 1), z1 = min(z0 + 1, VZ - 1);
+        float *b00 = g.p + x0 * g.sx + y0 * g.sy, *b10 = g.p + x1 * g.sx + y0 * g.sy;
+        float *b01 = g.p + x0 * g.sx + y1 * g.sy, *b11 = g.p + x1 * g.sx + y1 * g.sy;
+        const int64_t o0 = z0 * g.sz, o1 = z1 * g.sz;
+        float *const corner[8] = {b00 + o0, b10 + o0, b01 + o0, b11 + o0, b00 + o1, b10 + o1, b01 + o1, b11 + o1};
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) unsafeAtomicAdd(corner[k] + q * dsc, s[k][q]);
+    }
+};
+
+template <typename VT, bool VEC>
+__global__ __launch_bounds__(256) void march_rgba_bwd_kernel(RgbaParams<VT> P) {
+    int i, j;
+    if (!tile_pixel(P.W, P.H, i, j)) return;
+    const int view = blockIdx.y;
+    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    VolView<VT> vol = P.vol;
+    vol.p += view * P.vol_vs;
+    GradView dv = P.dvol;
+    dv.p += view * P.dvol_vs;
+    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
+
+    RayGeom rg;
+    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
+    const int m = rgba_samples(rg.n, P.S, false);
+    const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+
+    const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
+    const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+
+    Composite c;
+    VoxelRun run;
+    for (int s = 0; s < m; ++s) {
+        if (!(c.A < 0.99f)) break;
+        Sample sm;
+        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
+        Cell cell;
+        tri_cell(vol, sm.px, sm.py, sm.pz, cell);
+        const float4 v = tri_sample4<VT, VEC>(vol, P.sc, cell);
+        sm.r = v.x; sm.g = v.y; sm.b = v.z; sm.a = v.w;
+        sm.L = sm.Lraw = 1.0f; sm.flat = true;   // no shading: sample_adjoint's normal path is off
+        sm.op = opacity_of_alpha(sm.a, P.inv_sr);
+        const float T = c.add(sm);
+        const bool last = (s == m - 1) || !(c.A < 0.99f);
+        SampleAdj ad;
+        sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
+        const float adj[4] = {ad.r_bar, ad.g_bar, ad.b_bar, ad.a_bar};
+        if (!run.same(cell)) { run.flush(dv, P.dsc, vol.VX, vol.VY, vol.VZ); run.start(cell); }
+        run.add(cell, adj);
+    }
+    run.flush(dv, P.dsc, vol.VX, vol.VY, vol.VZ);
+}
+
+// VEC: a voxel's channels are one aligned 16-B (f32) / 8-B (f16) load wherever the voxel lies
+static bool rgba_vec_ok(const MarchArgs &a, const RgbaArgs &q) {
+    const size_t bytes = 4 * (a.vol_dtype == DR_F16 ? sizeof(__half) : sizeof(float));
+    return q.sc == 1 && a.sx % 4 == 0 && a.sy % 4 == 0 && a.sz % 4 == 0 && a.vol_vs % 4 == 0 &&
+           reinterpret_cast<uintptr_t>(a.vol) % bytes == 0;
+}
+
+template <typename VT>
+static int rgba_fwd_dispatch(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream) {
+    const RgbaParams<VT> P = make_rgba_params<VT>(a, q);
+    const bool vec = rgba_vec_ok(a, q);
+    if (a.mode == DR_MODE_DIFF)
+        return launch_tiles(vec ? march_rgba_fwd_kernel<VT, true, false> : march_rgba_fwd_kernel<VT, false, false>, a, 0, stream, P);
+    return launch_tiles(vec ? march_rgba_fwd_kernel<VT, true, true> : march_rgba_fwd_kernel<VT, false, true>, a, 0, stream, P);
+}
+
+template <typename VT>
+static int rgba_bwd_dispatch(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream) {
+    const RgbaParams<VT> P = make_rgba_params<VT>(a, q);
+    return launch_tiles(rgba_vec_ok(a, q) ? march_rgba_bwd_kernel<VT, true> : march_rgba_bwd_kernel<VT, false>, a, 0, stream, P);
+}
+
+int launch_march_rgba_fwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream) {
+    return a.vol_dtype == DR_F16 ? rgba_fwd_dispatch<__half>(a, q, stream) : rgba_fwd_dispatch<float>(a, q, stream);
+}
+
+int launch_march_rgba_bwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream) {
+    return a.vol_dtype == DR_F16 ? rgba_bwd_dispatch<__half>(a, q, stream) : rgba_bwd_dispatch<float>(a, q, stream);
+}
+
+}  // namespace dr

@@ -14,7 +14,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "march_tf2d_fwd", "march_tf2d_bwd", "project_fwd", "project_bwd",
+__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "march_tf2d_fwd", "march_tf2d_bwd", "march_rgba_fwd", "march_rgba_bwd", "project_fwd", "project_bwd",
            "project_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
@@ -500,6 +500,63 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
                                        out.data_ptr(), *dv, *dt, _stream())
     N.check(rc, "dr_march_tf2d_bwd")
     return d_vol, d_tf
+
+
+def _vol4_args(vol4, n_views):
+    """-> (ptr, dtype_tag, VX, VY, VZ, sx, sy, sz, sc, view_stride) of an RGBA volume ([views,] 4, VX, VY, VZ), any strides"""
+    if vol4.dtype == torch.float32:
+        tag = N.DR_F32
+    elif vol4.dtype == torch.float16:
+        tag = N.DR_F16
+    else:
+        raise TypeError(f"RGBA volume dtype must be float32 or float16, got {vol4.dtype}")
+    if vol4.ndim not in (4, 5) or vol4.shape[-4] != 4:
+        raise ValueError(f"RGBA volume must be (4,VX,VY,VZ) or (views,4,VX,VY,VZ), got {tuple(vol4.shape)}")
+    if vol4.ndim == 5 and vol4.shape[0] != n_views:
+        raise ValueError(f"batched RGBA volume has {vol4.shape[0]} items, expected {n_views}")
+    sc, sx, sy, sz = vol4.stride()[-4:]
+    return (vol4.data_ptr(), tag, *(int(v) for v in vol4.shape[-3:]), sx, sy, sz, sc, vol4.stride(0) if vol4.ndim == 5 else 0)
+
+
+def march_rgba_fwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate, mode=N.DR_MODE_DIFF, want_steps=True):
+    """The march through a pre-classified RGBA volume (dr_march_rgba_fwd): every sample is the trilinear
+    interpolation of the volume's four channels, composited with its opacity 1 - (1 - a)^(1/sampling_rate): no transfer function,
+    no shading. vol4: (4, VX, VY, VZ) shared or (views, 4, VX, VY, VZ), float32 or float16, any strides, never copied (with the
+    channel axis at stride 1 -- rgba.interleaved() -- a voxel is one load). Returns out (views,W,H,4) and steps (views,W,H) int32
+    (or None)."""
+    _require_gpu(vol4, "volume")
+    V, W, H = n.shape
+    dev = vol4.device
+    cam = cam.to(torch.float32).contiguous()
+    vargs = _vol4_args(vol4, V)
+    out = torch.empty((V, W, H, 4), dtype=torch.float32, device=dev)
+    steps = torch.empty((V, W, H), dtype=torch.int32, device=dev) if want_steps else None
+    with torch.cuda.device(dev):
+        rc = N.lib().dr_march_rgba_fwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
+                                       V, W, H, int(max_samples), float(sampling_rate), int(mode), out.data_ptr(),
+                                       steps.data_ptr() if want_steps else None, _stream())
+    N.check(rc, "dr_march_rgba_fwd")
+    return out, steps
+
+
+def march_rgba_bwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate, grad_out, out):
+    """d_vol of sum(march_rgba_fwd(...) * grad_out) (dr_march_rgba_bwd): float32, in vol4's own layout; a shared (un-batched)
+    volume receives one gradient summed over the views. NaN propagates (the plain kernels' convention: the caller applies
+    nan_to_num, as rgba.RaycasterRGBA does)."""
+    _require_gpu(vol4, "volume")
+    V, W, H = n.shape
+    cam = cam.to(torch.float32).contiguous()
+    grad_out = grad_out.to(torch.float32).contiguous()
+    out = out.contiguous()
+    vargs = _vol4_args(vol4, V)
+    d_vol = torch.zeros_like(vol4, dtype=torch.float32, memory_format=torch.preserve_format)
+    dc, dx, dy, dz = d_vol.stride()[-4:]
+    with torch.cuda.device(vol4.device):
+        rc = N.lib().dr_march_rgba_bwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
+                                       V, W, H, int(max_samples), float(sampling_rate), grad_out.data_ptr(), out.data_ptr(),
+                                       d_vol.data_ptr(), dx, dy, dz, dc, d_vol.stride(0) if d_vol.ndim == 5 else 0, _stream())
+    N.check(rc, "dr_march_rgba_bwd")
+    return d_vol
 
 
 _PROJ_MODES = {"sum": N.DR_PROJ_SUM, "max": N.DR_PROJ_MAX}

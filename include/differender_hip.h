@@ -361,6 +361,36 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                       float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
                       float *d_tf2d, int64_t dtf_view_stride, void *stream);
 
+/* March through a pre-classified ("pre-shaded") RGBA volume: the volume carries colour and opacity per voxel
+ * and is composited directly -- no transfer function, no shading. The samples are exactly those of the march, from the buffers
+ * of dr_ray_setup (jitter included): m = min(n, max_samples) of them in DR_MODE_DIFF, m = n in DR_MODE_NONDIFF, none for a ray
+ * with n <= 1 (pixel 0, steps 0). Per sample: (r, g, b, a) = the trilinear interpolation of the four channels (one cell, the
+ * lerps x -> y -> z per channel), op = 1 - (1 - a)^(1 / sampling_rate) (the specified power of dr_march_fwd); while A < 0.99:
+ * C_k += (1 - A) c_k op, A += (1 - A) op, sequentially in f32. DR_MODE_NONDIFF counts but does not composite samples with
+ * a <= 1e-3 and clamps the pixel to <= 1. Opacities outside [0, 1] are not clamped (NaN propagates as in the plain kernels).
+ *   vol      [n_views or 1] x 4 channels x (VX, VY, VZ), DR_F32 or DR_F16, element strides sx, sy, sz, sc (channel) and
+ *            vol_view_stride (0 = shared). With sc == 1 and the base pointer, sx, sy, sz and vol_view_stride all multiples of
+ *            four elements (an interleaved volume) a voxel is one 16-byte (8-byte) load; the results are the same bits.
+ *   out_rgba [n_views][W][H][4] f32; steps [n_views][W][H] int32, the live samples, nullable
+ * The backward (DR_MODE_DIFF) is the reverse-mode derivative of this program with n, the live samples and the cells frozen,
+ * tape-free like dr_march_bwd; d_vol is f32 with its own strides (dsx, dsy, dsz, dsc, dvol_view_stride; 0 = one gradient summed
+ * over the views), ACCUMULATED (caller zeroes); d_vol == NULL returns 0 before any HIP call.
+ * Invalid arguments (null required pointers, n_views, W or H <= 0, a volume extent < 2 (as for every march here: dr_ray_setup
+ * needs two voxels per axis), max_samples < 1, an unknown mode or dtype, a non-finite or non-positive sampling rate) return
+ * DR_EINVAL before any HIP call. */
+int dr_march_rgba_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                      int64_t sx, int64_t sy, int64_t sz, int64_t sc, int64_t vol_view_stride,
+                      const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                      int mode, float *out_rgba, int32_t *steps, void *stream);
+int dr_march_rgba_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                      int64_t sx, int64_t sy, int64_t sz, int64_t sc, int64_t vol_view_stride,
+                      const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                      const float *grad_out, const float *out_rgba,
+                      float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dsc, int64_t dvol_view_stride,
+                      void *stream);
+
 /* X-ray line-integral and maximum-intensity projections: the two standard projections of a scalar volume beside
  * compositing, differentiable w.r.t. the volume and the camera position. The samples are exactly those of the march, from the
  * ray buffers of dr_ray_setup (jitter included): s < m = min(n, max_samples), pos_s = look_from + mix(t0, exit, s/(n-1)) vd,
