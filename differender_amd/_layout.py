@@ -1,0 +1,98 @@
+"""The layout convention every renderer module shares (internal).
+
+A user volume ([BS,]C,D,H,W) is marched in the reference's field order (VX, VY, VZ) = (W, D, H) (VR.py:481), as a strided view
+and never a copy; an image leaves the kernels as ([BS,]W,H,K) and the user as ([BS,]K,H,W) with H flipped (VR.py:513,523);
+batched inputs agree on BS and un-batched ones are shared by all views. Raycaster, Raycaster2D, Projector and RaycasterRGBA
+differ in which inputs they take and what they check about them, not in any of this.
+"""
+import contextlib
+
+import torch
+
+from . import _native as N
+from . import functional as F
+
+
+def field_view(volume):
+    """Scalar volume ([BS,]1,D,H,W) -> its ([BS,]W,D,H) view."""
+    return volume.squeeze(1).permute(0, 3, 1, 2) if volume.ndim == 5 else volume.squeeze(0).permute(2, 0, 1)
+
+
+def field_view_rgba(volume):
+    """RGBA volume ([BS,]4,D,H,W) -> its ([BS,]4,W,D,H) view: whatever axis order the volume has in memory (rgba.interleaved)
+    reaches the kernels as strides."""
+    return volume.permute(0, 1, 4, 2, 3) if volume.ndim == 5 else volume.permute(0, 3, 1, 2)
+
+
+def batch_rule(look_from, *inputs):
+    """inputs: (tensor, its rank when batched) of everything beside look_from ([BS,]3). -> (batched, BS, look_from (BS,3)):
+    BS is the leading size the batched inputs agree on (ValueError otherwise), 0 and look_from (1,3) when none is batched;
+    an un-batched look_from is expanded to the batch, not copied."""
+    sizes = {t.shape[0] for t, rank in (*inputs, (look_from, 2)) if t.ndim == rank}
+    if not sizes:
+        return False, 0, look_from.reshape(1, 3)
+    if len(sizes) != 1:
+        raise ValueError(f"batched inputs disagree on the batch size: {sorted(sizes)}")
+    bs = sizes.pop()
+    return True, bs, look_from if look_from.ndim == 2 else look_from.reshape(1, 3).expand(bs, 3)
+
+
+def image(out):
+    """Kernel image ([BS,]W,H,K) -> user image ([BS,]K,H,W), H flipped, contiguous (VR.py:513,523). A projection's
+    ([BS,]W,H) is K = 1: image(out.unsqueeze(-1))."""
+    return torch.flip(out, (-2,)).transpose(-1, -3).contiguous()
+
+
+def unbatch(t, batched):
+    """The (views, ...) result of the functional calls as the caller's ([BS,] ...)."""
+    return t if batched else t[0]
+
+
+def diff_rays(volume, look_from, jitter, output_shape, sampling_rate, fov, near):
+    """What the autograd forwards do before their march -> (volume, cam, seed, (entry, exit, rays, n)): the volume as the kernels
+    read it, the cameras (views,3), the jitter seed drawn for this forward (0: none) and the ray buffers of ray_setup."""
+    cam = look_from.reshape(-1, 3)
+    volume = F.as_volume(volume)
+    seed = F.new_jitter_seed() if jitter else 0
+    return volume, cam, seed, F.ray_setup(cam, output_shape, volume.shape[-3:], sampling_rate, fov, near, seed)
+
+
+@contextlib.contextmanager
+def nondiff_rays(volume, look_from, sampling_rate, module_rate, output_shape, fov, near):
+    """The scope and preamble of every raycast_nondiff (VR.py:490-523): no autograd, no autocast, the default rate of 4x the
+    module's, never jittered. Yields (sampling_rate, volume, cam, (entry, exit, rays, n)) for the march inside the scope."""
+    with torch.no_grad(), torch.autocast("cuda", enabled=False):
+        sr = sampling_rate if sampling_rate is not None else 4.0 * module_rate
+        volume = F.as_volume(volume)
+        cam = look_from.reshape(-1, 3).float()
+        yield sr, volume, cam, F.ray_setup(cam, output_shape, volume.shape[-3:], sr, fov, near, 0)
+
+
+class RayModule(torch.nn.Module):
+    """What Raycaster2D, Projector and RaycasterRGBA keep alike: the volume shape in field order, the image shape, the sampling
+    options and the camera. (Raycaster keeps the reference's attributes and its VolumeRaycaster instead.)"""
+
+    def __init__(self, volume_shape, output_shape, sampling_rate, jitter, max_samples, fov, near, far):
+        super().__init__()
+        self.volume_shape = (volume_shape[2], volume_shape[0], volume_shape[1])  # (W, D, H), as Raycaster
+        self.output_shape = tuple(output_shape)
+        self.sampling_rate = sampling_rate
+        self.jitter = jitter
+        self.max_samples = max_samples
+        self.fov, self.near, self.far = fov, near, far
+        self._steps = None
+        N.lib()  # fail loudly at construction time if the HIP library is missing
+
+    def _check_built_for(self, volume):
+        """The (D, H, W) of a user volume ([BS,]C,D,H,W) against the shape the module was built for."""
+        w, d, h = self.volume_shape
+        if tuple(volume.shape[-3:]) != (d, h, w):
+            raise ValueError(f"volume has (D, H, W) = {tuple(volume.shape[-3:])}, the module was built for {(d, h, w)}")
+
+    def _nondiff_rays(self, volume, look_from, sampling_rate):
+        return nondiff_rays(volume, look_from, sampling_rate, self.sampling_rate, self.output_shape, self.fov, self.near)
+
+    @staticmethod
+    def _image(out, batched):
+        """([BS,]W,H,4) -> ([BS,]4,H,W); `batched` restates out's rank."""
+        return image(out)

@@ -47,6 +47,19 @@ struct DeviceOf {
     }
     ~DeviceOf() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// The end of an entry whose arguments have passed their checks: switch to the device that owns device_ptr, then call the
+// launch function -- a weak symbol (dr_kernels.h), null in a library linked without that kernel's object.
+template <typename... Params, typename... Args>
+int launch_on(const void *device_ptr, int (*launch)(Params...), Args &&...args) {
+    DeviceOf guard(device_ptr);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    if (!launch) return DR_EUNSUPPORTED;
+    return launch(args...);
+}
+
+// the W buffer rows are rows [row0, row0 + W) of an image of img_W rows
+bool band_fits(int W, int img_W, int row0) { return row0 >= 0 && img_W >= W && row0 <= img_W - W; }
 }  // namespace
 
 extern "C" {
@@ -87,7 +100,7 @@ int dr_ray_setup_rows(const float *cam, int n_views, int W, int H, int img_W, in
     if (!cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
     if (n_views <= 0 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
     if (n_views > 65535 || !(sampling_rate > 0.0f)) return DR_EINVAL;
-    if (row0 < 0 || img_W < W || row0 > img_W - W) return DR_EINVAL;
+    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
     DeviceOf guard(entry);
     if (guard.err != hipSuccess) return (int)guard.err;
     return (int)launch_ray_setup(cam, n_views, W, H, img_W, row0, VX, VY, VZ, fov_rad, near_plane, sampling_rate,
@@ -101,21 +114,37 @@ int dr_ray_setup(const float *cam, int n_views, int W, int H, int VX, int VY, in
                              view_base, entry, exit_, rays, nsamp, stream);
 }
 
+// What every entry that takes ray buffers checks before any HIP call, and the MarchArgs fields they all set: the volume, the
+// ray buffers and the extents. min_samples: the lowest max_samples the caller's kernels accept; finite_rate: sampling_rate
+// must be finite as well as > 0. No table (R = RG = 1) and the whole image (img_W = W, row0 = 0) until the caller says
+// otherwise.
+static int fill_rays(MarchArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                     int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                     const int32_t *nsamp, int n_views, int W, int H, int max_samples, int min_samples, float sampling_rate,
+                     bool finite_rate) {
+    if (!vol || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
+    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
+    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
+    if (max_samples < min_samples || !(sampling_rate > 0.0f) || (finite_rate && !std::isfinite(sampling_rate))) return DR_EINVAL;
+    a = MarchArgs{};
+    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
+    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
+    a.R = 1; a.RG = 1;
+    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
+    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate; a.img_W = W; a.row0 = 0;
+    return 0;
+}
+
+// fill_rays and the 1-D table (the 2-D TF entries add their second axis in fill_tf2d)
 static int fill_common(MarchArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
                        int64_t sz, int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride,
                        const float *cam, const float *entry, const float *exit_, const float *rays,
                        const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate) {
-    if (!vol || !tf || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
-    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
-    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2 || R < 1) return DR_EINVAL;
-    if (max_samples < 0 || !(sampling_rate > 0.0f)) return DR_EINVAL;
-    if (tf_view_stride % 4 != 0) return DR_EINVAL;
-    a = MarchArgs{};
-    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
-    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
-    a.tf = tf; a.R = R; a.tf_vs = tf_view_stride; a.RG = 1;
-    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
-    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate;
+    const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                             W, H, max_samples, 0, sampling_rate, false);
+    if (rc) return rc;
+    if (!tf || R < 1 || tf_view_stride % 4 != 0) return DR_EINVAL;
+    a.tf = tf; a.R = R; a.tf_vs = tf_view_stride;
     return 0;
 }
 
@@ -143,7 +172,7 @@ int dr_march_fwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
                          entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
     if (!out_rgba) return DR_EINVAL;
-    if (row0 < 0 || img_W < W || row0 > img_W - W) return DR_EINVAL;
+    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
     a.img_W = img_W; a.row0 = row0;
     if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
     const int hints = variant & ~0xff;
@@ -202,7 +231,7 @@ int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     if (rc) return rc;
     rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf, dtf_view_stride);
     if (rc) return rc;
-    if (row0 < 0 || img_W < W || row0 > img_W - W) return DR_EINVAL;
+    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
     a.img_W = img_W; a.row0 = row0;
     const int bwd_flags = variant & ~0xff;
     variant &= 0xff;
@@ -247,16 +276,13 @@ int dr_march_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int
                          entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
     if (!steps || !grad_out || !out_rgba || !d_cam) return DR_EINVAL;
-    if (row0 < 0 || img_W < W || row0 > img_W - W) return DR_EINVAL;
+    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
     if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
     a.img_W = img_W; a.row0 = row0; a.mode = DR_MODE_DIFF;
     a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
-    if (!launch_camera_grad) return DR_EUNSUPPORTED;   // (a library linked without camera_grad.o)
     CamArgs c;
     c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
-    return launch_camera_grad(a, c, (hipStream_t)stream);
+    return launch_on(vol, launch_camera_grad, a, c, (hipStream_t)stream);
 }
 
 int dr_mse_loss_grad(const float *out_rgba, const float *reference, int64_t n, float inv_norm, float *grad_out,
@@ -294,10 +320,7 @@ int dr_dssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W,
     LossArgs a;
     int rc = fill_loss(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, flags, stats);
     if (rc) return rc;
-    DeviceOf guard(x);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_dssim_mse_fwd) return DR_EUNSUPPORTED;   // (a library linked without image_loss.o)
-    return launch_dssim_mse_fwd(a, (hipStream_t)stream);
+    return launch_on(x, launch_dssim_mse_fwd, a, (hipStream_t)stream);
 }
 
 int dr_dssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
@@ -309,10 +332,7 @@ int dr_dssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W,
     if (rc) return rc;
     if (!grad_x) return DR_EINVAL;
     a.upstream = upstream3; a.grad_x = grad_x; a.grad_y = grad_y;
-    DeviceOf guard(x);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_dssim_mse_bwd) return DR_EUNSUPPORTED;
-    return launch_dssim_mse_bwd(a, (hipStream_t)stream);
+    return launch_on(x, launch_dssim_mse_bwd, a, (hipStream_t)stream);
 }
 
 static_assert(MS_MAX_LEVELS == DR_MSSSIM_MAX_LEVELS, "dr_kernels.h and the public header disagree on the MS-SSIM levels");
@@ -349,10 +369,7 @@ int dr_msssim_mse_fwd(const float *x, const float *y, int N, int C, int H, int W
     int rc = fill_msssim(a, x, y, N, C, H, W, strides4, data_range, win_size, win_sigma, K1, K2, weights, levels, workspace,
                          stats);
     if (rc) return rc;
-    DeviceOf guard(x);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_msssim_mse_fwd) return DR_EUNSUPPORTED;   // (a library linked without msssim.o)
-    return launch_msssim_mse_fwd(a, (hipStream_t)stream);
+    return launch_on(x, launch_msssim_mse_fwd, a, (hipStream_t)stream);
 }
 
 int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W, const int64_t *strides4, double data_range,
@@ -365,10 +382,7 @@ int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W
     if (rc) return rc;
     if (!grad_x) return DR_EINVAL;
     a.upstream = upstream3; a.grad_x = grad_x; a.grad_y = grad_y;
-    DeviceOf guard(x);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_msssim_mse_bwd) return DR_EUNSUPPORTED;
-    return launch_msssim_mse_bwd(a, (hipStream_t)stream);
+    return launch_on(x, launch_msssim_mse_bwd, a, (hipStream_t)stream);
 }
 
 static int fill_tv(TVArgs &a, const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4, int norm,
@@ -392,10 +406,7 @@ int dr_tv3d_fwd(const void *vol, int vol_dtype, int B, int D, int H, int W, cons
     if (rc) return rc;
     if (!sum) return DR_EINVAL;
     a.sum = sum;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_tv3d_fwd) return DR_EUNSUPPORTED;   // (a library linked without tv_loss.o)
-    return launch_tv3d_fwd(a, (hipStream_t)stream);
+    return launch_on(vol, launch_tv3d_fwd, a, (hipStream_t)stream);
 }
 
 int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4, int norm, double eps,
@@ -406,10 +417,7 @@ int dr_tv3d_bwd(const void *vol, int vol_dtype, int B, int D, int H, int W, cons
     if (!grad || !grad_strides4 || !std::isfinite(scale)) return DR_EINVAL;
     a.upstream = upstream; a.scale = scale; a.grad = grad; a.accumulate = accumulate != 0;
     for (int i = 0; i < 4; ++i) a.grad_strides[i] = grad_strides4[i];
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_tv3d_bwd) return DR_EUNSUPPORTED;
-    return launch_tv3d_bwd(a, (hipStream_t)stream);
+    return launch_on(vol, launch_tv3d_bwd, a, (hipStream_t)stream);
 }
 
 // fill_common with R = RV, and what only the 2-D TF checks: the texel index RV * RG stays below 2^31, g_scale
@@ -438,10 +446,7 @@ int dr_march_tf2d_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     if (!out_rgba) return DR_EINVAL;
     if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
     a.mode = mode; a.out = out_rgba; a.steps = steps;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_march_tf2d_fwd) return DR_EUNSUPPORTED;   // (a library linked without march_tf2d.o)
-    return launch_march_tf2d_fwd(a, (hipStream_t)stream);
+    return launch_on(vol, launch_march_tf2d_fwd, a, (hipStream_t)stream);
 }
 
 int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
@@ -457,26 +462,16 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf2d, dtf_view_stride);
     if (rc) return rc;
     if (!d_vol && !d_tf2d) return 0;  // nothing requested
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_march_tf2d_bwd) return DR_EUNSUPPORTED;
-    return launch_march_tf2d_bwd(a, (hipStream_t)stream);
+    return launch_on(vol, launch_march_tf2d_bwd, a, (hipStream_t)stream);
 }
 
 // what the two RGBA-volume entries check before any HIP call, and the MarchArgs they share
 static int fill_rgba(MarchArgs &a, RgbaArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
                      int64_t sz, int64_t sc, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,
                      const float *rays, const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate) {
-    if (!vol || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
-    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
-    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
-    if (max_samples < 1 || !std::isfinite(sampling_rate) || !(sampling_rate > 0.0f)) return DR_EINVAL;
-    a = MarchArgs{};
-    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
-    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
-    a.R = 1; a.RG = 1;
-    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
-    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.sr = sampling_rate; a.img_W = W;
+    const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                             W, H, max_samples, 1, sampling_rate, true);
+    if (rc) return rc;
     q = RgbaArgs{};
     q.sc = sc;
     return 0;
@@ -494,10 +489,7 @@ int dr_march_rgba_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     if (!out_rgba) return DR_EINVAL;
     if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
     a.mode = mode; a.out = out_rgba; a.steps = steps;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_march_rgba_fwd) return DR_EUNSUPPORTED;   // (a library linked without march_rgba.o)
-    return launch_march_rgba_fwd(a, q, (hipStream_t)stream);
+    return launch_on(vol, launch_march_rgba_fwd, a, q, (hipStream_t)stream);
 }
 
 int dr_march_rgba_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
@@ -516,30 +508,20 @@ int dr_march_rgba_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     a.grad_out = grad_out; a.out_fwd = out_rgba;
     a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
     q.dsc = dsc;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_march_rgba_bwd) return DR_EUNSUPPORTED;
-    return launch_march_rgba_bwd(a, q, (hipStream_t)stream);
+    return launch_on(vol, launch_march_rgba_bwd, a, q, (hipStream_t)stream);
 }
 
-// what the three projection entries check: fill_common's volume and ray checks without a table, max_samples >= 1, the mode,
-// and arg_max for DR_PROJ_MAX
+// what the three projection entries check: fill_rays at the projections' fixed rate of 1 with max_samples >= 1, the mode, and
+// arg_max for DR_PROJ_MAX
 static int fill_proj(MarchArgs &a, ProjArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
                      int64_t sz, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,
                      const float *rays, const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
                      const int32_t *arg_max) {
-    if (!vol || !cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
-    if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
-    if (n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
-    if (max_samples < 1) return DR_EINVAL;
+    const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                             W, H, max_samples, 1, 1.0f, false);
+    if (rc) return rc;
     if (mode != DR_PROJ_SUM && mode != DR_PROJ_MAX) return DR_EINVAL;
     if (mode == DR_PROJ_MAX && !arg_max) return DR_EINVAL;
-    a = MarchArgs{};
-    a.vol = vol; a.vol_dtype = vol_dtype; a.VX = VX; a.VY = VY; a.VZ = VZ;
-    a.sx = sx; a.sy = sy; a.sz = sz; a.vol_vs = vol_view_stride;
-    a.R = 1; a.RG = 1; a.sr = 1.0f;
-    a.cam = cam; a.entry = entry; a.exit_ = exit_; a.rays = rays; a.nsamp = nsamp;
-    a.n_views = n_views; a.W = W; a.H = H; a.S = max_samples; a.img_W = W;
     q = ProjArgs{};
     q.mode = mode; q.variant = DR_VARIANT_AUTO; q.arg_max = const_cast<int32_t *>(arg_max);
     return 0;
@@ -556,10 +538,7 @@ int dr_project_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64
     if (rc) return rc;
     if (!out) return DR_EINVAL;
     a.out = out;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_project_fwd) return DR_EUNSUPPORTED;   // (a library linked without projection.o)
-    return launch_project_fwd(a, q, (hipStream_t)stream);
+    return launch_on(vol, launch_project_fwd, a, q, (hipStream_t)stream);
 }
 
 int dr_project_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
@@ -578,10 +557,7 @@ int dr_project_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64
     a.grad_out = grad_out; a.mode = DR_MODE_DIFF;
     a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
     q.variant = variant;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_project_bwd) return DR_EUNSUPPORTED;
-    return launch_project_bwd(a, q, (hipStream_t)stream);
+    return launch_on(vol, launch_project_bwd, a, q, (hipStream_t)stream);
 }
 
 int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
@@ -598,10 +574,7 @@ int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, i
     if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
     a.grad_out = grad_out; a.mode = DR_MODE_DIFF; a.fov_rad = fov_rad; a.near_plane = near_plane;
     q.jitter_seed = jitter_seed; q.view_base = view_base; q.d_cam = d_cam; q.d_cam_ray = d_cam_ray;
-    DeviceOf guard(vol);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    if (!launch_project_bwd_cam) return DR_EUNSUPPORTED;
-    return launch_project_bwd_cam(a, q, (hipStream_t)stream);
+    return launch_on(vol, launch_project_bwd_cam, a, q, (hipStream_t)stream);
 }
 
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,

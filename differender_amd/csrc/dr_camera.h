@@ -91,4 +91,48 @@ __device__ __forceinline__ void slab_rows(f3 lf, f3 vd, const M3 &J, f3 &g_tmin,
     g_tmax = slab_grad(amax, tmax, ivmax, J);
 }
 
+// The near-plane extents of VR.py:146-147 as ray_setup.hip forms them: doubles, rounded once (host side of the two camera
+// backwards; img_W: the rows of the whole image, of which a band call renders W).
+inline void near_plane_extents(double fov_rad, double near_plane, int img_W, int H, float &near_, float &near_w, float &near_h) {
+    const double h = 2.0 * tan(fov_rad) * near_plane;
+    const double w = h * ((double)img_W / (double)H);
+    near_ = (float)near_plane; near_w = (float)w; near_h = (float)h;
+}
+
+// Once per ray: J = d vd / d look_from and the rows of the slab faces the forward picked (VR.py:28-53, same arithmetic as
+// ray_setup.hip), the jitter draw u, and grad t0 = A grad tmin + (1-A) grad tmax, A = (1 - u/n)(1 - 0.5/n). row: the pixel's
+// row within the whole image of img_W rows (a band adds its row0), j its column of H.
+__device__ __forceinline__ void camera_ray_tail(f3 lf, f3 vd, int row, int img_W, int j, int H, float near_, float near_w,
+                                                float near_h, int n, uint32_t jitter_seed, uint32_t view, M3 &J, f3 &g_tmin,
+                                                f3 &g_tmax, f3 &g_t0, float &u) {
+    const float x = ((float)row + 0.5f) / (float)img_W;
+    const float y = ((float)j + 0.5f) / (float)H;
+    J = ray_dir_jacobian(lf, near_, (x - 0.5f) * near_w, (y - 0.5f) * near_h);
+    slab_rows(lf, vd, J, g_tmin, g_tmax);
+    const float nf = (float)n;
+    u = jitter_seed != 0u ? jitter_u(jitter_seed, view, (uint32_t)(row * H + j)) : 0.0f;
+    const float Acoef = (1.0f - u / nf) * (1.0f - 0.5f / nf);
+    g_t0 = f3_fma(Acoef, g_tmin, f3_scale(1.0f - Acoef, g_tmax));
+}
+
+// The end of both camera backwards (256 lanes, every lane arrives): the optional per-ray store, then the workgroup's sum in
+// double (LDS tree) and ONE f64 atomic per component into d_cam[view][3]. p: the ray's index, read only where in_img.
+__device__ __forceinline__ void camera_reduce(f3 dcam, bool in_img, size_t p, int view, float *d_cam_ray, double *d_cam,
+                                              double (&red)[3][256]) {
+    if (in_img && d_cam_ray) {
+        d_cam_ray[3 * p] = dcam.x; d_cam_ray[3 * p + 1] = dcam.y; d_cam_ray[3 * p + 2] = dcam.z;
+    }
+    red[0][threadIdx.x] = (double)dcam.x; red[1][threadIdx.x] = (double)dcam.y; red[2][threadIdx.x] = (double)dcam.z;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+            red[2][threadIdx.x] += red[2][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3 && red[threadIdx.x][0] != 0.0) atomicAdd(d_cam + 3 * view + threadIdx.x, red[threadIdx.x][0]);
+}
+
 }  // namespace dr

@@ -303,16 +303,13 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
             s0 = fmaf(1.0f - f, gv, s0);
             s1 = fmaf(f, gv, s1);
         }
-        // once per ray: J_vd and the rows of the slab faces the forward picked
-        const float x = ((float)i + 0.5f) / (float)P.W;
-        const float y = ((float)j + 0.5f) / (float)P.H;
-        const M3 J = ray_dir_jacobian(lf, P.near_, (x - 0.5f) * P.near_w, (y - 0.5f) * P.near_h);
-        f3 g_tmin, g_tmax;
-        slab_rows(lf, vd, J, g_tmin, g_tmax);
+        // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw (a projection is never a band)
+        M3 J;
+        f3 g_tmin, g_tmax, g_t0;
+        float u;
+        camera_ray_tail(lf, vd, i, P.W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed, P.view_base + (uint32_t)view, J,
+                        g_tmin, g_tmax, g_t0, u);
         const float nf = (float)rg.n;
-        const float u = P.jitter_seed != 0u ? jitter_u(P.jitter_seed, P.view_base + (uint32_t)view, (uint32_t)(i * P.H + j)) : 0.0f;
-        const float Acoef = (1.0f - u / nf) * (1.0f - 0.5f / nf);
-        const f3 g_t0 = f3_fma(Acoef, g_tmin, f3_scale(1.0f - Acoef, g_tmax));
         f3 dpos = f3_add(sP, mul_t(J, sTP));
         dpos = f3_fma(s0, g_t0, dpos);
         dpos = f3_fma(s1, g_tmax, dpos);
@@ -324,30 +321,14 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
         // D5: a NaN ray contributes nothing, infinities are clamped
         dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
     }
-    if (in_img && P.d_cam_ray) {
-        P.d_cam_ray[3 * p] = dcam.x; P.d_cam_ray[3 * p + 1] = dcam.y; P.d_cam_ray[3 * p + 2] = dcam.z;
-    }
-    red[0][threadIdx.x] = (double)dcam.x; red[1][threadIdx.x] = (double)dcam.y; red[2][threadIdx.x] = (double)dcam.z;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-            red[2][threadIdx.x] += red[2][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 3 && red[threadIdx.x][0] != 0.0) atomicAdd(P.d_cam + 3 * view + threadIdx.x, red[threadIdx.x][0]);
+    camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
 }
 
 template <typename VT>
 static ProjParams<VT> proj_params(const MarchArgs &a, const ProjArgs &q) {
     ProjParams<VT> P{make_ray_params<VT>(a)};
     P.arg_max = q.arg_max;
-    // VR.py:146-147 as ray_setup.hip forms them: doubles, rounded once
-    const double near_h = 2.0 * tan(a.fov_rad) * a.near_plane;
-    const double near_w = near_h * ((double)a.W / (double)a.H);
-    P.near_ = (float)a.near_plane; P.near_w = (float)near_w; P.near_h = (float)near_h;
+    near_plane_extents(a.fov_rad, a.near_plane, a.img_W, a.H, P.near_, P.near_w, P.near_h);   // (fill_proj: img_W = W)
     P.jitter_seed = q.jitter_seed; P.view_base = q.view_base;
     P.d_cam = q.d_cam; P.d_cam_ray = q.d_cam_ray;
     return P;

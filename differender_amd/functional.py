@@ -53,14 +53,22 @@ def bwd_is_sanitised(vol, tf, d_vol, workspace, n):
                                         int(d_vol is not None), N.DR_VARIANT_AUTO, 1) == N.DR_VARIANT_AUTO
 
 
+def _dtype_tag(vol, rule):
+    """DR_F32 / DR_F16 of a volume the kernels read as it is; `rule` words the TypeError of any other dtype."""
+    if vol.dtype == torch.float32:
+        return N.DR_F32
+    if vol.dtype == torch.float16:
+        return N.DR_F16
+    raise TypeError(f"{rule}, got {vol.dtype}")
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 def _vol_args(vol, n_views):
     """-> (ptr, dtype_tag, VX, VY, VZ, sx, sy, sz, view_stride)"""
-    if vol.dtype == torch.float32:
-        tag = N.DR_F32
-    elif vol.dtype == torch.float16:
-        tag = N.DR_F16
-    else:
-        raise TypeError(f"volume dtype must be float32 or float16, got {vol.dtype}")
+    tag = _dtype_tag(vol, "volume dtype must be float32 or float16")
     if vol.ndim == 3:
         vs, (VX, VY, VZ), (sx, sy, sz) = 0, vol.shape, vol.stride()
     elif vol.ndim == 4:
@@ -172,6 +180,40 @@ def ray_setup(cam, out_shape, vol_shape, sampling_rate, fov_deg=30.0, near=0.1, 
                                        entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), _stream())
     N.check(rc, "dr_ray_setup_rows")
     return entry, exit_, rays, n
+
+
+def _ray_args(vol, cam, entry, exit_, rays, n):
+    """What every call on ray buffers starts with -> (cam, V, W, H, args): the camera as the float32 contiguous tensor the kernels
+    read, the extents of the (views, W, H) ray buffers, and the eight C-ABI arguments cam, entry, exit, rays, n, V, W, H. The
+    caller keeps `cam` (a temporary when it had to be converted) until its call has been issued."""
+    _require_gpu(vol, "volume")
+    V, W, H = n.shape
+    cam = cam.to(torch.float32).contiguous()
+    return cam, V, W, H, (cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), V, W, H)
+
+
+def _fwd_buffers(V, W, H, device, want_steps):
+    """A march forward's out (views,W,H,4) float32 and steps (views,W,H) int32 (None when not wanted)."""
+    out = torch.empty((V, W, H, 4), dtype=torch.float32, device=device)
+    return out, torch.empty((V, W, H), dtype=torch.int32, device=device) if want_steps else None
+
+
+def _bwd_images(grad_out, out):
+    """A march backward's upstream gradient and forward image as the kernels read them: float32, contiguous."""
+    return grad_out.to(torch.float32).contiguous(), out.contiguous()
+
+
+def _cam_grad_buffers(V, W, H, device, per_ray):
+    """A camera backward's d_cam (views, 3), zeros in float64 for the workgroups' atomics, and the per-ray d_ray (views,W,H,3)
+    float32 (None when not wanted)."""
+    d_cam = torch.zeros((V, 3), dtype=torch.float64, device=device)
+    return d_cam, torch.empty((V, W, H, 3), dtype=torch.float32, device=device) if per_ray else None
+
+
+def _cam_grad_result(d_cam, d_ray):
+    """What a camera backward returns. D5: a sum beyond the float range saturates, as nan_to_num makes of d_tf."""
+    d_cam = torch.nan_to_num(d_cam.float())
+    return d_cam if d_ray is None else (d_cam, d_ray)
 
 
 class _TerminationHints:
@@ -336,12 +378,9 @@ def march_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, m
     hints: "auto" (DR_HINT_* from the TF's largest alpha once it is known, see _TerminationHints), 0 / None, or explicit bits.
     tape: DR_TAPE_TF -- the caller will ask for the TF gradient only (march_bwd(want_vol=False, tape=True)); the workspace must come
     from alloc_workspace(..., tape=(max_samples, sampling_rate)). Differentiable mode only; same image."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
     dev = vol.device
-    cam = cam.to(torch.float32).contiguous()
-    out = torch.empty((V, W, H, 4), dtype=torch.float32, device=dev)
-    steps = torch.empty((V, W, H), dtype=torch.int32, device=dev) if want_steps else None
+    out, steps = _fwd_buffers(V, W, H, dev, want_steps)
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
     if isinstance(workspace, str):
@@ -349,12 +388,10 @@ def march_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, m
     if isinstance(hints, str):
         hints = _hints.hints(tf, vargs[2:5], sampling_rate, max_samples, mode) if variant == N.DR_VARIANT_AUTO else 0
     with torch.cuda.device(dev):
-        rc = N.lib().dr_march_fwd_rows(*vargs, targs[0], targs[1], targs[2], cam.data_ptr(), entry.data_ptr(),
-                                       exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), V, W, H, int(max_samples),
-                                       float(sampling_rate), float(np.radians(fov_deg)), float(near), int(mode),
+        rc = N.lib().dr_march_fwd_rows(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
+                                       float(np.radians(fov_deg)), float(near), int(mode),
                                        int(variant) | int(hints or 0) | (N.DR_TAPE_TF if tape else 0), out.data_ptr(),
-                                       steps.data_ptr() if want_steps else None,
-                                       *_ws_args(workspace), *_rows(rows, W), _stream())
+                                       _ptr(steps), *_ws_args(workspace), *_rows(rows, W), _stream())
     N.check(rc, "dr_march_fwd_rows")
     return out, steps
 
@@ -380,11 +417,8 @@ def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, g
     tape: the forward was run with tape=True and only d_tf is wanted: the per-ray pass over the tape (csrc/tf_tape.hip)."""
     if tape and want_vol:
         raise ValueError("tape=True serves the backward w.r.t. the transfer function alone (want_vol=False)")
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
-    cam = cam.to(torch.float32).contiguous()
-    grad_out = grad_out.to(torch.float32).contiguous()
-    out = out.contiguous()
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
     d_vol, dv = _d_vol(vol, want_vol)
@@ -396,9 +430,8 @@ def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, g
     if not (want_vol or want_tf):
         return None, None
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_bwd_rows(*vargs, targs[0], targs[1], targs[2], cam.data_ptr(), entry.data_ptr(),
-                                       exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), V, W, H, int(max_samples),
-                                       float(sampling_rate), float(np.radians(fov_deg)), float(near),
+        rc = N.lib().dr_march_bwd_rows(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
+                                       float(np.radians(fov_deg)), float(near),
                                        int(variant) | (N.DR_COUNT_EVALUATED if count_evaluated else 0) | (N.DR_TAPE_TF if tape else 0),
                                        grad_out.data_ptr(), out.data_ptr(), *dv, *dt, *_ws_args(workspace),
                                        *_rows(rows, W), _stream())
@@ -412,26 +445,19 @@ def march_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampl
     reference has none, VR.py:465). The ray buffers, `steps`, `out`, jitter_seed, view_base and rows are those of the forward
     (ray_setup + march_fwd). Returns d_cam (views, 3) float32 -- and, with per_ray=True, each ray's contribution
     (views, W, H, 3) float32 as well."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
-    cam = cam.to(torch.float32).contiguous()
-    grad_out = grad_out.to(torch.float32).contiguous()
-    out = out.contiguous()
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
     steps = steps.to(torch.int32).contiguous()
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
-    d_cam = torch.zeros((V, 3), dtype=torch.float64, device=vol.device)
-    d_ray = torch.empty((V, W, H, 3), dtype=torch.float32, device=vol.device) if per_ray else None
+    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_bwd_cam(*vargs, targs[0], targs[1], targs[2], cam.data_ptr(), entry.data_ptr(),
-                                      exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), V, W, H, int(max_samples),
-                                      float(sampling_rate), float(np.radians(fov_deg)), float(near),
-                                      int(jitter_seed) & 0xFFFFFFFF, int(view_base), *_rows(rows, W), steps.data_ptr(),
-                                      grad_out.data_ptr(), out.data_ptr(), d_cam.data_ptr(),
-                                      d_ray.data_ptr() if per_ray else None, _stream())
+        rc = N.lib().dr_march_bwd_cam(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
+                                      float(np.radians(fov_deg)), float(near), int(jitter_seed) & 0xFFFFFFFF, int(view_base),
+                                      *_rows(rows, W), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(), d_cam.data_ptr(),
+                                      _ptr(d_ray), _stream())
     N.check(rc, "dr_march_bwd_cam")
-    d_cam = torch.nan_to_num(d_cam.float())   # D5: a sum beyond the float range saturates, as nan_to_num makes of d_tf
-    return (d_cam, d_ray) if per_ray else d_cam
+    return _cam_grad_result(d_cam, d_ray)
 
 
 def _tf2d_args(tf2d, n_views):
@@ -457,18 +483,13 @@ def march_tf2d_fwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
     classification rgba = T[I (RV-1), u (RG-1)] (bilinear, value axis first), u = |central-difference taps| * g_scale.
     tf2d: (RV, RG, 4) shared or (views, RV, RG, 4) float32 contiguous. Returns out (views,W,H,4) and steps (views,W,H) int32
     (or None). A (RV, 1) table gives march_fwd's bits with the 1-D TF of RV entries."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
-    dev = vol.device
-    cam = cam.to(torch.float32).contiguous()
-    out = torch.empty((V, W, H, 4), dtype=torch.float32, device=dev)
-    steps = torch.empty((V, W, H), dtype=torch.int32, device=dev) if want_steps else None
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    out, steps = _fwd_buffers(V, W, H, vol.device, want_steps)
     vargs = _vol_args(vol, V)
     targs = _tf2d_args(tf2d, V)
-    with torch.cuda.device(dev):
-        rc = N.lib().dr_march_tf2d_fwd(*vargs, *targs, _g_scale(g_scale), cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(),
-                                       rays.data_ptr(), n.data_ptr(), V, W, H, int(max_samples), float(sampling_rate), int(mode),
-                                       out.data_ptr(), steps.data_ptr() if want_steps else None, _stream())
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_march_tf2d_fwd(*vargs, *targs, _g_scale(g_scale), *rargs, int(max_samples), float(sampling_rate),
+                                       int(mode), out.data_ptr(), _ptr(steps), _stream())
     N.check(rc, "dr_march_tf2d_fwd")
     return out, steps
 
@@ -478,11 +499,8 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
     """Adjoint of the differentiable march_tf2d_fwd w.r.t. vol and tf2d (dr_march_tf2d_bwd). Returns (d_vol, d_tf2d), either
     None when not wanted; a shared (un-batched) vol / tf2d receives one gradient accumulated over all views. NaN propagates (the
     plain kernels' convention: the caller applies nan_to_num, as tf2d.Raycaster2D does)."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
-    cam = cam.to(torch.float32).contiguous()
-    grad_out = grad_out.to(torch.float32).contiguous()
-    out = out.contiguous()
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
     vargs = _vol_args(vol, V)
     targs = _tf2d_args(tf2d, V)
     g = _g_scale(g_scale)
@@ -495,8 +513,7 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
         d_tf = torch.zeros_like(tf2d)
         dt = (d_tf.data_ptr(), d_tf.stride(0) if tf2d.ndim == 4 else 0)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_tf2d_bwd(*vargs, *targs, g, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(),
-                                       n.data_ptr(), V, W, H, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
+        rc = N.lib().dr_march_tf2d_bwd(*vargs, *targs, g, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
                                        out.data_ptr(), *dv, *dt, _stream())
     N.check(rc, "dr_march_tf2d_bwd")
     return d_vol, d_tf
@@ -504,12 +521,7 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
 
 def _vol4_args(vol4, n_views):
     """-> (ptr, dtype_tag, VX, VY, VZ, sx, sy, sz, sc, view_stride) of an RGBA volume ([views,] 4, VX, VY, VZ), any strides"""
-    if vol4.dtype == torch.float32:
-        tag = N.DR_F32
-    elif vol4.dtype == torch.float16:
-        tag = N.DR_F16
-    else:
-        raise TypeError(f"RGBA volume dtype must be float32 or float16, got {vol4.dtype}")
+    tag = _dtype_tag(vol4, "RGBA volume dtype must be float32 or float16")
     if vol4.ndim not in (4, 5) or vol4.shape[-4] != 4:
         raise ValueError(f"RGBA volume must be (4,VX,VY,VZ) or (views,4,VX,VY,VZ), got {tuple(vol4.shape)}")
     if vol4.ndim == 5 and vol4.shape[0] != n_views:
@@ -524,17 +536,12 @@ def march_rgba_fwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate,
     no shading. vol4: (4, VX, VY, VZ) shared or (views, 4, VX, VY, VZ), float32 or float16, any strides, never copied (with the
     channel axis at stride 1 -- rgba.interleaved() -- a voxel is one load). Returns out (views,W,H,4) and steps (views,W,H) int32
     (or None)."""
-    _require_gpu(vol4, "volume")
-    V, W, H = n.shape
-    dev = vol4.device
-    cam = cam.to(torch.float32).contiguous()
+    cam, V, W, H, rargs = _ray_args(vol4, cam, entry, exit_, rays, n)
     vargs = _vol4_args(vol4, V)
-    out = torch.empty((V, W, H, 4), dtype=torch.float32, device=dev)
-    steps = torch.empty((V, W, H), dtype=torch.int32, device=dev) if want_steps else None
-    with torch.cuda.device(dev):
-        rc = N.lib().dr_march_rgba_fwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
-                                       V, W, H, int(max_samples), float(sampling_rate), int(mode), out.data_ptr(),
-                                       steps.data_ptr() if want_steps else None, _stream())
+    out, steps = _fwd_buffers(V, W, H, vol4.device, want_steps)
+    with torch.cuda.device(vol4.device):
+        rc = N.lib().dr_march_rgba_fwd(*vargs, *rargs, int(max_samples), float(sampling_rate), int(mode), out.data_ptr(),
+                                       _ptr(steps), _stream())
     N.check(rc, "dr_march_rgba_fwd")
     return out, steps
 
@@ -543,17 +550,13 @@ def march_rgba_bwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate,
     """d_vol of sum(march_rgba_fwd(...) * grad_out) (dr_march_rgba_bwd): float32, in vol4's own layout; a shared (un-batched)
     volume receives one gradient summed over the views. NaN propagates (the plain kernels' convention: the caller applies
     nan_to_num, as rgba.RaycasterRGBA does)."""
-    _require_gpu(vol4, "volume")
-    V, W, H = n.shape
-    cam = cam.to(torch.float32).contiguous()
-    grad_out = grad_out.to(torch.float32).contiguous()
-    out = out.contiguous()
+    cam, V, W, H, rargs = _ray_args(vol4, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
     vargs = _vol4_args(vol4, V)
     d_vol = torch.zeros_like(vol4, dtype=torch.float32, memory_format=torch.preserve_format)
     dc, dx, dy, dz = d_vol.stride()[-4:]
     with torch.cuda.device(vol4.device):
-        rc = N.lib().dr_march_rgba_bwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
-                                       V, W, H, int(max_samples), float(sampling_rate), grad_out.data_ptr(), out.data_ptr(),
+        rc = N.lib().dr_march_rgba_bwd(*vargs, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(), out.data_ptr(),
                                        d_vol.data_ptr(), dx, dy, dz, dc, d_vol.stride(0) if d_vol.ndim == 5 else 0, _stream())
     N.check(rc, "dr_march_rgba_bwd")
     return d_vol
@@ -575,22 +578,28 @@ def _max_samples(max_samples):
     return NO_SAMPLE_LIMIT if max_samples is None else int(max_samples)
 
 
+def _proj_bwd_args(max_samples, mode, arg_max):
+    """What both projection backwards make of their options -> (arg_max as the int32 contiguous tensor the kernels read, or
+    None; the C-ABI arguments max_samples, mode)."""
+    md = _proj_mode(mode)
+    if md == N.DR_PROJ_MAX and arg_max is None:
+        raise ValueError("mode 'max' needs the forward's arg_max")
+    arg = arg_max.to(torch.int32).contiguous() if arg_max is not None else None
+    return arg, (_max_samples(max_samples), md)
+
+
 def project_fwd(vol, cam, entry, exit_, rays, n, max_samples=None, mode="sum"):
     """X-ray line integral (mode "sum": D * sum of the trilinear samples, D = (exit - entry) / n) or maximum intensity projection
     ("max") of vol along the rays of ray_setup (dr_project_fwd). Returns out (views, W, H) float32 and, for "max",
     arg_max (views, W, H) int32, the index of the first maximal sample (-1: none) -- None for "sum". max_samples None: no limit."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
     dev = vol.device
     md = _proj_mode(mode)
-    cam = cam.to(torch.float32).contiguous()
     out = torch.empty((V, W, H), dtype=torch.float32, device=dev)
     arg = torch.empty((V, W, H), dtype=torch.int32, device=dev) if md == N.DR_PROJ_MAX else None
     vargs = _vol_args(vol, V)
     with torch.cuda.device(dev):
-        rc = N.lib().dr_project_fwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
-                                    V, W, H, _max_samples(max_samples), md, out.data_ptr(),
-                                    arg.data_ptr() if arg is not None else None, _stream())
+        rc = N.lib().dr_project_fwd(*vargs, *rargs, _max_samples(max_samples), md, out.data_ptr(), _ptr(arg), _stream())
     N.check(rc, "dr_project_fwd")
     return out, arg
 
@@ -600,20 +609,13 @@ def project_bwd(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None, mod
     """d_vol of sum(project_fwd(...) * grad_out) (dr_project_bwd): a back-projection. A shared (un-batched) vol receives one
     gradient summed over the views. variant DR_VARIANT_AUTO: the windowed "sum" kernel; DR_VARIANT_BASELINE: per-tap global
     atomics. "max" needs the forward's arg_max."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
-    md = _proj_mode(mode)
-    cam = cam.to(torch.float32).contiguous()
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    arg, pargs = _proj_bwd_args(max_samples, mode, arg_max)
     grad_out = grad_out.to(torch.float32).contiguous()
-    if md == N.DR_PROJ_MAX and arg_max is None:
-        raise ValueError("mode 'max' needs the forward's arg_max")
-    arg = arg_max.to(torch.int32).contiguous() if arg_max is not None else None
     vargs = _vol_args(vol, V)
     d_vol, dv = _d_vol(vol, True)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_project_bwd(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(),
-                                    V, W, H, _max_samples(max_samples), md, grad_out.data_ptr(),
-                                    arg.data_ptr() if arg is not None else None, *dv, int(variant), _stream())
+        rc = N.lib().dr_project_bwd(*vargs, *rargs, *pargs, grad_out.data_ptr(), _ptr(arg), *dv, int(variant), _stream())
     N.check(rc, "dr_project_bwd")
     return d_vol
 
@@ -623,26 +625,17 @@ def project_bwd_cam(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None,
     """d look_from of sum(project_fwd(...) * grad_out) (dr_project_bwd_cam): cam (views, 3), the ray buffers, jitter_seed and
     view_base those of the forward's ray_setup. Returns d_cam (views, 3) float32 -- and, with per_ray=True, each ray's
     contribution (views, W, H, 3) as well."""
-    _require_gpu(vol, "volume")
-    V, W, H = n.shape
-    md = _proj_mode(mode)
-    cam = cam.to(torch.float32).contiguous()
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    arg, pargs = _proj_bwd_args(max_samples, mode, arg_max)
     grad_out = grad_out.to(torch.float32).contiguous()
-    if md == N.DR_PROJ_MAX and arg_max is None:
-        raise ValueError("mode 'max' needs the forward's arg_max")
-    arg = arg_max.to(torch.int32).contiguous() if arg_max is not None else None
     vargs = _vol_args(vol, V)
-    d_cam = torch.zeros((V, 3), dtype=torch.float64, device=vol.device)
-    d_ray = torch.empty((V, W, H, 3), dtype=torch.float32, device=vol.device) if per_ray else None
+    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_project_bwd_cam(*vargs, cam.data_ptr(), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(),
-                                        n.data_ptr(), V, W, H, _max_samples(max_samples), md, float(np.radians(fov_deg)),
-                                        float(near), int(jitter_seed) & 0xFFFFFFFF, int(view_base), grad_out.data_ptr(),
-                                        arg.data_ptr() if arg is not None else None, d_cam.data_ptr(),
-                                        d_ray.data_ptr() if per_ray else None, _stream())
+        rc = N.lib().dr_project_bwd_cam(*vargs, *rargs, *pargs, float(np.radians(fov_deg)), float(near),
+                                        int(jitter_seed) & 0xFFFFFFFF, int(view_base), grad_out.data_ptr(), _ptr(arg),
+                                        d_cam.data_ptr(), _ptr(d_ray), _stream())
     N.check(rc, "dr_project_bwd_cam")
-    d_cam = torch.nan_to_num(d_cam.float())
-    return (d_cam, d_ray) if per_ray else d_cam
+    return _cam_grad_result(d_cam, d_ray)
 
 
 def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):
@@ -846,12 +839,7 @@ def _tv_volume(vol):
     if vol.ndim < 3:
         raise ValueError(f"the TV regulariser expects a volume (..., D, H, W), got {vol.ndim} dimensions")
     _require_gpu(vol, "vol")
-    if vol.dtype == torch.float32:
-        tag = N.DR_F32
-    elif vol.dtype == torch.float16:
-        tag = N.DR_F16
-    else:
-        raise TypeError(f"the TV regulariser reads float32 or float16 volumes, got {vol.dtype}")
+    tag = _dtype_tag(vol, "the TV regulariser reads float32 or float16 volumes")
     geo = _tv_strides(vol)
     if geo is None:   # leading axes that no single stride describes: one copy
         vol = vol.contiguous()

@@ -14,7 +14,7 @@ constant volume c gives c times the chord of the ray through the box.
 """
 import torch
 
-from . import _native as N
+from . import _layout as L
 from . import functional as F
 
 __all__ = ["Projector", "ProjectFunction"]
@@ -29,15 +29,12 @@ class ProjectFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, pj, volume, look_from, batched, jitter=True):
-        cam = look_from.reshape(-1, 3)
-        volume = F.as_volume(volume)
-        seed = F.new_jitter_seed() if jitter else 0
-        e, x, r, n = F.ray_setup(cam, pj.output_shape, volume.shape[-3:], pj.sampling_rate, pj.fov, pj.near, seed)
-        out, arg = F.project_fwd(volume, cam, e, x, r, n, pj.max_samples, pj.mode)
-        ctx.save_for_backward(volume, cam, e, x, r, n, *((arg,) if arg is not None else ()))
+        volume, cam, seed, rays = L.diff_rays(volume, look_from, jitter, pj.output_shape, pj.sampling_rate, pj.fov, pj.near)
+        out, arg = F.project_fwd(volume, cam, *rays, pj.max_samples, pj.mode)
+        ctx.save_for_backward(volume, cam, *rays, *((arg,) if arg is not None else ()))
         ctx.pj, ctx.batched, ctx.seed = pj, batched, seed
         ctx.lf_shape, ctx.lf_dtype = look_from.shape, look_from.dtype
-        return out if batched else out[0]
+        return L.unbatch(out, batched)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -56,7 +53,7 @@ class ProjectFunction(torch.autograd.Function):
         return None, dv, d_cam, None, None
 
 
-class Projector(torch.nn.Module):
+class Projector(L.RayModule):
     """Line-integral (mode "sum") or maximum intensity ("max") projection of a volume.
 
     volume_shape (D, H, W), output_shape (H, W) as for Raycaster; sampling_rate, jitter, fov, near and far as for Raycaster.
@@ -66,7 +63,6 @@ class Projector(torch.nn.Module):
 
     def __init__(self, volume_shape, output_shape, mode="sum", sampling_rate=1.0, jitter=True, max_samples=None, fov=30.0,
                  near=0.1, far=100.0):
-        super().__init__()
         if len(tuple(volume_shape)) != 3 or len(tuple(output_shape)) != 2:
             raise ValueError("expected volume_shape (D, H, W) and output_shape (H, W)")
         if min(volume_shape) < 2 or min(output_shape) < 1:
@@ -78,14 +74,8 @@ class Projector(torch.nn.Module):
             raise ValueError(f"sampling_rate must be > 0, got {sampling_rate}")
         if max_samples is not None and int(max_samples) < 1:
             raise ValueError(f"max_samples must be None or >= 1, got {max_samples}")
-        self.volume_shape = (volume_shape[2], volume_shape[0], volume_shape[1])  # (W, D, H), as Raycaster
-        self.output_shape = tuple(output_shape)
+        super().__init__(volume_shape, output_shape, float(sampling_rate), jitter, max_samples, fov, near, far)
         self.mode = mode
-        self.sampling_rate = float(sampling_rate)
-        self.jitter = jitter
-        self.max_samples = max_samples
-        self.fov, self.near, self.far = fov, near, far
-        N.lib()  # fail loudly at construction time if the HIP library is missing
 
     def _determine_batch(self, volume, look_from):
         """-> (batched, vol ([BS,] W, D, H) view, look_from (BS, 3)); an un-batched volume is shared by all views."""
@@ -94,26 +84,14 @@ class Projector(torch.nn.Module):
         if volume.shape[-4] != 1 or look_from.shape[-1] != 3:
             raise ValueError(f"expected volume ([BS,]1,D,H,W) and look_from ([BS,]3); got {tuple(volume.shape)}, "
                              f"{tuple(look_from.shape)}")
-        vshape = (volume.shape[-1], volume.shape[-3], volume.shape[-2])
-        if vshape != self.volume_shape:
-            raise ValueError(f"volume (D, H, W) = {tuple(volume.shape[-3:])}, the module was built for "
-                             f"{(self.volume_shape[1], self.volume_shape[2], self.volume_shape[0])}")
-        flags = (volume.ndim == 5, look_from.ndim == 2)
-        if any(flags):
-            sizes = {t.shape[0] for t, f in zip((volume, look_from), flags) if f}
-            if len(sizes) != 1:
-                raise ValueError(f"batched inputs disagree on the batch size: {sorted(sizes)}")
-            bs = sizes.pop()
-            vol = volume.squeeze(1).permute(0, 3, 1, 2) if flags[0] else volume.squeeze(0).permute(2, 0, 1)
-            lf = look_from if flags[1] else look_from.reshape(1, 3).expand(bs, 3)
-            return True, vol, lf
-        return False, volume.squeeze(0).permute(2, 0, 1), look_from.reshape(1, 3)
+        self._check_built_for(volume)
+        batched, _, lf = L.batch_rule(look_from, (volume, 5))
+        return batched, L.field_view(volume), lf
 
     @staticmethod
     def _image(out, batched):
-        if batched:  # (BS,W,H) -> flip H -> (BS,1,H,W), as Raycaster
-            return torch.flip(out, (2,)).permute(0, 2, 1).unsqueeze(1).contiguous()
-        return torch.flip(out, (1,)).t().unsqueeze(0).contiguous()
+        """([BS,]W,H) -> ([BS,]1,H,W): the shared orientation at K = 1."""
+        return L.image(out.unsqueeze(-1))
 
     def forward(self, volume, look_from):
         """volume ([BS,]1,D,H,W), look_from ([BS,]3) -> ([BS,]1,H,W)."""

@@ -15,6 +15,7 @@ import math
 
 import torch
 
+from . import _layout as L
 from . import _native as N
 from . import functional as F
 
@@ -60,17 +61,13 @@ class Tf2dRaycastFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, rc, volume, tf2d, look_from, sampling_rate, batched, jitter=True):
-        cam = look_from.reshape(-1, 3)
-        volume = F.as_volume(volume)
+        volume, cam, _, rays = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near)
         tf2d = tf2d.float().contiguous()
-        seed = F.new_jitter_seed() if jitter else 0
-        e, x, r, n = F.ray_setup(cam, rc.output_shape, volume.shape[-3:], sampling_rate, rc.fov, rc.near, seed)
-        out, steps = F.march_tf2d_fwd(volume, tf2d, cam, e, x, r, n, rc.max_samples, sampling_rate, rc.g_scale,
-                                      N.DR_MODE_DIFF)
-        ctx.save_for_backward(volume, tf2d, cam, e, x, r, n, out)
+        out, steps = F.march_tf2d_fwd(volume, tf2d, cam, *rays, rc.max_samples, sampling_rate, rc.g_scale, N.DR_MODE_DIFF)
+        ctx.save_for_backward(volume, tf2d, cam, *rays, out)
         ctx.rc, ctx.sampling_rate, ctx.batched = rc, sampling_rate, batched
-        rc._steps = steps if batched else steps[0]
-        return out if batched else out[0]
+        rc._steps = L.unbatch(steps, batched)
+        return L.unbatch(out, batched)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -85,7 +82,7 @@ class Tf2dRaycastFunction(torch.autograd.Function):
         return None, dv, dt, None, None, None, None
 
 
-class Raycaster2D(torch.nn.Module):
+class Raycaster2D(L.RayModule):
     """Raycaster with a 2-D (value, gradient-magnitude) transfer function.
 
     volume_shape (D, H, W), output_shape (H, W) as for Raycaster, tf_shape (RV, RG), g_scale > 0 (gradient_scale() estimates one).
@@ -93,7 +90,6 @@ class Raycaster2D(torch.nn.Module):
 
     def __init__(self, volume_shape, output_shape, tf_shape, g_scale, sampling_rate=1.0, jitter=True, max_samples=512,
                  fov=30.0, near=0.1, far=100.0):
-        super().__init__()
         if len(tuple(volume_shape)) != 3 or len(tuple(output_shape)) != 2 or len(tuple(tf_shape)) != 2:
             raise ValueError("expected volume_shape (D, H, W), output_shape (H, W) and tf_shape (RV, RG)")
         if min(tf_shape) < 1:
@@ -101,16 +97,9 @@ class Raycaster2D(torch.nn.Module):
         g = float(g_scale)
         if not (math.isfinite(g) and g > 0.0):
             raise ValueError(f"g_scale must be finite and > 0, got {g_scale}")
-        self.volume_shape = (volume_shape[2], volume_shape[0], volume_shape[1])  # (W, D, H), as Raycaster
-        self.output_shape = tuple(output_shape)
+        super().__init__(volume_shape, output_shape, sampling_rate, jitter, max_samples, fov, near, far)
         self.tf_shape = tuple(int(v) for v in tf_shape)
         self.g_scale = g
-        self.sampling_rate = sampling_rate
-        self.jitter = jitter
-        self.max_samples = max_samples
-        self.fov, self.near, self.far = fov, near, far
-        self._steps = None
-        N.lib()  # fail loudly at construction time if the HIP library is missing
 
     def _determine_batch(self, volume, tf2d, look_from):
         """-> (batched, vol ([BS,] W, D, H) view, tf2d ([BS,] RV, RG, 4) view, look_from (BS, 3)); un-batched inputs are
@@ -122,23 +111,8 @@ class Raycaster2D(torch.nn.Module):
                              f"{tuple(volume.shape)}, {tuple(tf2d.shape)}, {tuple(look_from.shape)}")
         if tuple(tf2d.shape[-2:]) != self.tf_shape:
             raise ValueError(f"tf2d has (RV, RG) = {tuple(tf2d.shape[-2:])}, the module was built for {self.tf_shape}")
-        flags = (volume.ndim == 5, tf2d.ndim == 4, look_from.ndim == 2)
-        if any(flags):
-            sizes = {t.shape[0] for t, f in zip((volume, tf2d, look_from), flags) if f}
-            if len(sizes) != 1:
-                raise ValueError(f"batched inputs disagree on the batch size: {sorted(sizes)}")
-            bs = sizes.pop()
-            vol = volume.squeeze(1).permute(0, 3, 1, 2) if flags[0] else volume.squeeze(0).permute(2, 0, 1)
-            tf = tf2d.permute(0, 2, 3, 1) if flags[1] else tf2d.permute(1, 2, 0)
-            lf = look_from if flags[2] else look_from.reshape(1, 3).expand(bs, 3)
-            return True, vol, tf, lf
-        return False, volume.squeeze(0).permute(2, 0, 1), tf2d.permute(1, 2, 0), look_from.reshape(1, 3)
-
-    @staticmethod
-    def _image(out, batched):
-        if batched:  # (BS,W,H,4) -> flip H -> (BS,4,H,W), as Raycaster
-            return torch.flip(out, (2,)).permute(0, 3, 2, 1).contiguous()
-        return torch.flip(out, (1,)).permute(2, 1, 0).contiguous()
+        batched, _, lf = L.batch_rule(look_from, (volume, 5), (tf2d, 4))
+        return batched, L.field_view(volume), tf2d.movedim(-3, -1), lf
 
     def forward(self, volume, tf2d, look_from):
         """volume ([BS,]1,D,H,W), tf2d ([BS,]4,RV,RG), look_from ([BS,]3) -> ([BS,]4,H,W)."""
@@ -151,16 +125,12 @@ class Raycaster2D(torch.nn.Module):
 
     def raycast_nondiff(self, volume, tf2d, look_from, sampling_rate=None):
         """Non-differentiable render (never jittered); default rate 4x the module's, as Raycaster.raycast_nondiff."""
-        with torch.no_grad(), torch.autocast("cuda", enabled=False):
-            batched, vol, tf, lf = self._determine_batch(volume, tf2d, look_from)
-            sr = sampling_rate if sampling_rate is not None else 4.0 * self.sampling_rate
-            vol = F.as_volume(vol)
-            cam = lf.reshape(-1, 3).float()
-            e, x, r, n = F.ray_setup(cam, self.output_shape, vol.shape[-3:], sr, self.fov, self.near, 0)
-            out, steps = F.march_tf2d_fwd(vol, tf.float().contiguous(), cam, e, x, r, n, self.max_samples, sr, self.g_scale,
+        batched, vol, tf, lf = self._determine_batch(volume, tf2d, look_from)
+        with self._nondiff_rays(vol, lf, sampling_rate) as (sr, vol, cam, rays):
+            out, steps = F.march_tf2d_fwd(vol, tf.float().contiguous(), cam, *rays, self.max_samples, sr, self.g_scale,
                                           N.DR_MODE_NONDIFF)
-            self._steps = steps if batched else steps[0]
-            return self._image(out if batched else out[0], batched)
+            self._steps = L.unbatch(steps, batched)
+            return L.image(L.unbatch(out, batched))
 
     def extra_repr(self):
         return (f"Volume ({self.volume_shape}), Output Render ({self.output_shape}), TF2D ({self.tf_shape}), "

@@ -19,6 +19,7 @@ import warnings
 
 import torch
 
+from . import _layout as L
 from . import _native as N
 from . import functional as F
 
@@ -335,16 +336,11 @@ class Raycaster(torch.nn.Module):
     def _determine_batch(self, volume, tf, look_from):
         """VR.py:551-571, without the copies: returns (batched, bs, vol, tf, lf) where vol is the
         ([BS,] W, D, H) *view* of the input, tf is ([BS,] R, 4); un-batched inputs stay un-batched (shared)."""
-        flags = (volume.ndim == 5, tf.ndim == 3, look_from.ndim == 2)
         if volume.ndim not in (4, 5) or tf.ndim not in (2, 3) or look_from.ndim not in (1, 2):
             raise ValueError("expected volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3)")
-        if any(flags):
-            bs = [volume, tf, look_from][flags.index(True)].size(0)
-            vol_out = volume.squeeze(1).permute(0, 3, 1, 2) if flags[0] else volume.squeeze(0).permute(2, 0, 1)
-            tf_out = tf.permute(0, 2, 1) if flags[1] else tf.permute(1, 0)
-            lf_out = look_from if flags[2] else look_from.expand(bs, -1)
-            return True, bs, vol_out, tf_out, lf_out
-        return False, 0, volume.squeeze(0).permute(2, 0, 1), tf.permute(1, 0), look_from
+        batched, bs, lf = L.batch_rule(look_from, (volume, 5), (tf, 3))
+        # (the un-batched look_from stays (3,), as the reference hands it on)
+        return batched, bs, L.field_view(volume), tf.transpose(-1, -2), lf if batched else look_from
 
     def _hints(self, tf, vol_in, sampling_rate, mode):
         """DR_HINT_* from the USER's TF tensor ([BS,] 4, R) -- the object that lives across iterations and whose version
@@ -356,28 +352,21 @@ class Raycaster(torch.nn.Module):
 
     def raycast_nondiff(self, volume, tf, look_from, sampling_rate=None):
         """VR.py:490-523: non-differentiable render (never jittered); default rate 4x the module's."""
-        with torch.no_grad(), torch.autocast("cuda", enabled=False):
-            batched, bs, vol_in, tf_in, lf_in = self._determine_batch(volume, tf, look_from)
-            sr = sampling_rate if sampling_rate is not None else 4.0 * self.sampling_rate
-            vol_in = F.as_volume(vol_in)
-            cam = lf_in.reshape(-1, 3).float()
-            e, x, r, n = F.ray_setup(cam, self.vr.resolution, vol_in.shape[-3:], sr, self.vr.fov_deg, self.vr.near, 0)
-            out, steps = F.march_fwd(vol_in, tf_in.float().contiguous(), cam, e, x, r, n, self.vr.max_samples, sr,
+        batched, bs, vol_in, tf_in, lf_in = self._determine_batch(volume, tf, look_from)
+        with L.nondiff_rays(vol_in, lf_in, sampling_rate, self.sampling_rate, self.vr.resolution, self.vr.fov_deg,
+                            self.vr.near) as (sr, vol_in, cam, rays):
+            out, steps = F.march_fwd(vol_in, tf_in.float().contiguous(), cam, *rays, self.vr.max_samples, sr,
                                      N.DR_MODE_NONDIFF, fov_deg=self.vr.fov_deg, near=self.vr.near,
                                      hints=self._hints(tf, vol_in, sr, N.DR_MODE_NONDIFF))
-            self.vr._steps = steps if batched else steps[0]
-            if batched:  # (BS,W,H,4) -> flip H -> (BS,4,H,W), VR.py:513
-                return torch.flip(out, (2,)).permute(0, 3, 2, 1).contiguous()
-            return torch.flip(out[0], (1,)).permute(2, 1, 0).contiguous()  # VR.py:523
+            self.vr._steps = L.unbatch(steps, batched)
+            return L.image(L.unbatch(out, batched))
 
     def forward(self, volume, tf, look_from):
         """VR.py:525-548. volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3) -> ([BS,]4,H,W)."""
         batched, bs, vol_in, tf_in, lf_in = self._determine_batch(volume, tf, look_from)
         res = RaycastFunction.apply(self.vr, vol_in, tf_in, lf_in, self.sampling_rate, (batched, bs), self.jitter,
                                     self._hints(tf, vol_in, self.sampling_rate, N.DR_MODE_DIFF))
-        if batched:
-            return torch.flip(res, (2,)).permute(0, 3, 2, 1).contiguous()
-        return torch.flip(res, (1,)).permute(2, 1, 0).contiguous()
+        return L.image(res)
 
     def extra_repr(self):
         return (f"Volume ({self.volume_shape}), Output Render ({self.output_shape}), TF ({self.tf_shape}), "

@@ -267,6 +267,34 @@ def test_projector_matches_the_functional_calls():
             assert torch.isfinite(pj(vol, lf)).all()
 
 
+def test_projector_shares_an_unbatched_volume_among_batched_cameras():
+    """A shared (1, D, H, W) volume with look_from (2, 3), mode "max", on a 9 x 10 x 11 volume and an 11 x 13 image (no multiple
+    of the 8 x 8 tile): the image is bit for bit the functional calls' on the explicitly permuted view, the shared volume
+    receives one gradient summed over both views. (The gradients are sums of atomics whose order varies from run to run:
+    compared at the bar of test_projector_matches_the_functional_calls, not bit for bit.)"""
+    from differender_amd import functional as F
+    from differender_amd.projection import Projector
+    D, Hh, Ww, WH = 9, 10, 11, (11, 13)
+    pj = Projector((D, Hh, Ww), WH, mode="max", jitter=False)
+    vol = _volume((1, D, Hh, Ww), 21).requires_grad_(True)
+    lf = torch.tensor([_cam(0.3, 0.2, 2.8), _cam(1.9, -0.3, 2.6)], device=_dev(), requires_grad=True)
+    img = pj(vol, lf)
+    assert img.shape == (2, 1, 13, 11)
+    vf = vol.detach().squeeze(0).permute(2, 0, 1)
+    e, x, r, n = F.ray_setup(lf.detach(), WH, vf.shape, 1.0, 30.0, 0.1, 0)
+    out, arg = F.project_fwd(vf, lf.detach(), e, x, r, n, None, "max")
+    assert torch.equal(img.detach(), torch.flip(out, (2,)).permute(0, 2, 1)[:, None])
+    g = torch.randn_like(img)
+    (img * g).sum().backward()
+    gk = torch.flip(g[:, 0].permute(0, 2, 1), (2,))
+    dv = F.project_bwd(vf, lf.detach(), e, x, r, n, gk, None, "max", arg)
+    assert vol.grad.shape == vol.shape and dv.shape == vf.shape
+    torch.testing.assert_close(vol.grad.squeeze(0).permute(2, 0, 1), dv, rtol=1e-5, atol=1e-6)
+    dc = F.project_bwd_cam(vf, lf.detach(), e, x, r, n, gk, None, "max", arg)
+    assert lf.grad.shape == (2, 3)
+    torch.testing.assert_close(lf.grad, dc, rtol=1e-5, atol=1e-6)
+
+
 def test_full_size_512():
     from differender_amd import functional as F
     N, WH = 512, (512, 512)

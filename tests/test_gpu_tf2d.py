@@ -298,6 +298,37 @@ def test_raycaster2d_matches_the_functional_calls(hiplib):
         rc(vol_user, tf_user, lf.clone().requires_grad_(True))
 
 
+def test_raycaster2d_shares_an_unbatched_volume_and_table_among_batched_cameras(hiplib):
+    """A shared (1, D, H, W) volume and (4, RV, RG) table with look_from (2, 3), on a 9 x 10 x 11 volume and an 11 x 13 image (no
+    multiple of the 8 x 8 tile): image and live-sample counts are bit for bit the functional calls' on the explicitly permuted
+    views, the shared inputs receive one gradient summed over both views. (The gradients are sums of atomics whose order varies
+    from run to run: compared at the bar of test_raycaster2d_matches_the_functional_calls, not bit for bit.)"""
+    from differender_amd.tf2d import Raycaster2D
+    F = _F()
+    D, H, W, WH = 9, 10, 11, (11, 13)
+    vol_user = _volume((D, H, W), seed=12)[None].requires_grad_(True)       # (1, D, H, W)
+    tf_user = _tf2d(8, 6, "opaque", seed=13).permute(2, 0, 1).contiguous().requires_grad_(True)   # (4, RV, RG)
+    lf = _cams(2)
+    g_scale = _g_scale(vol_user.detach()[0])
+    rc = Raycaster2D((D, H, W), WH, (8, 6), g_scale, jitter=False)
+    img = rc(vol_user, tf_user, lf)
+    assert img.shape == (2, 4, 13, 11)
+    vol_f = vol_user.detach().squeeze(0).permute(2, 0, 1)                  # (W, D, H): the field view
+    tf_f = tf_user.detach().permute(1, 2, 0).contiguous()
+    e, x, r, n = F.ray_setup(lf, WH, vol_f.shape, 1.0)
+    out, steps = F.march_tf2d_fwd(vol_f, tf_f, lf, e, x, r, n, 512, 1.0, g_scale)
+    assert torch.equal(img.detach(), torch.flip(out, (2,)).permute(0, 3, 2, 1)) and torch.equal(rc._steps, steps)
+    G = torch.randn(img.shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(2))
+    (img * G).sum().backward()
+    gk = torch.flip(G.permute(0, 3, 2, 1), (2,))
+    dv, dt = F.march_tf2d_bwd(vol_f, tf_f, lf, e, x, r, n, 512, 1.0, g_scale, gk, out)
+    dv_user = dv.permute(1, 2, 0)[None]
+    dt_user = dt.permute(2, 0, 1)
+    assert vol_user.grad.shape == vol_user.shape and tf_user.grad.shape == tf_user.shape
+    assert (vol_user.grad - dv_user).abs().max() <= 1e-5 * dv_user.abs().max()
+    assert (tf_user.grad - dt_user).abs().max() <= 1e-5 * dt_user.abs().max()
+
+
 @pytest.mark.parametrize("batched", [False, True])
 def test_raycaster2d_with_one_gradient_column_renders_what_raycaster_renders(hiplib, batched):
     from differender_amd.tf2d import Raycaster2D

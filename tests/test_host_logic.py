@@ -38,6 +38,99 @@ def test_determine_batch_mixed(rc):
         rc._determine_batch(torch.rand(6, 8, 10), tf, lf)
 
 
+def test_determine_batch_rejects_disagreeing_batch_sizes(rc):
+    """Raycaster raises what the other three modules raise, before anything reaches expand or the C-ABI marshalling."""
+    tf = torch.rand(4, 12)
+    for bad in ((torch.rand(2, 1, 6, 8, 10), tf, torch.rand(3, 3)), (torch.rand(3, 1, 6, 8, 10), tf, torch.rand(2, 3)),
+                (torch.rand(1, 6, 8, 10), torch.rand(2, 4, 12), torch.rand(3, 3)),
+                (torch.rand(2, 1, 6, 8, 10), torch.rand(3, 4, 12), torch.rand(3))):
+        with pytest.raises(ValueError, match="batch size"):
+            rc._determine_batch(*bad)
+
+
+# --- the layout convention the four renderer modules share (differender_amd/_layout.py) ------------------------------------
+
+def _same_view(got, want):
+    return got.shape == want.shape and got.stride() == want.stride() and got.data_ptr() == want.data_ptr()
+
+
+def test_field_view_is_the_strided_view_the_kernels_consume():
+    """Against the squeeze / permute expressions written out, on (D, H, W) = (5, 6, 7): three different extents, so that a
+    swapped axis cannot pass. Shapes, strides and data_ptr: a view, never a copy."""
+    from differender_amd import _layout as L
+    from differender_amd.rgba import interleaved
+    v = torch.rand(1, 5, 6, 7)
+    assert L.field_view(v).shape == (7, 5, 6) and _same_view(L.field_view(v), v.squeeze(0).permute(2, 0, 1))
+    vb = torch.rand(3, 1, 5, 6, 7)
+    assert L.field_view(vb).shape == (3, 7, 5, 6) and _same_view(L.field_view(vb), vb.squeeze(1).permute(0, 3, 1, 2))
+    c = torch.rand(4, 5, 6, 7)
+    cb = torch.rand(3, 4, 5, 6, 7)
+    for q, qb in ((c, cb), (interleaved(c), interleaved(cb))):
+        assert L.field_view_rgba(q).shape == (4, 7, 5, 6) and _same_view(L.field_view_rgba(q), q.permute(0, 3, 1, 2))
+        assert L.field_view_rgba(qb).shape == (3, 4, 7, 5, 6) and _same_view(L.field_view_rgba(qb), qb.permute(0, 1, 4, 2, 3))
+    assert L.field_view_rgba(interleaved(cb)).stride(1) == 1   # the channel axis stays at stride 1: one load per voxel
+
+
+def test_image_orientation_flips_h_and_is_contiguous():
+    from differender_amd import _layout as L
+    from differender_amd.projection import Projector
+    W, H = 9, 13
+    o, ob = torch.rand(W, H, 4), torch.rand(2, W, H, 4)
+    for got, want in ((L.image(o), torch.flip(o, (1,)).permute(2, 1, 0)), (L.image(ob), torch.flip(ob, (2,)).permute(0, 3, 2, 1))):
+        assert got.shape == want.shape and torch.equal(got, want) and got.is_contiguous()
+    assert L.image(o).shape == (4, H, W) and L.image(ob).shape == (2, 4, H, W)
+    p, pb = torch.rand(W, H), torch.rand(2, W, H)    # a projection: K = 1
+    for got, want in ((Projector._image(p, False), torch.flip(p, (1,)).t().unsqueeze(0)),
+                      (Projector._image(pb, True), torch.flip(pb, (2,)).permute(0, 2, 1).unsqueeze(1))):
+        assert got.shape == want.shape and torch.equal(got, want) and got.is_contiguous()
+    assert Projector._image(p, False).shape == (1, H, W) and Projector._image(pb, True).shape == (2, 1, H, W)
+
+
+def _batch_cases():
+    """(a module's _determine_batch, the shapes of its un-batched inputs -- look_from last --, the same batched with BS = 3) for the
+    four renderer modules, at (D, H, W) = (5, 6, 7)."""
+    from differender_amd.projection import Projector
+    from differender_amd.rgba import RaycasterRGBA
+    from differender_amd.tf2d import Raycaster2D
+    from differender_amd.volume_raycaster import Raycaster
+    shape = (5, 6, 7)
+    return [(Raycaster(shape, (8, 8), 12)._determine_batch, ((1, 5, 6, 7), (4, 12), (3,)), ((3, 1, 5, 6, 7), (3, 4, 12), (3, 3))),
+            (Raycaster2D(shape, (8, 8), (6, 4), 1.0)._determine_batch, ((1, 5, 6, 7), (4, 6, 4), (3,)),
+             ((3, 1, 5, 6, 7), (3, 4, 6, 4), (3, 3))),
+            (Projector(shape, (8, 8))._determine_batch, ((1, 5, 6, 7), (3,)), ((3, 1, 5, 6, 7), (3, 3))),
+            (RaycasterRGBA(shape, (8, 8))._determine_batch, ((4, 5, 6, 7), (3,)), ((3, 4, 5, 6, 7), (3, 3)))]
+
+
+def test_batch_rule_of_the_four_modules(hiplib):
+    """Un-batched inputs, each single input batched, all batched, and two batched inputs of different BS, for every module: the
+    batch flag, a batched input's view with its leading BS and a shared one's without, look_from as (BS, 3) -- Raycaster's stays
+    (3,) when nothing is batched --, and a ValueError for disagreeing batch sizes."""
+    for determine, single, batch in _batch_cases():
+        n_in = len(single)
+        plain = [torch.rand(s) for s in single]
+        res = determine(*plain)
+        field_shapes = [v.shape for v in res[-n_in:-1]]   # of the un-batched views, in field order
+        assert res[0] is False
+        is_raycaster = len(res) == 5 and res[1] == 0      # (batched, bs, vol, tf, lf)
+        assert res[-1].shape == ((3,) if is_raycaster else (1, 3)) and torch.equal(res[-1].reshape(3), plain[-1])
+        for which in [(j,) for j in range(n_in)] + [tuple(range(n_in))]:
+            args = [torch.rand(batch[j] if j in which else single[j]) for j in range(n_in)]
+            res = determine(*args)
+            assert res[0] is True and (not is_raycaster or res[1] == 3)
+            for j, view in enumerate(res[-n_in:-1]):
+                assert view.shape == ((3,) if j in which else ()) + tuple(field_shapes[j]), (which, j)
+                assert view.data_ptr() == args[j].data_ptr()
+            assert res[-1].shape == (3, 3)
+            assert torch.equal(res[-1], args[-1] if n_in - 1 in which else args[-1].expand(3, 3))
+        for a in range(n_in):
+            for b in range(a + 1, n_in):
+                args = [torch.rand(s) for s in single]
+                args[a] = torch.rand(batch[a])
+                args[b] = torch.rand((2,) + tuple(batch[b][1:]))
+                with pytest.raises(ValueError, match="batch size"):
+                    determine(*args)
+
+
 def test_no_cpu_fallback(rc):
     with pytest.raises(RuntimeError, match="no CPU path"):
         rc(torch.rand(1, 6, 8, 10), torch.rand(4, 12), torch.tensor([2.5, 0.7, 0.0]))
