@@ -30,7 +30,9 @@ def T(a):
 
 SCALE = int(os.environ.get("FUZZ_SCALE", "1"))   # 3: volumes up to 288 per axis, images up to 288 px (a case takes seconds)
 PROFILE = os.environ.get("FUZZ_PROFILE", "")     # "inside": every camera inside or next to the volume (work items of heavy
-                                                 # bricks); "ert": opaque TFs at high sampling rates (termination decisions)
+                                                 # bricks); "ert": opaque TFs at high sampling rates (termination decisions);
+                                                 # "tape": every differentiable fast-path case asks for d_tf alone, over the
+                                                 # per-sample tape (DR_TAPE_TF, csrc/tf_tape.hip)
 
 
 def make_case(seed):
@@ -101,6 +103,10 @@ def make_case(seed):
         g *= np.exp(rng.uniform(-9, 9, size=(n_views, *WH, 1))).astype(np.float32)   # wide dynamic range of the upstream gradient
     want = [(True, True), (True, True), (True, False), (False, True)][int(rng.integers(0, 4))]
     variant = 1 if seed % 6 == 5 else 0     # every sixth case runs the baseline kernels (DR_VARIANT_BASELINE) instead
+    # PROFILE "tape": the TF-only backward over the per-sample tape on every differentiable case of the fast path (without the profile:
+    # one case in sixteen or so). Overridden after the draw, so that the other fields of a seed stay what they were.
+    if PROFILE == "tape" and variant == 0 and mode == 0:
+        want = (False, True)
     # every fourth multi-view case: one volume and one TF PER VIEW (VR.py:415-427 "batched" inputs), per-item gradients.
     # (drawn from a generator of their own, so that the other fields of a seed stay what they were)
     vols, tfs = None, None
@@ -149,7 +155,7 @@ def run_case(c):
         rows = None if cut == 0 else (row0, W)
         eb, xb, rb, nb = Fn.ray_setup(cam, (nr, WH[1]), vshape, sr, jitter_seed=c["jitter"], rows=rows)
         # the TF-only backward of the fast path runs over the per-sample tape (DR_TAPE_TF) on every second such case
-        use_tape = variant == 0 and mode == 0 and tuple(c["want"]) == (False, True) and c["seed"] % 2 == 0
+        use_tape = variant == 0 and mode == 0 and tuple(c["want"]) == (False, True) and (c["seed"] % 2 == 0 or PROFILE == "tape")
         c["tape"] = use_tape
         wsb = Fn.alloc_workspace(c["n_views"], (nr, WH[1]), vshape, c["R"], dev, tape=(S, sr) if use_tape else None) if variant == 0 else None
         use_tape = use_tape and wsb is not None
@@ -265,7 +271,7 @@ def run_case(c):
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    t0 = time.time(); n_run = 0; n_bad = 0; last = t0; n_undef = 0; n_ill = 0
+    t0 = time.time(); n_run = 0; n_bad = 0; last = t0; n_undef = 0; n_ill = 0; n_tape = 0
     while time.time() - t0 < budget:
         c = make_case(seed)
         try:
@@ -275,11 +281,11 @@ def main():
         if fails:
             n_bad += 1
             print("FAIL seed", seed, fails, describe(c), flush=True)
-        n_run += 1; seed += 1; n_undef += bool(c.get("_undefined")); n_ill += bool(c.get("_illcond"))
+        n_run += 1; seed += 1; n_undef += bool(c.get("_undefined")); n_ill += bool(c.get("_illcond")); n_tape += bool(c.get("tape"))
         if time.time() - last > 30:
             last = time.time(); print(f"... {n_run} cases, {n_bad} failing, next seed {seed}", flush=True)
     print(f"fuzz done: {n_run} cases in {time.time() - t0:.0f} s, {n_bad} failing, seeds up to {seed - 1}; "
-          f"{n_undef} cases with an infinite reference gradient, {n_ill} ill-conditioned cases judged against the baseline kernels' noise")
+          f"{n_undef} cases with an infinite reference gradient, {n_ill} ill-conditioned cases judged against the baseline kernels' noise; {n_tape} cases over the per-sample tape")
     sys.exit(1 if n_bad else 0)
 
 
