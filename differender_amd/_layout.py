@@ -6,6 +6,7 @@ batched inputs agree on BS and un-batched ones are shared by all views. Raycaste
 differ in which inputs they take and what they check about them, not in any of this.
 """
 import contextlib
+import math
 
 import torch
 
@@ -37,6 +38,45 @@ def batch_rule(look_from, *inputs):
     return True, bs, look_from if look_from.ndim == 2 else look_from.reshape(1, 3).expand(bs, 3)
 
 
+def pose_rule(look_from, pose, *inputs):
+    """batch_rule for the free camera: pose = (look_at, up, fov) -- look_at and up ([BS,]3), fov ([BS,]) degrees,
+    a 0-d tensor or a number, each may be None -- joins the rule: a batched one sets BS like any other input, an un-batched one
+    is shared by all views. -> (batched, BS, look_from (BS,3), (look_at, up (BS,3), fov (BS,))): the pose as tensors on
+    look_from's device with one row per view (expanded, not copied), None staying None."""
+    look_at, up, fov = pose
+    if fov is not None and not torch.is_tensor(fov):
+        fov = torch.tensor(float(fov), dtype=torch.float32, device=look_from.device)
+    for name, t, ranks, last in (("look_at", look_at, (1, 2), 3), ("up", up, (1, 2), 3), ("fov", fov, (0, 1), None)):
+        if t is not None and (t.ndim not in ranks or (last is not None and t.shape[-1] != last)):
+            raise ValueError(f"expected {name} ([BS,]{last or ''}), got {tuple(t.shape)}")
+    posed = [(t, rank) for t, rank in ((look_at, 2), (up, 2), (fov, 1)) if t is not None]
+    batched, bs, lf = batch_rule(look_from, *inputs, *posed)
+    views = bs if batched else 1
+    rows = lambda t, k: None if t is None else t.to(look_from.device).reshape(-1, *k).expand(views, *k)
+    return batched, bs, lf, (rows(look_at, (3,)), rows(up, (3,)), rows(fov, ()))
+
+
+def has_pose(look_at, up, fov):
+    """False when all are None: the renderers then take the fixed camera's code path, untouched."""
+    return not (look_at is None and up is None and fov is None)
+
+
+def refuse_pose_grad(who, **tensors):
+    """Raycaster2D and RaycasterRGBA have no camera gradients: a camera tensor that requires grad is an error, not a silent None."""
+    for name, t in tensors.items():
+        if torch.is_grad_enabled() and torch.is_tensor(t) and t.requires_grad:
+            raise ValueError(f"{who} has no gradient w.r.t. {name}: use volume_raycaster.Raycaster for camera gradients, or "
+                             f"pass {name}.detach()")
+
+
+def reduce_to(d, shape, dtype):
+    """A per-view gradient (views, ...) back in the shape its input came in: an un-batched input that was shared by the views
+    gets their sum."""
+    if d.numel() != math.prod(shape):
+        d = d.sum(0)
+    return d.reshape(shape).to(dtype)
+
+
 def image(out):
     """Kernel image ([BS,]W,H,K) -> user image ([BS,]K,H,W), H flipped, contiguous (VR.py:513,523). A projection's
     ([BS,]W,H) is K = 1: image(out.unsqueeze(-1))."""
@@ -48,24 +88,44 @@ def unbatch(t, batched):
     return t if batched else t[0]
 
 
-def diff_rays(volume, look_from, jitter, output_shape, sampling_rate, fov, near):
+def pose_tensors(cam, pose):
+    """pose_rule's (look_at, up, fov) for the cameras cam (views,3) -> what the kernels read: the pose (views,9)
+    float32 and fov_v (views,) float32 in RADIANS, None when fov is (the module's scalar fov serves every view)."""
+    look_at, up, fov = pose
+    fov_v = None if fov is None else torch.deg2rad(fov.to(cam.device, torch.float32).reshape(-1).expand(cam.shape[0])).contiguous()
+    return F.pack_pose(cam, look_at, up), fov_v
+
+
+def diff_rays(volume, look_from, jitter, output_shape, sampling_rate, fov, near, pose=None):
     """What the autograd forwards do before their march -> (volume, cam, seed, (entry, exit, rays, n)): the volume as the kernels
-    read it, the cameras (views,3), the jitter seed drawn for this forward (0: none) and the ray buffers of ray_setup."""
+    read it, the cameras (views,3), the jitter seed drawn for this forward (0: none) and the ray buffers of ray_setup.
+    pose: pose_rule's (look_at, up, fov) -- the buffers are ray_setup_pose's then, cam is the pose's float32 look_from rows, and
+    the result has two more entries: the pose (views,9) and fov_v (pose_tensors)."""
     cam = look_from.reshape(-1, 3)
     volume = F.as_volume(volume)
     seed = F.new_jitter_seed() if jitter else 0
-    return volume, cam, seed, F.ray_setup(cam, output_shape, volume.shape[-3:], sampling_rate, fov, near, seed)
+    if pose is None:
+        return volume, cam, seed, F.ray_setup(cam, output_shape, volume.shape[-3:], sampling_rate, fov, near, seed)
+    pose9, fov_v = pose_tensors(cam, pose)
+    rays = F.ray_setup_pose(pose9, output_shape, volume.shape[-3:], sampling_rate, fov, near, seed, fov_v=fov_v)
+    return volume, pose9[:, :3], seed, rays, pose9, fov_v
 
 
 @contextlib.contextmanager
-def nondiff_rays(volume, look_from, sampling_rate, module_rate, output_shape, fov, near):
+def nondiff_rays(volume, look_from, sampling_rate, module_rate, output_shape, fov, near, pose=None):
     """The scope and preamble of every raycast_nondiff (VR.py:490-523): no autograd, no autocast, the default rate of 4x the
-    module's, never jittered. Yields (sampling_rate, volume, cam, (entry, exit, rays, n)) for the march inside the scope."""
+    module's, never jittered. Yields (sampling_rate, volume, cam, (entry, exit, rays, n)) for the march inside the scope --
+    and, with pose = pose_rule's (look_at, up, fov), the pose (views,9) and fov_v as two more (diff_rays)."""
     with torch.no_grad(), torch.autocast("cuda", enabled=False):
         sr = sampling_rate if sampling_rate is not None else 4.0 * module_rate
         volume = F.as_volume(volume)
         cam = look_from.reshape(-1, 3).float()
-        yield sr, volume, cam, F.ray_setup(cam, output_shape, volume.shape[-3:], sr, fov, near, 0)
+        if pose is None:
+            yield sr, volume, cam, F.ray_setup(cam, output_shape, volume.shape[-3:], sr, fov, near, 0)
+        else:
+            pose9, fov_v = pose_tensors(cam, pose)
+            rays = F.ray_setup_pose(pose9, output_shape, volume.shape[-3:], sr, fov, near, 0, fov_v=fov_v)
+            yield sr, volume, pose9[:, :3], rays, pose9, fov_v
 
 
 class RayModule(torch.nn.Module):
@@ -89,8 +149,8 @@ class RayModule(torch.nn.Module):
         if tuple(volume.shape[-3:]) != (d, h, w):
             raise ValueError(f"volume has (D, H, W) = {tuple(volume.shape[-3:])}, the module was built for {(d, h, w)}")
 
-    def _nondiff_rays(self, volume, look_from, sampling_rate):
-        return nondiff_rays(volume, look_from, sampling_rate, self.sampling_rate, self.output_shape, self.fov, self.near)
+    def _nondiff_rays(self, volume, look_from, sampling_rate, pose=None):
+        return nondiff_rays(volume, look_from, sampling_rate, self.sampling_rate, self.output_shape, self.fov, self.near, pose)
 
     @staticmethod
     def _image(out, batched):

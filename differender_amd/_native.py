@@ -45,6 +45,16 @@ SIGNATURES = {
                                _I, _I, _I, _I, _F, _D, _D, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _Z, _I, _I, _P]),
     "dr_march_bwd_cam": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
                               _I, _I, _I, _I, _F, _D, _D, _U, _U, _I, _I, _P, _P, _P, _P, _P, _P]),
+    # the free camera: the entries above plus pose, fov_v (and d_pose, d_pose_ray for d_cam, d_cam_ray)
+    "dr_ray_setup_pose_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _D, _D, _F, _U, _U, _P, _P, _P, _P, _P, _P, _P]),
+    "dr_march_fwd_rows_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                                    _I, _I, _I, _I, _F, _D, _D, _I, _I, _P, _P, _P, _Z, _I, _I, _P, _P, _P]),
+    "dr_march_bwd_rows_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                                    _I, _I, _I, _I, _F, _D, _D, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _Z, _I, _I, _P, _P, _P]),
+    "dr_march_bwd_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                               _I, _I, _I, _I, _F, _D, _D, _U, _U, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dr_project_bwd_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _U, _U,
+                                 _P, _P, _P, _P, _P, _P, _P]),
     "dr_march_bwd_variant": (_I, [_I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I, _I, _I]),
     "dr_comm_unique_id": (_I, [_P]),
     "dr_comm_init_rank": (_I, [_c.POINTER(_P), _I, _P, _I]),

@@ -30,9 +30,13 @@ struct CamParams : RayParams<VT> {
     float near_, near_w, near_h;
     uint32_t jitter_seed, view_base;
     double *d_cam; float *d_cam_ray;
+    const float *pose, *fov_v;   // POSE: [views][9] look_from, look_at, up; [views] fov in radians, nullable
+    double near_d, aspect;       // ... the near plane and img_W / H as doubles, for a view's own extents
 };
 
-template <typename VT, bool TF_LDS>
+// POSE: the gradient w.r.t. the free camera's ten parameters (look_from, look_at, up, fov) from the same four sums -- only the
+// once-per-ray tail and the reduction differ (dr_camera.h: pose_ray_grad, pose_reduce); d_cam is [views][10], d_cam_ray [..][10].
+template <typename VT, bool TF_LDS, bool POSE = false>
 __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     __shared__ double red[3][256];
@@ -40,6 +44,7 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
     const float4 *tf = stage_table<TF_LDS>(lds_tf_, P.tf + view * P.tf_vs, P.R);
 
     f3 dcam = make_f3(0.f, 0.f, 0.f);
+    PoseGrad dpose = pose_zero();
     int i, j;
     const bool in_img = tile_pixel(P.W, P.H, i, j);
     const size_t p = ((size_t)view * P.W + i) * P.H + j;
@@ -113,19 +118,27 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
             s1 = fmaf(f, gv, s1);
         }
 
-        // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw behind grad t0
-        M3 J;
-        f3 g_tmin, g_tmax, g_t0;
-        float u;
-        camera_ray_tail(lf, vd, i + P.row0, P.img_W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed,
-                        P.view_base + (uint32_t)view, J, g_tmin, g_tmax, g_t0, u);
-        dcam = f3_add(sP, mul_t(J, sTG));
-        dcam = f3_fma(s0, g_t0, dcam);
-        dcam = f3_fma(s1, g_tmax, dcam);
-        // D5: a NaN ray (NaN upstream gradient) contributes nothing, infinities are clamped
-        dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
+        if (POSE) {
+            // once per ray: the ten pose gradients from the four sums (dr_camera.h), then D5
+            const PoseRay q = pose_ray(P.pose, P.fov_v, view, P.near_d, P.aspect, P.near_w, P.near_h, i + P.row0, P.img_W, j, P.H,
+                                       rg.n, P.jitter_seed, P.view_base + (uint32_t)view);
+            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.near_, sP, sTG, s0 * q.A, fmaf(s0, 1.0f - q.A, s1)));
+        } else {
+            // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw behind grad t0
+            M3 J;
+            f3 g_tmin, g_tmax, g_t0;
+            float u;
+            camera_ray_tail(lf, vd, i + P.row0, P.img_W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed,
+                            P.view_base + (uint32_t)view, J, g_tmin, g_tmax, g_t0, u);
+            dcam = f3_add(sP, mul_t(J, sTG));
+            dcam = f3_fma(s0, g_t0, dcam);
+            dcam = f3_fma(s1, g_tmax, dcam);
+            // D5: a NaN ray (NaN upstream gradient) contributes nothing, infinities are clamped
+            dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
+        }
     }
-    camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    if (POSE) pose_reduce(dpose, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    else camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
 }
 
 template <typename VT>
@@ -135,6 +148,12 @@ static int cam_dispatch(const MarchArgs &a, const CamArgs &c, hipStream_t stream
     near_plane_extents(a.fov_rad, a.near_plane, a.img_W, a.H, P.near_, P.near_w, P.near_h);
     P.jitter_seed = c.jitter_seed; P.view_base = c.view_base;
     P.d_cam = c.d_cam; P.d_cam_ray = c.d_cam_ray;
+    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)a.img_W / (double)a.H;
+    if (a.pose) {   // (the table tiers of the fixed camera, below)
+        const size_t lds_p = (size_t)a.R * sizeof(float4);
+        if (lds_p <= 48 * 1024) return launch_tiles(camera_grad_kernel<VT, true, true>, a, lds_p, stream, P);
+        return launch_tiles(camera_grad_kernel<VT, false, true>, a, 0, stream, P);
+    }
     const size_t lds = (size_t)a.R * sizeof(float4);
     if (lds <= 48 * 1024) return launch_tiles(camera_grad_kernel<VT, true>, a, lds, stream, P);
     return launch_tiles(camera_grad_kernel<VT, false>, a, 0, stream, P);   // a large TF is read where it lies

@@ -94,17 +94,26 @@ size_t dr_workspace_bytes_tape(int n_views, int W, int H, int VX, int VY, int VZ
     return brick_workspace_bytes_tape(n_views, W, H, VX, VY, VZ, max_samples, sampling_rate);
 }
 
-int dr_ray_setup_rows(const float *cam, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
-                      double fov_rad, double near_plane, float sampling_rate, uint32_t jitter_seed, uint32_t view_base,
-                      float *entry, float *exit_, float *rays, int32_t *nsamp, void *stream) {
-    if (!cam || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
+int dr_ray_setup_pose_rows(const float *cam, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
+                           double fov_rad, double near_plane, float sampling_rate, uint32_t jitter_seed, uint32_t view_base,
+                           float *entry, float *exit_, float *rays, int32_t *nsamp, const float *pose, const float *fov_v,
+                           void *stream) {
+    if ((!cam && !pose) || (fov_v && !pose) || !entry || !exit_ || !rays || !nsamp) return DR_EINVAL;
     if (n_views <= 0 || W <= 0 || H <= 0 || VX < 2 || VY < 2 || VZ < 2) return DR_EINVAL;
     if (n_views > 65535 || !(sampling_rate > 0.0f)) return DR_EINVAL;
     if (!band_fits(W, img_W, row0)) return DR_EINVAL;
     DeviceOf guard(entry);
     if (guard.err != hipSuccess) return (int)guard.err;
-    return (int)launch_ray_setup(cam, n_views, W, H, img_W, row0, VX, VY, VZ, fov_rad, near_plane, sampling_rate,
+    return (int)launch_ray_setup(cam, pose, fov_v, n_views, W, H, img_W, row0, VX, VY, VZ, fov_rad, near_plane, sampling_rate,
                                  jitter_seed, view_base, entry, exit_, rays, nsamp, (hipStream_t)stream);
+}
+
+int dr_ray_setup_rows(const float *cam, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
+                      double fov_rad, double near_plane, float sampling_rate, uint32_t jitter_seed, uint32_t view_base,
+                      float *entry, float *exit_, float *rays, int32_t *nsamp, void *stream) {
+    if (!cam) return DR_EINVAL;
+    return dr_ray_setup_pose_rows(cam, n_views, W, H, img_W, row0, VX, VY, VZ, fov_rad, near_plane, sampling_rate, jitter_seed,
+                                  view_base, entry, exit_, rays, nsamp, nullptr, nullptr, stream);
 }
 
 int dr_ray_setup(const float *cam, int n_views, int W, int H, int VX, int VY, int VZ, double fov_rad,
@@ -161,19 +170,22 @@ static int fill_bwd(MarchArgs &a, const float *grad_out, const float *out_rgba, 
     return 0;
 }
 
-int dr_march_fwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+// a pose's look_from rows are the `cam` the march kernels read as the ray origin; fov_v only comes with a pose
+static bool pose_fits(const float *pose, const float *fov_v) { return pose || !fov_v; }
+
+int dr_march_fwd_rows_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                  int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
                  const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
                  int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, int mode, int variant,
                  float *out_rgba, int32_t *steps, void *workspace, size_t workspace_bytes, int img_W, int row0,
-                      void *stream) {
+                 const float *pose, const float *fov_v, void *stream) {
     MarchArgs a;
     int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
                          entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
     if (!out_rgba) return DR_EINVAL;
-    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
-    a.img_W = img_W; a.row0 = row0;
+    if (!band_fits(W, img_W, row0) || !pose_fits(pose, fov_v)) return DR_EINVAL;
+    a.img_W = img_W; a.row0 = row0; a.pose = pose; a.fov_v = fov_v;
     if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
     const int hints = variant & ~0xff;
     variant &= 0xff;
@@ -199,6 +211,17 @@ int dr_march_fwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     return launch_march_fwd_baseline(a, (hipStream_t)stream);
 }
 
+int dr_march_fwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                 int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                 const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                 int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, int mode, int variant,
+                 float *out_rgba, int32_t *steps, void *workspace, size_t workspace_bytes, int img_W, int row0,
+                      void *stream) {
+    return dr_march_fwd_rows_pose(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry,
+                                  exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, mode,
+                                  variant, out_rgba, steps, workspace, workspace_bytes, img_W, row0, nullptr, nullptr, stream);
+}
+
 int dr_march_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                  int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
                  const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
@@ -218,21 +241,21 @@ int dr_march_bwd_variant(int n_views, int W, int H, int VX, int VY, int VZ, int 
     return fast ? DR_VARIANT_AUTO : DR_VARIANT_BASELINE;
 }
 
-int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+int dr_march_bwd_rows_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                  int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
                  const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
                  int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, int variant,
                  const float *grad_out, const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz,
                  int64_t dvol_view_stride, float *d_tf, int64_t dtf_view_stride, void *workspace,
-                 size_t workspace_bytes, int img_W, int row0, void *stream) {
+                 size_t workspace_bytes, int img_W, int row0, const float *pose, const float *fov_v, void *stream) {
     MarchArgs a;
     int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
                          entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
     rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf, dtf_view_stride);
     if (rc) return rc;
-    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
-    a.img_W = img_W; a.row0 = row0;
+    if (!band_fits(W, img_W, row0) || !pose_fits(pose, fov_v)) return DR_EINVAL;
+    a.img_W = img_W; a.row0 = row0; a.pose = pose; a.fov_v = fov_v;
     const int bwd_flags = variant & ~0xff;
     variant &= 0xff;
     if (bwd_flags & ~(DR_COUNT_EVALUATED | DR_TAPE_TF)) return DR_EINVAL;
@@ -252,6 +275,19 @@ int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     return launch_march_bwd_baseline(a, (hipStream_t)stream);
 }
 
+int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                 int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                 const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                 int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, int variant,
+                 const float *grad_out, const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz,
+                 int64_t dvol_view_stride, float *d_tf, int64_t dtf_view_stride, void *workspace,
+                 size_t workspace_bytes, int img_W, int row0, void *stream) {
+    return dr_march_bwd_rows_pose(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry,
+                                  exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, variant,
+                                  grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf, dtf_view_stride, workspace,
+                                  workspace_bytes, img_W, row0, nullptr, nullptr, stream);
+}
+
 int dr_march_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                  int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
                  const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
@@ -265,24 +301,50 @@ int dr_march_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t
                              workspace, workspace_bytes, W, 0, stream);
 }
 
+// dr_march_bwd_cam (pose null: d_cam [n_views][3]) and dr_march_bwd_pose (d_cam [n_views][10]): one implementation
+static int march_bwd_camera(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                            int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                            const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                            int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed,
+                            uint32_t view_base, int img_W, int row0, const int32_t *steps, const float *grad_out,
+                            const float *out_rgba, const float *pose, const float *fov_v, double *d_cam, float *d_cam_ray,
+                            void *stream) {
+    MarchArgs a;
+    int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
+                         entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!steps || !grad_out || !out_rgba || !d_cam) return DR_EINVAL;
+    if (!band_fits(W, img_W, row0) || !pose_fits(pose, fov_v)) return DR_EINVAL;
+    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
+    a.img_W = img_W; a.row0 = row0; a.mode = DR_MODE_DIFF; a.pose = pose; a.fov_v = fov_v;
+    a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    CamArgs c;
+    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    return launch_on(vol, launch_camera_grad, a, c, (hipStream_t)stream);
+}
+
 int dr_march_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                      int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
                      const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
                      int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed,
                      uint32_t view_base, int img_W, int row0, const int32_t *steps, const float *grad_out,
                      const float *out_rgba, double *d_cam, float *d_cam_ray, void *stream) {
-    MarchArgs a;
-    int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
-                         entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
-    if (rc) return rc;
-    if (!steps || !grad_out || !out_rgba || !d_cam) return DR_EINVAL;
-    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
-    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
-    a.img_W = img_W; a.row0 = row0; a.mode = DR_MODE_DIFF;
-    a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
-    CamArgs c;
-    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
-    return launch_on(vol, launch_camera_grad, a, c, (hipStream_t)stream);
+    return march_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
+                            rays, nsamp, n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, jitter_seed, view_base,
+                            img_W, row0, steps, grad_out, out_rgba, nullptr, nullptr, d_cam, d_cam_ray, stream);
+}
+
+int dr_march_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                      int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                      const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                      int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed,
+                      uint32_t view_base, int img_W, int row0, const int32_t *steps, const float *grad_out,
+                      const float *out_rgba, const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray,
+                      void *stream) {
+    if (!pose) return DR_EINVAL;
+    return march_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
+                            rays, nsamp, n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, jitter_seed, view_base,
+                            img_W, row0, steps, grad_out, out_rgba, pose, fov_v, d_pose, d_pose_ray, stream);
 }
 
 int dr_mse_loss_grad(const float *out_rgba, const float *reference, int64_t n, float inv_norm, float *grad_out,
@@ -560,21 +622,45 @@ int dr_project_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64
     return launch_on(vol, launch_project_bwd, a, q, (hipStream_t)stream);
 }
 
-int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
-                       int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
-                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, double fov_rad,
-                       double near_plane, uint32_t jitter_seed, uint32_t view_base, const float *grad_out,
-                       const int32_t *arg_max, double *d_cam, float *d_cam_ray, void *stream) {
+// dr_project_bwd_cam (pose null) and dr_project_bwd_pose: one implementation
+static int project_bwd_camera(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                              int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                              const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, double fov_rad,
+                              double near_plane, uint32_t jitter_seed, uint32_t view_base, const float *grad_out,
+                              const int32_t *arg_max, const float *pose, const float *fov_v, double *d_cam, float *d_cam_ray,
+                              void *stream) {
     MarchArgs a;
     ProjArgs q;
     int rc = fill_proj(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
                        W, H, max_samples, mode, arg_max);
     if (rc) return rc;
-    if (!grad_out || !d_cam) return DR_EINVAL;
+    if (!grad_out || !d_cam || !pose_fits(pose, fov_v)) return DR_EINVAL;
     if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
-    a.grad_out = grad_out; a.mode = DR_MODE_DIFF; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    a.grad_out = grad_out; a.mode = DR_MODE_DIFF; a.fov_rad = fov_rad; a.near_plane = near_plane; a.pose = pose; a.fov_v = fov_v;
     q.jitter_seed = jitter_seed; q.view_base = view_base; q.d_cam = d_cam; q.d_cam_ray = d_cam_ray;
     return launch_on(vol, launch_project_bwd_cam, a, q, (hipStream_t)stream);
+}
+
+int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                       int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, double fov_rad,
+                       double near_plane, uint32_t jitter_seed, uint32_t view_base, const float *grad_out,
+                       const int32_t *arg_max, double *d_cam, float *d_cam_ray, void *stream) {
+    return project_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views, W,
+                              H, max_samples, mode, fov_rad, near_plane, jitter_seed, view_base, grad_out, arg_max, nullptr,
+                              nullptr, d_cam, d_cam_ray, stream);
+}
+
+int dr_project_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                        int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                        const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode, double fov_rad,
+                        double near_plane, uint32_t jitter_seed, uint32_t view_base, const float *grad_out,
+                        const int32_t *arg_max, const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray,
+                        void *stream) {
+    if (!pose) return DR_EINVAL;
+    return project_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views, W,
+                              H, max_samples, mode, fov_rad, near_plane, jitter_seed, view_base, grad_out, arg_max, pose, fov_v,
+                              d_pose, d_pose_ray, stream);
 }
 
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,

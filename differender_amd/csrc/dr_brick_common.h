@@ -26,6 +26,8 @@ struct BrickParams {
     int W, H, S; float sr, inv_sr;
     int imgW, row0;      // band of a wider image (see MarchArgs)
     float near_, near_w, near_h;
+    const float *pose, *fov_v;   // free camera, nullable: [view][9] look_from, look_at, up; [view] fov in radians
+    double near_d, aspect;       // ... the near plane and imgW / H as doubles, for a view's own extents
     BrickGrid g;
     float4 *seg_rgba;    // [view][NL][NP]: F1 partial composite, then (F2) prefix before the segment
     uint16_t *seg_cnt;   // [view][NL][NP]: samples of the ray inside the brick of that layer (low 15 bits, saturating at 32767: a
@@ -129,9 +131,31 @@ __device__ __forceinline__ f3 cross3b(f3 a, f3 b) {
     return make_f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
 
+// The pinhole model of a view (VR.py:127-151): its basis and near-plane extents. The fixed camera looks at the origin with
+// up = +y and the launch's extents; a pose brings its own look_at and up and, with fov_v, its own extents --
+// ray_setup.hip's statements, so that the rectangles and the line pre-test follow the rays the buffers hold.
+template <typename VT>
+__device__ __forceinline__ void view_basis(const BrickParams<VT> &P, int view, f3 cam, f3 &vdir, f3 &right, f3 &up, float &near_w,
+                                           float &near_h) {
+    near_w = P.near_w; near_h = P.near_h;
+    if (P.pose) {   // uniform
+        const float *ps = P.pose + 9 * view;
+        vdir = normalized3(make_f3(ps[3] - cam.x, ps[4] - cam.y, ps[5] - cam.z));
+        right = normalized3(cross3b(vdir, make_f3(ps[6], ps[7], ps[8])));
+        if (P.fov_v) {
+            const double h = 2.0 * tan((double)P.fov_v[view]) * P.near_d;
+            near_h = (float)h; near_w = (float)(h * P.aspect);
+        }
+    } else {
+        vdir = normalized3(make_f3(-cam.x, -cam.y, -cam.z));
+        right = normalized3(cross3b(vdir, make_f3(0.f, 1.f, 0.f)));
+    }
+    up = normalized3(cross3b(right, vdir));
+}
+
 // Brick geometry + its projected pixel rectangle (pinhole model of VR.py:127-151).
 template <typename VT>
-__device__ __forceinline__ void brick_setup(const BrickParams<VT> &P, int b, f3 cam, BrickCtx &c) {
+__device__ __forceinline__ void brick_setup(const BrickParams<VT> &P, int b, int view, f3 cam, BrickCtx &c) {
     const BrickGrid &g = P.g;
     c.bz = b % g.NBz; c.by = (b / g.NBz) % g.NBy; c.bx = b / (g.NBz * g.NBy);
     c.ox = c.bx * BRK - 1; c.oy = c.by * BRK - 1; c.oz = c.bz * BRK - 1;
@@ -147,9 +171,9 @@ __device__ __forceinline__ void brick_setup(const BrickParams<VT> &P, int b, f3 
         if (bb[k] == nb[k] - 1) hi = 1.0f;
         c.lo[k] = lo - BRICK_EPS; c.hi[k] = hi + BRICK_EPS;
     }
-    const f3 vdir = normalized3(make_f3(-cam.x, -cam.y, -cam.z));
-    const f3 right = normalized3(cross3b(vdir, make_f3(0.f, 1.f, 0.f)));
-    const f3 up = normalized3(cross3b(right, vdir));
+    f3 vdir, right, up;
+    float near_w, near_h;
+    view_basis(P, view, cam, vdir, right, up, near_w, near_h);
     // Which pixels' LINES (the reference marches from tmin even when it is negative: a camera inside the volume sees
     // samples behind the eye, VR.py:28-53) can meet the brick? The pinhole map X -> (u, v) is the same central projection
     // on both sides of the eye, so the part of the brick in front of it (depth >= eps) and the part behind it
@@ -159,7 +183,7 @@ __device__ __forceinline__ void brick_setup(const BrickParams<VT> &P, int b, f3 
     // spacing of any line; a miss there would be caught by the per-ray sample-count check.
     float pxmin = 1e30f, pxmax = -1e30f, pymin = 1e30f, pymax = -1e30f;
     const float eps = 1e-3f;
-    const float ku = P.near_ / P.near_w, kv = P.near_ / P.near_h;
+    const float ku = P.near_ / near_w, kv = P.near_ / near_h;
     f3 dk[8];
     float dep[8], du[8], dv[8];
     for (int k = 0; k < 8; ++k) {
@@ -233,6 +257,7 @@ static inline unsigned int ws_fingerprint(const MarchArgs &a) {
     mix((unsigned long long)a.vol_vs);
     mix((unsigned long long)(uintptr_t)a.vol); mix((unsigned long long)(uintptr_t)a.entry); mix((unsigned long long)(uintptr_t)a.exit_);
     mix((unsigned long long)(uintptr_t)a.rays); mix((unsigned long long)(uintptr_t)a.nsamp);
+    mix((unsigned long long)(a.pose != nullptr)); mix((unsigned long long)(a.fov_v != nullptr));
     // (not the camera's address: hosts hand over `cam.contiguous()` -- a fresh temporary per call for an expanded or
     //  converted look_from -- and a backward that did not recognise its own forward would silently run 10-40 x slower;
     //  the ray buffers, which are derived from the camera, identify the call)
@@ -303,7 +328,7 @@ static __global__ __launch_bounds__(256) void brick_ctx_kernel(BrickParams<VT> P
     if (b >= nbricks) return;
     const f3 cam = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
     BrickCtx c;
-    brick_setup(P, b, cam, c);
+    brick_setup(P, b, view, cam, c);
     BrickCtxRec r;
     r.bx = c.bx; r.by = c.by; r.bz = c.bz; r.layer = c.layer;
     for (int k = 0; k < 3; ++k) { r.lo[k] = c.lo[k]; r.hi[k] = c.hi[k]; }
@@ -729,6 +754,7 @@ static inline BrickParams<VT> make_brick_params(const MarchArgs &a, const Worksp
     P.imgW = a.img_W > 0 ? a.img_W : a.W; P.row0 = a.img_W > 0 ? a.row0 : 0;
     const double near_h = 2.0 * tan(a.fov_rad) * a.near_plane;
     P.near_ = (float)a.near_plane; P.near_h = (float)near_h; P.near_w = (float)(near_h * ((double)P.imgW / (double)a.H));
+    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)P.imgW / (double)a.H;
     P.g = make_brick_grid(a.VX, a.VY, a.VZ);
 
     P.seg_rgba = w.seg_rgba; P.seg_cnt = w.seg_cnt; P.rayflag = w.rayflag; P.stats = w.stats; P.vflags = w.vflags; P.n_views = a.n_views; P.ws_steps = w.ws_steps; P.fin = w.fin; P.exact_list = w.exact_list; P.seg_tiny = w.seg_tiny; P.dtf64 = w.dtf64; P.tape = nullptr; P.tape_stride = 0; P.unlit = w.unlit; P.lm_words = 0;

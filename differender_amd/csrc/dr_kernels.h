@@ -30,9 +30,13 @@ struct MarchArgs {
     int hints;                    // DR_HINT_* bits of the forward call
     int use_live;                 // forward: per-ray live sample counts are available (alpha pre-pass)
     int pp_l0, pp_l1, pp_first;   // alpha pre-pass phase: brick layers [pp_l0, pp_l1); pp_first: no earlier phase
+    // free camera; null: the fixed one (look at the origin, up = +y, the scalar fov_rad)
+    const float *pose;            // [n_views][9] look_from, look_at, up; look_from equals cam
+    const float *fov_v;           // [n_views] fov in radians, nullable: fov_rad for every view
 };
 
-hipError_t launch_ray_setup(const float *cam, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
+// pose null: cam [n_views][3] and the fixed camera; else pose / fov_v as in MarchArgs, and cam is not read
+hipError_t launch_ray_setup(const float *cam, const float *pose, const float *fov_v, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
                             double fov_rad, double near_plane, float sr, uint32_t jitter_seed, uint32_t view_base,
                             float *entry, float *exit_, float *rays, int32_t *nsamp, hipStream_t stream);
 
@@ -65,8 +69,8 @@ int launch_march_bwd_flat(const MarchArgs &a, hipStream_t stream);
 struct CamArgs {
     uint32_t jitter_seed, view_base;
     const int32_t *steps;   // the forward's live samples per ray
-    double *d_cam;          // [n_views][3], accumulated
-    float *d_cam_ray;       // [n_views][W][H][3] per-ray contributions, nullable
+    double *d_cam;          // [n_views][3], accumulated ([n_views][10] with MarchArgs::pose: look_from, look_at, up, fov_rad)
+    float *d_cam_ray;       // [n_views][W][H][3] per-ray contributions, nullable ([..][10] with MarchArgs::pose)
 };
 // weak: the C entry (capi.o) must load in a library linked from the other objects alone (tests/test_abi.py's what-if build)
 __attribute__((weak)) int launch_camera_grad(const MarchArgs &a, const CamArgs &c, hipStream_t stream);
@@ -155,8 +159,8 @@ struct ProjArgs {
     int mode, variant;                 // DR_PROJ_*; DR_VARIANT_AUTO (windowed SUM backward) or DR_VARIANT_BASELINE
     int32_t *arg_max;                  // MAX: [view][W][H], written by the forward, read by the backwards
     uint32_t jitter_seed, view_base;   // camera backward
-    double *d_cam;                     // [n_views][3], accumulated
-    float *d_cam_ray;                  // [n_views][W][H][3] per-ray contributions, nullable
+    double *d_cam;                     // [n_views][3], accumulated ([n_views][10] with MarchArgs::pose)
+    float *d_cam_ray;                  // [n_views][W][H][3] per-ray contributions, nullable ([..][10] with MarchArgs::pose)
 };
 // weak, as launch_camera_grad: capi.o must load in a library linked without projection.o
 __attribute__((weak)) int launch_project_fwd(const MarchArgs &a, const ProjArgs &q, hipStream_t stream);

@@ -266,16 +266,16 @@ constexpr size_t ITEM_EXTRA_LDS = (size_t)ITEM_MAX_CAND * 2 + 16;
 // of pixel (i, j) runs along dn + u * rw + v * uh.
 struct CamBasis { f3 dn, rw, uh; bool heavy; };
 template <typename VT>
-__device__ __forceinline__ CamBasis make_cam_basis(const BrickParams<VT> &P, f3 cam, bool heavy) {
+__device__ __forceinline__ CamBasis make_cam_basis(const BrickParams<VT> &P, int view, f3 cam, bool heavy) {
     CamBasis b;
     b.heavy = heavy;
     if (!heavy) { b.dn = b.rw = b.uh = make_f3(0.f, 0.f, 0.f); return b; }
-    const f3 vdir = normalized3(make_f3(-cam.x, -cam.y, -cam.z));
-    const f3 right = normalized3(cross3b(vdir, make_f3(0.f, 1.f, 0.f)));
-    const f3 up = normalized3(cross3b(right, vdir));
+    f3 vdir, right, up;
+    float near_w, near_h;
+    view_basis(P, view, cam, vdir, right, up, near_w, near_h);   // the pose's basis when there is one
     b.dn = make_f3(P.near_ * vdir.x, P.near_ * vdir.y, P.near_ * vdir.z);
-    b.rw = make_f3(P.near_w * right.x, P.near_w * right.y, P.near_w * right.z);
-    b.uh = make_f3(P.near_h * up.x, P.near_h * up.y, P.near_h * up.z);
+    b.rw = make_f3(near_w * right.x, near_w * right.y, near_w * right.z);
+    b.uh = make_f3(near_h * up.x, near_h * up.y, near_h * up.z);
     return b;
 }
 // does the LINE cam + t * d (any t) meet the brick's (slack-widened) box?
@@ -618,7 +618,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
         int *nhit = reinterpret_cast<int *>(hl + ITEM_MAX_CAND);
         if (threadIdx.x == 0) *nhit = 0;
         __syncthreads();
-        const CamBasis cbasis = make_cam_basis(P, cam, true);
+        const CamBasis cbasis = make_cam_basis(P, view, cam, true);
         const int nj = c.j1 - c.j0 + 1;
         const float rnj = __builtin_amdgcn_rcpf((float)nj);
         for (int c0 = c_lo; c0 < ncand; c0 += FNT) {  // uniform

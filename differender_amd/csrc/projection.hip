@@ -19,6 +19,8 @@ struct ProjParams : RayParams<VT> {
     float near_, near_w, near_h;    // camera backward
     uint32_t jitter_seed, view_base;
     double *d_cam; float *d_cam_ray;
+    const float *pose, *fov_v;      // camera backward of the free camera, as CamParams of camera_grad.hip
+    double near_d, aspect;
 };
 
 // samples of a ray (n <= 1: none, as H6)
@@ -263,11 +265,14 @@ __global__ __launch_bounds__(256) void project_bwd_window_kernel(ProjParams<VT> 
 //                 [+ g (sum mu_s) (grad tmax - grad entry) / n   for SUM: D's own dependence on the camera],
 //   grad t0 = A grad tmin + (1-A) grad tmax, A = (1 - u/n)(1 - 0.5/n), grad entry = grad tmin + (u/n)(grad tmax - grad tmin).
 // Sums in f32 per ray, f64 per workgroup (LDS), one f64 atomic per component per workgroup.
-template <typename VT, int MODE>
+// POSE: the ten pose gradients of the free camera instead (dr_camera.h: pose_ray_grad, pose_reduce) -- the same sums, with the
+// weights of grad tmin and grad tmax collected: coef s0 A - E and coef (s0 (1 - A) + s1) + E, E = g (sum mu_s) (1 - u/n) / n.
+template <typename VT, int MODE, bool POSE>
 __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
     __shared__ double red[3][256];
     const int view = blockIdx.y;
     f3 dcam = make_f3(0.f, 0.f, 0.f);
+    PoseGrad dpose = pose_zero();
     int i, j;
     const bool in_img = tile_pixel(P.W, P.H, i, j);
     const size_t p = ((size_t)view * P.W + i) * P.H + j;
@@ -303,25 +308,36 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
             s0 = fmaf(1.0f - f, gv, s0);
             s1 = fmaf(f, gv, s1);
         }
-        // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw (a projection is never a band)
-        M3 J;
-        f3 g_tmin, g_tmax, g_t0;
-        float u;
-        camera_ray_tail(lf, vd, i, P.W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed, P.view_base + (uint32_t)view, J,
-                        g_tmin, g_tmax, g_t0, u);
-        const float nf = (float)rg.n;
-        f3 dpos = f3_add(sP, mul_t(J, sTP));
-        dpos = f3_fma(s0, g_t0, dpos);
-        dpos = f3_fma(s1, g_tmax, dpos);
-        dcam = f3_scale(coef, dpos);
-        if (MODE == DR_PROJ_SUM && m > 0) {
-            const f3 g_entry = f3_fma(u / nf, f3_add(g_tmax, f3_scale(-1.0f, g_tmin)), g_tmin);
-            dcam = f3_fma((g * smu) / nf, f3_add(g_tmax, f3_scale(-1.0f, g_entry)), dcam);
+        if (POSE) {
+            // once per ray: the ten pose gradients from the same sums (dr_camera.h; a projection is never a band), then D5
+            const PoseRay q = pose_ray(P.pose, P.fov_v, view, P.near_d, P.aspect, P.near_w, P.near_h, i, P.W, j, P.H, rg.n,
+                                       P.jitter_seed, P.view_base + (uint32_t)view);
+            const float nf = (float)rg.n;
+            const float E = (MODE == DR_PROJ_SUM && m > 0) ? ((g * smu) / nf) * (1.0f - q.jit / nf) : 0.0f;
+            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.near_, f3_scale(coef, sP), f3_scale(coef, sTP), coef * (s0 * q.A) - E,
+                                              coef * fmaf(s0, 1.0f - q.A, s1) + E));
+        } else {
+            // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw (a projection is never a band)
+            M3 J;
+            f3 g_tmin, g_tmax, g_t0;
+            float u;
+            camera_ray_tail(lf, vd, i, P.W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed, P.view_base + (uint32_t)view, J,
+                            g_tmin, g_tmax, g_t0, u);
+            const float nf = (float)rg.n;
+            f3 dpos = f3_add(sP, mul_t(J, sTP));
+            dpos = f3_fma(s0, g_t0, dpos);
+            dpos = f3_fma(s1, g_tmax, dpos);
+            dcam = f3_scale(coef, dpos);
+            if (MODE == DR_PROJ_SUM && m > 0) {
+                const f3 g_entry = f3_fma(u / nf, f3_add(g_tmax, f3_scale(-1.0f, g_tmin)), g_tmin);
+                dcam = f3_fma((g * smu) / nf, f3_add(g_tmax, f3_scale(-1.0f, g_entry)), dcam);
+            }
+            // D5: a NaN ray contributes nothing, infinities are clamped
+            dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
         }
-        // D5: a NaN ray contributes nothing, infinities are clamped
-        dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
     }
-    camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    if (POSE) pose_reduce(dpose, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    else camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
 }
 
 template <typename VT>
@@ -331,6 +347,7 @@ static ProjParams<VT> proj_params(const MarchArgs &a, const ProjArgs &q) {
     near_plane_extents(a.fov_rad, a.near_plane, a.img_W, a.H, P.near_, P.near_w, P.near_h);   // (fill_proj: img_W = W)
     P.jitter_seed = q.jitter_seed; P.view_base = q.view_base;
     P.d_cam = q.d_cam; P.d_cam_ray = q.d_cam_ray;
+    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)a.img_W / (double)a.H;
     return P;
 }
 
@@ -358,8 +375,11 @@ static int bwd_dispatch(const MarchArgs &a, const ProjArgs &q, hipStream_t strea
 template <typename VT>
 static int cam_dispatch(const MarchArgs &a, const ProjArgs &q, hipStream_t stream) {
     const ProjParams<VT> P = proj_params<VT>(a, q);
-    return launch_tiles(q.mode == DR_PROJ_SUM ? project_cam_kernel<VT, DR_PROJ_SUM> : project_cam_kernel<VT, DR_PROJ_MAX>, a, 0,
-                        stream, P);
+    if (a.pose)
+        return launch_tiles(q.mode == DR_PROJ_SUM ? project_cam_kernel<VT, DR_PROJ_SUM, true> : project_cam_kernel<VT, DR_PROJ_MAX, true>,
+                            a, 0, stream, P);
+    return launch_tiles(q.mode == DR_PROJ_SUM ? project_cam_kernel<VT, DR_PROJ_SUM, false> : project_cam_kernel<VT, DR_PROJ_MAX, false>,
+                        a, 0, stream, P);
 }
 
 int launch_project_fwd(const MarchArgs &a, const ProjArgs &q, hipStream_t stream) {

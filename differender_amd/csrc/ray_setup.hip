@@ -13,6 +13,8 @@ namespace dr {
 
 struct RaySetupParams {
     const float *cam;  // [views][3]
+    const float *pose, *fov_v;  // POSE: [views][9] look_from, look_at, up; [views] fov in radians, nullable
+    double near_d, aspect;      // ... the near plane and img_W / H as doubles, for the per-view extents
     int n_views, W, H;
     int img_W, row0;   // band: buffer row i is image row row0 + i of img_W
     float near_, near_w, near_h, vol_diag, sr;
@@ -26,6 +28,10 @@ __device__ __forceinline__ f3 cross3(f3 a, f3 b) {
 }
 
 // One thread per pixel; a wave covers an 8x8 pixel tile (the reference's image tile, VR.py:104-112).
+// POSE: the free camera of DESIGN.md D15 -- look_from, look_at and up of the view come from P.pose and, with P.fov_v, the
+// near-plane extents are formed per view as launch_ray_setup forms them on the host (doubles, rounded once). Every statement
+// after that is the fixed camera's, in its order: look_at = 0, up = e_y and the scalar fov give its rays bit for bit.
+template <bool POSE>
 __global__ __launch_bounds__(256) void ray_setup_kernel(RaySetupParams P) {
     const int tiles_j = (P.H + 7) >> 3;
     const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -35,17 +41,28 @@ __global__ __launch_bounds__(256) void ray_setup_kernel(RaySetupParams P) {
     const int view = blockIdx.y;
     if (i >= P.W || j >= P.H) return;
 
-    const float *cam = P.cam + 3 * view;
+    const float *cam = POSE ? P.pose + 9 * view : P.cam + 3 * view;
     const f3 lf = make_f3(cam[0], cam[1], cam[2]);
-    const f3 view_dir = normalized3(make_f3(-lf.x, -lf.y, -lf.z));
+    f3 up = make_f3(0.f, 1.f, 0.f);
+    f3 view_dir;
+    float near_w = P.near_w, near_h = P.near_h;
+    if (POSE) {
+        view_dir = normalized3(make_f3(cam[3] - lf.x, cam[4] - lf.y, cam[5] - lf.z));
+        up = make_f3(cam[6], cam[7], cam[8]);
+        if (P.fov_v) {
+            const double h = 2.0 * tan((double)P.fov_v[view]) * P.near_d;
+            near_h = (float)h; near_w = (float)(h * P.aspect);
+        }
+    } else {
+        view_dir = normalized3(make_f3(-lf.x, -lf.y, -lf.z));
+    }
     const float x = ((float)(i + P.row0) + 0.5f) / (float)P.img_W;
     const float y = ((float)j + 0.5f) / (float)P.H;
     const float u = x - 0.5f, v = y - 0.5f;
-    f3 up = make_f3(0.f, 1.f, 0.f);
     const f3 right = normalized3(cross3(view_dir, up));
     up = normalized3(cross3(right, view_dir));
     const f3 near_m = make_f3(lf.x + P.near_ * view_dir.x, lf.y + P.near_ * view_dir.y, lf.z + P.near_ * view_dir.z);
-    const float uw = u * P.near_w, vh = v * P.near_h;
+    const float uw = u * near_w, vh = v * near_h;
     const f3 near_pos = make_f3((near_m.x + uw * right.x) + vh * up.x, (near_m.y + uw * right.y) + vh * up.y,
                                 (near_m.z + uw * right.z) + vh * up.z);
     const f3 vd = normalized3(make_f3(near_pos.x - lf.x, near_pos.y - lf.y, near_pos.z - lf.z));
@@ -74,21 +91,22 @@ __global__ __launch_bounds__(256) void ray_setup_kernel(RaySetupParams P) {
     P.nsamp[p] = (int32_t)n_samples;
 }
 
-hipError_t launch_ray_setup(const float *cam, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
+hipError_t launch_ray_setup(const float *cam, const float *pose, const float *fov_v, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
                             double fov_rad, double near_plane, float sr, uint32_t jitter_seed, uint32_t view_base,
                             float *entry, float *exit_, float *rays, int32_t *nsamp, hipStream_t stream) {
     RaySetupParams P;
     // VR.py:146-147: Python doubles, then rounded once (ti.tan of a Python float is math.tan)
     const double near_h = 2.0 * tan(fov_rad) * near_plane;
     const double near_w = near_h * ((double)img_W / (double)H);
-    P.cam = cam; P.n_views = n_views; P.W = W; P.H = H; P.img_W = img_W; P.row0 = row0;
+    P.cam = cam; P.pose = pose; P.fov_v = fov_v; P.near_d = near_plane; P.aspect = (double)img_W / (double)H;
+    P.n_views = n_views; P.W = W; P.H = H; P.img_W = img_W; P.row0 = row0;
     P.near_ = (float)near_plane; P.near_w = (float)near_w; P.near_h = (float)near_h;
     P.vol_diag = (float)sqrt((double)(VX - 1) * (VX - 1) + (double)(VY - 1) * (VY - 1) + (double)(VZ - 1) * (VZ - 1));
     P.sr = sr; P.jitter_seed = jitter_seed; P.view_base = view_base;
     P.entry = entry; P.exit_ = exit_; P.rays = rays; P.nsamp = nsamp;
     const int tiles = ((W + 7) / 8) * ((H + 7) / 8);
     dim3 grid((tiles + 3) / 4, n_views);
-    hipLaunchKernelGGL(ray_setup_kernel, grid, dim3(256), 0, stream, P);
+    hipLaunchKernelGGL(pose ? ray_setup_kernel<true> : ray_setup_kernel<false>, grid, dim3(256), 0, stream, P);
     return hipGetLastError();
 }
 

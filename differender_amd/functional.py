@@ -14,7 +14,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "march_fwd", "march_bwd", "march_bwd_cam", "march_tf2d_fwd", "march_tf2d_bwd", "march_rgba_fwd", "march_rgba_bwd", "project_fwd", "project_bwd",
+__all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd", "march_bwd_cam", "march_bwd_pose", "project_bwd_pose", "march_tf2d_fwd", "march_tf2d_bwd", "march_rgba_fwd", "march_rgba_bwd", "project_fwd", "project_bwd",
            "project_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
@@ -160,11 +160,58 @@ def _rows(rows, W):
     return img_w, row0
 
 
+def pack_pose(look_from, look_at=None, up=None):
+    """The (views, 9) float32 pose the kernels read -- look_from, look_at, up of every view -- from look_from
+    (views, 3) and look_at, up (views, 3), (3,) (shared by the views) or None (the origin, +y)."""
+    cam = look_from.reshape(-1, 3).to(torch.float32)
+    V = cam.shape[0]
+
+    def rows(t, default):
+        if t is None:
+            return cam.new_tensor(default).expand(V, 3)
+        t = t.to(device=cam.device, dtype=torch.float32).reshape(-1, 3)
+        if t.shape[0] not in (1, V):
+            raise ValueError(f"a pose entry has {t.shape[0]} rows, look_from {V}")
+        return t.expand(V, 3)
+
+    return torch.cat([cam, rows(look_at, (0.0, 0.0, 0.0)), rows(up, (0.0, 1.0, 0.0))], 1).contiguous()
+
+
+def _pose_args(pose, fov_v, V):
+    """A pose (views, 9) and its optional per-view fov in RADIANS (views,) as the float32 contiguous tensors the kernels read ->
+    (pose, fov_v, then their two C-ABI arguments). The caller keeps the tensors until its call has been issued."""
+    pose = pose.to(torch.float32).contiguous()
+    if pose.shape != (V, 9):
+        raise ValueError(f"pose must be (views, 9) = ({V}, 9): look_from, look_at, up; got {tuple(pose.shape)}")
+    if fov_v is not None:
+        fov_v = fov_v.to(device=pose.device, dtype=torch.float32).contiguous()
+        if fov_v.shape != (V,):
+            raise ValueError(f"fov_v must be (views,) = ({V},) radians, got {tuple(fov_v.shape)}")
+    return pose, fov_v, pose.data_ptr(), _ptr(fov_v)
+
+
+def ray_setup_pose(pose, out_shape, vol_shape, sampling_rate, fov_deg=30.0, near=0.1, jitter_seed=0, view_base=0, rows=None,
+                   fov_v=None):
+    """ray_setup for the free camera (dr_ray_setup_pose_rows): pose (views, 9) = look_from, look_at, up
+    (pack_pose); fov_v (views,) float32 RADIANS gives every view its own field of view, None takes fov_deg for all. The default
+    pose (look_at 0, up +y) without fov_v gives ray_setup's buffers bit for bit."""
+    return _ray_setup(None, pose, fov_v, out_shape, vol_shape, sampling_rate, fov_deg, near, jitter_seed, view_base, rows)
+
+
 def ray_setup(cam, out_shape, vol_shape, sampling_rate, fov_deg=30.0, near=0.1, jitter_seed=0, view_base=0, rows=None):
     """compute_entry_exit (VR.py:221-259) for cam (views,3) -> entry, exit (views,W,H), rays (views,W,H,3),
     n (views,W,H) int32. rows=(row0, image_rows) renders a band of a taller image (see distributed.shard_rows)."""
-    _require_gpu(cam, "look_from")
-    cam = cam.to(torch.float32).contiguous()
+    return _ray_setup(cam, None, None, out_shape, vol_shape, sampling_rate, fov_deg, near, jitter_seed, view_base, rows)
+
+
+def _ray_setup(cam, pose, fov_v, out_shape, vol_shape, sampling_rate, fov_deg, near, jitter_seed, view_base, rows):
+    if pose is not None:
+        _require_gpu(pose, "pose")
+        pose, fov_v, *pargs = _pose_args(pose, fov_v, pose.shape[0])
+        cam = pose
+    else:
+        _require_gpu(cam, "look_from")
+        cam = cam.to(torch.float32).contiguous()
     V = cam.shape[0]
     W, H = int(out_shape[0]), int(out_shape[1])
     dev = cam.device
@@ -173,12 +220,14 @@ def ray_setup(cam, out_shape, vol_shape, sampling_rate, fov_deg=30.0, near=0.1, 
     rays = torch.empty((V, W, H, 3), dtype=torch.float32, device=dev)
     n = torch.empty((V, W, H), dtype=torch.int32, device=dev)
     VX, VY, VZ = (int(s) for s in vol_shape)
+    args = (V, W, H, *_rows(rows, W), VX, VY, VZ, float(np.radians(fov_deg)), float(near), float(sampling_rate),
+            int(jitter_seed) & 0xFFFFFFFF, int(view_base), entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr())
     with torch.cuda.device(dev):
-        rc = N.lib().dr_ray_setup_rows(cam.data_ptr(), V, W, H, *_rows(rows, W), VX, VY, VZ,
-                                       float(np.radians(fov_deg)), float(near),
-                                       float(sampling_rate), int(jitter_seed) & 0xFFFFFFFF, int(view_base),
-                                       entry.data_ptr(), exit_.data_ptr(), rays.data_ptr(), n.data_ptr(), _stream())
-    N.check(rc, "dr_ray_setup_rows")
+        if pose is None:
+            rc = N.lib().dr_ray_setup_rows(cam.data_ptr(), *args, _stream())
+        else:
+            rc = N.lib().dr_ray_setup_pose_rows(None, *args, *pargs, _stream())
+    N.check(rc, "dr_ray_setup_rows" if pose is None else "dr_ray_setup_pose_rows")
     return entry, exit_, rays, n
 
 
@@ -203,11 +252,11 @@ def _bwd_images(grad_out, out):
     return grad_out.to(torch.float32).contiguous(), out.contiguous()
 
 
-def _cam_grad_buffers(V, W, H, device, per_ray):
-    """A camera backward's d_cam (views, 3), zeros in float64 for the workgroups' atomics, and the per-ray d_ray (views,W,H,3)
-    float32 (None when not wanted)."""
-    d_cam = torch.zeros((V, 3), dtype=torch.float64, device=device)
-    return d_cam, torch.empty((V, W, H, 3), dtype=torch.float32, device=device) if per_ray else None
+def _cam_grad_buffers(V, W, H, device, per_ray, k=3):
+    """A camera backward's d_cam (views, k), zeros in float64 for the workgroups' atomics, and the per-ray d_ray (views,W,H,k)
+    float32 (None when not wanted); k = 3 for look_from, 10 for a pose."""
+    d_cam = torch.zeros((V, k), dtype=torch.float64, device=device)
+    return d_cam, torch.empty((V, W, H, k), dtype=torch.float32, device=device) if per_ray else None
 
 
 def _cam_grad_result(d_cam, d_ray):
@@ -368,16 +417,27 @@ def termination_hints(tf, vol_shape, sampling_rate, max_samples, mode, alpha=lam
     return _hints.hints(tf, vol_shape, sampling_rate, max_samples, mode, alpha)
 
 
+def _pose_entry(name, pose, fov_v, V):
+    """The entry point `name` and (None, None), or `name`_pose and _pose_args' (pose, fov_v, their two C-ABI arguments)."""
+    if pose is None:
+        if fov_v is not None:
+            raise ValueError("fov_v comes with a pose")
+        return getattr(N.lib(), name), (None, None)
+    return getattr(N.lib(), name + "_pose"), _pose_args(pose, fov_v, V)
+
+
 def march_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, mode=N.DR_MODE_DIFF,
               variant=N.DR_VARIANT_AUTO, want_steps=True, fov_deg=30.0, near=0.1, workspace="auto", rows=None,
-              hints="auto", tape=False):
+              hints="auto", tape=False, pose=None, fov_v=None):
     """raycast + get_final_image (VR.py:261-306,363-372) or the nondiff pair (VR.py:308-361).
     Returns out (views,W,H,4) and steps (views,W,H) int32 (or None).
     workspace: a buffer from alloc_workspace() (keep it for march_bwd), "auto" to allocate a throw-away one,
     or None to force the baseline kernels.
     hints: "auto" (DR_HINT_* from the TF's largest alpha once it is known, see _TerminationHints), 0 / None, or explicit bits.
     tape: DR_TAPE_TF -- the caller will ask for the TF gradient only (march_bwd(want_vol=False, tape=True)); the workspace must come
-    from alloc_workspace(..., tape=(max_samples, sampling_rate)). Differentiable mode only; same image."""
+    from alloc_workspace(..., tape=(max_samples, sampling_rate)). Differentiable mode only; same image.
+    pose, fov_v: those of ray_setup_pose when the buffers come from it (cam: the pose's look_from, pose[:, :3]) -- the fast
+    kernels' brick geometry follows the camera's basis (dr_march_fwd_rows_pose); None: the fixed camera, as ever."""
     cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
     dev = vol.device
     out, steps = _fwd_buffers(V, W, H, dev, want_steps)
@@ -387,12 +447,13 @@ def march_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, m
         workspace = alloc_workspace(V, (W, H), vargs[2:5], targs[1], dev) if variant == N.DR_VARIANT_AUTO else None
     if isinstance(hints, str):
         hints = _hints.hints(tf, vargs[2:5], sampling_rate, max_samples, mode) if variant == N.DR_VARIANT_AUTO else 0
+    entry_point, pargs = _pose_entry("dr_march_fwd_rows", pose, fov_v, V)
     with torch.cuda.device(dev):
-        rc = N.lib().dr_march_fwd_rows(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
-                                       float(np.radians(fov_deg)), float(near), int(mode),
-                                       int(variant) | int(hints or 0) | (N.DR_TAPE_TF if tape else 0), out.data_ptr(),
-                                       _ptr(steps), *_ws_args(workspace), *_rows(rows, W), _stream())
-    N.check(rc, "dr_march_fwd_rows")
+        rc = entry_point(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
+                         float(np.radians(fov_deg)), float(near), int(mode),
+                         int(variant) | int(hints or 0) | (N.DR_TAPE_TF if tape else 0), out.data_ptr(),
+                         _ptr(steps), *_ws_args(workspace), *_rows(rows, W), *pargs[2:], _stream())
+    N.check(rc, "dr_march_fwd_rows" if pose is None else "dr_march_fwd_rows_pose")
     return out, steps
 
 
@@ -409,12 +470,13 @@ def _d_vol(vol, want):
 
 def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, grad_out, out, want_vol=True,
               want_tf=True, variant=N.DR_VARIANT_AUTO, fov_deg=30.0, near=0.1, workspace=None, rows=None, count_evaluated=False,
-              tape=False):
+              tape=False, pose=None, fov_v=None):
     """Adjoint of the differentiable march w.r.t. vol and tf (replaces raycast.grad, VR.py:460-461,470-471).
     Shared (un-batched) vol / tf receive one gradient accumulated over all views.
     workspace: the buffer the matching march_fwd filled (fast path); None runs the baseline kernels.
     count_evaluated: measurement only (DR_COUNT_EVALUATED; see evaluated_samples()).
-    tape: the forward was run with tape=True and only d_tf is wanted: the per-ray pass over the tape (csrc/tf_tape.hip)."""
+    tape: the forward was run with tape=True and only d_tf is wanted: the per-ray pass over the tape (csrc/tf_tape.hip).
+    pose, fov_v: those the forward was given."""
     if tape and want_vol:
         raise ValueError("tape=True serves the backward w.r.t. the transfer function alone (want_vol=False)")
     cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
@@ -429,18 +491,29 @@ def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, g
         dt = (d_tf.data_ptr(), d_tf.stride(0) if tf.ndim == 3 else 0)
     if not (want_vol or want_tf):
         return None, None
+    entry_point, pargs = _pose_entry("dr_march_bwd_rows", pose, fov_v, V)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_bwd_rows(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
-                                       float(np.radians(fov_deg)), float(near),
-                                       int(variant) | (N.DR_COUNT_EVALUATED if count_evaluated else 0) | (N.DR_TAPE_TF if tape else 0),
-                                       grad_out.data_ptr(), out.data_ptr(), *dv, *dt, *_ws_args(workspace),
-                                       *_rows(rows, W), _stream())
-    N.check(rc, "dr_march_bwd_rows")
+        rc = entry_point(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
+                         float(np.radians(fov_deg)), float(near),
+                         int(variant) | (N.DR_COUNT_EVALUATED if count_evaluated else 0) | (N.DR_TAPE_TF if tape else 0),
+                         grad_out.data_ptr(), out.data_ptr(), *dv, *dt, *_ws_args(workspace),
+                         *_rows(rows, W), *pargs[2:], _stream())
+    N.check(rc, "dr_march_bwd_rows" if pose is None else "dr_march_bwd_rows_pose")
     return d_vol, d_tf
 
 
+def march_bwd_pose(vol, tf, pose, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
+                   near=0.1, jitter_seed=0, view_base=0, rows=None, per_ray=False, fov_v=None):
+    """Gradient of the differentiable march w.r.t. the pose (views, 9) and the field of view (dr_march_bwd_pose):
+    march_bwd_cam for the free camera of ray_setup_pose, whose buffers, pose and fov_v these are. Returns d_pose (views, 10)
+    float32 -- d look_from, d look_at, d up, d fov PER RADIAN (of fov_v's entries, or of fov_deg's angle when fov_v is None) --
+    and, with per_ray=True, each ray's contribution (views, W, H, 10) as well."""
+    return march_bwd_cam(vol, tf, pose[:, :3], entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg,
+                         near, jitter_seed, view_base, rows, per_ray, pose=pose, fov_v=fov_v)
+
+
 def march_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
-                  near=0.1, jitter_seed=0, view_base=0, rows=None, per_ray=False):
+                  near=0.1, jitter_seed=0, view_base=0, rows=None, per_ray=False, pose=None, fov_v=None):
     """Gradient of the differentiable march w.r.t. the camera positions `cam` (views, 3) (dr_march_bwd_cam; the
     reference has none, VR.py:465). The ray buffers, `steps`, `out`, jitter_seed, view_base and rows are those of the forward
     (ray_setup + march_fwd). Returns d_cam (views, 3) float32 -- and, with per_ray=True, each ray's contribution
@@ -450,13 +523,17 @@ def march_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampl
     steps = steps.to(torch.int32).contiguous()
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
-    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray)
+    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray, 3 if pose is None else 10)
+    if pose is None:
+        entry_point, pargs = N.lib().dr_march_bwd_cam, ()
+    else:   # (march_bwd_pose)
+        entry_point, pargs = N.lib().dr_march_bwd_pose, _pose_args(pose, fov_v, V)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_bwd_cam(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
-                                      float(np.radians(fov_deg)), float(near), int(jitter_seed) & 0xFFFFFFFF, int(view_base),
-                                      *_rows(rows, W), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(), d_cam.data_ptr(),
-                                      _ptr(d_ray), _stream())
-    N.check(rc, "dr_march_bwd_cam")
+        rc = entry_point(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
+                         float(np.radians(fov_deg)), float(near), int(jitter_seed) & 0xFFFFFFFF, int(view_base),
+                         *_rows(rows, W), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(), *pargs[2:], d_cam.data_ptr(),
+                         _ptr(d_ray), _stream())
+    N.check(rc, "dr_march_bwd_cam" if pose is None else "dr_march_bwd_pose")
     return _cam_grad_result(d_cam, d_ray)
 
 
@@ -620,8 +697,17 @@ def project_bwd(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None, mod
     return d_vol
 
 
+def project_bwd_pose(vol, pose, entry, exit_, rays, n, grad_out, max_samples=None, mode="sum", arg_max=None, fov_deg=30.0,
+                     near=0.1, jitter_seed=0, view_base=0, per_ray=False, fov_v=None):
+    """d pose of sum(project_fwd(...) * grad_out) (dr_project_bwd_pose): project_bwd_cam for the free camera, as march_bwd_pose
+    is march_bwd_cam's. Returns d_pose (views, 10) float32 (the fov column per radian) -- and, with per_ray=True, each ray's
+    contribution (views, W, H, 10) as well."""
+    return project_bwd_cam(vol, pose[:, :3], entry, exit_, rays, n, grad_out, max_samples, mode, arg_max, fov_deg, near,
+                           jitter_seed, view_base, per_ray, pose=pose, fov_v=fov_v)
+
+
 def project_bwd_cam(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None, mode="sum", arg_max=None, fov_deg=30.0,
-                    near=0.1, jitter_seed=0, view_base=0, per_ray=False):
+                    near=0.1, jitter_seed=0, view_base=0, per_ray=False, pose=None, fov_v=None):
     """d look_from of sum(project_fwd(...) * grad_out) (dr_project_bwd_cam): cam (views, 3), the ray buffers, jitter_seed and
     view_base those of the forward's ray_setup. Returns d_cam (views, 3) float32 -- and, with per_ray=True, each ray's
     contribution (views, W, H, 3) as well."""
@@ -629,12 +715,16 @@ def project_bwd_cam(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None,
     arg, pargs = _proj_bwd_args(max_samples, mode, arg_max)
     grad_out = grad_out.to(torch.float32).contiguous()
     vargs = _vol_args(vol, V)
-    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray)
+    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray, 3 if pose is None else 10)
+    if pose is None:
+        entry_point, qargs = N.lib().dr_project_bwd_cam, ()
+    else:   # (project_bwd_pose)
+        entry_point, qargs = N.lib().dr_project_bwd_pose, _pose_args(pose, fov_v, V)
     with torch.cuda.device(vol.device):
-        rc = N.lib().dr_project_bwd_cam(*vargs, *rargs, *pargs, float(np.radians(fov_deg)), float(near),
-                                        int(jitter_seed) & 0xFFFFFFFF, int(view_base), grad_out.data_ptr(), _ptr(arg),
-                                        d_cam.data_ptr(), _ptr(d_ray), _stream())
-    N.check(rc, "dr_project_bwd_cam")
+        rc = entry_point(*vargs, *rargs, *pargs, float(np.radians(fov_deg)), float(near),
+                         int(jitter_seed) & 0xFFFFFFFF, int(view_base), grad_out.data_ptr(), _ptr(arg), *qargs[2:],
+                         d_cam.data_ptr(), _ptr(d_ray), _stream())
+    N.check(rc, "dr_project_bwd_cam" if pose is None else "dr_project_bwd_pose")
     return _cam_grad_result(d_cam, d_ray)
 
 

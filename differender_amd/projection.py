@@ -77,24 +77,31 @@ class Projector(L.RayModule):
         super().__init__(volume_shape, output_shape, float(sampling_rate), jitter, max_samples, fov, near, far)
         self.mode = mode
 
-    def _determine_batch(self, volume, look_from):
-        """-> (batched, vol ([BS,] W, D, H) view, look_from (BS, 3)); an un-batched volume is shared by all views."""
+    def _determine_batch(self, volume, look_from, pose=None):
+        """-> (batched, vol ([BS,] W, D, H) view, look_from (BS, 3)); an un-batched volume is shared by all views.
+        pose = (look_at, up, fov): they join the batch rule, and a fourth result holds them as rows per view."""
         if volume.ndim not in (4, 5) or look_from.ndim not in (1, 2):
             raise ValueError("expected volume ([BS,]1,D,H,W) and look_from ([BS,]3)")
         if volume.shape[-4] != 1 or look_from.shape[-1] != 3:
             raise ValueError(f"expected volume ([BS,]1,D,H,W) and look_from ([BS,]3); got {tuple(volume.shape)}, "
                              f"{tuple(look_from.shape)}")
         self._check_built_for(volume)
-        batched, _, lf = L.batch_rule(look_from, (volume, 5))
-        return batched, L.field_view(volume), lf
+        batched, _, lf, *posed = L.batch_rule(look_from, (volume, 5)) if pose is None else L.pose_rule(look_from, pose, (volume, 5))
+        return (batched, L.field_view(volume), lf, *posed)
 
     @staticmethod
     def _image(out, batched):
         """([BS,]W,H) -> ([BS,]1,H,W): the shared orientation at K = 1."""
         return L.image(out.unsqueeze(-1))
 
-    def forward(self, volume, look_from):
-        """volume ([BS,]1,D,H,W), look_from ([BS,]3) -> ([BS,]1,H,W)."""
+    def forward(self, volume, look_from, look_at=None, up=None, fov=None):
+        """volume ([BS,]1,D,H,W), look_from ([BS,]3) -> ([BS,]1,H,W).
+        look_at, up ([BS,]3), fov ([BS,] degrees): the free camera (pose.py) and its gradients, as
+        Raycaster.forward; all None: the fixed camera."""
+        if L.has_pose(look_at, up, fov):
+            from .pose import PoseProjectFunction
+            batched, vol, lf, pose = self._determine_batch(volume, look_from, (look_at, up, fov))
+            return self._image(PoseProjectFunction.apply(self, vol, lf, *pose, batched, self.jitter), batched)
         batched, vol, lf = self._determine_batch(volume, look_from)
         res = ProjectFunction.apply(self, vol, lf, batched, self.jitter)
         return self._image(res, batched)

@@ -36,8 +36,8 @@ class RgbaRaycastFunction(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, rc, volume, look_from, sampling_rate, batched, jitter=True):
-        volume, cam, _, rays = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near)
+    def forward(ctx, rc, volume, look_from, sampling_rate, batched, jitter=True, pose=None):
+        volume, cam, _, rays = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near, pose)[:4]
         out, steps = F.march_rgba_fwd(volume, cam, *rays, rc.max_samples, sampling_rate, N.DR_MODE_DIFF)
         ctx.save_for_backward(volume, cam, *rays, out)
         ctx.rc, ctx.sampling_rate, ctx.batched = rc, sampling_rate, batched
@@ -49,11 +49,11 @@ class RgbaRaycastFunction(torch.autograd.Function):
     def backward(ctx, grad_output):
         volume, cam, e, x, r, n, out = ctx.saved_tensors
         if not ctx.needs_input_grad[1]:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         g = grad_output if ctx.batched else grad_output[None]
         dv = F.march_rgba_bwd(volume, cam, e, x, r, n, ctx.rc.max_samples, ctx.sampling_rate, g, out)
         # the plain kernels propagate NaN like the reference: nan_to_num, as Tf2dRaycastFunction does
-        return None, torch.nan_to_num(dv), None, None, None, None
+        return None, torch.nan_to_num(dv), None, None, None, None, None
 
 
 class RaycasterRGBA(L.RayModule):
@@ -70,30 +70,41 @@ class RaycasterRGBA(L.RayModule):
             raise ValueError(f"max_samples must be >= 1, got {max_samples}")
         super().__init__(tuple(int(v) for v in volume_shape), output_shape, sampling_rate, jitter, max_samples, fov, near, far)
 
-    def _determine_batch(self, volume, look_from):
-        """-> (batched, vol ([BS,] 4, W, D, H) view, look_from (BS, 3)); an un-batched volume is shared by all views."""
+    def _determine_batch(self, volume, look_from, pose=None):
+        """-> (batched, vol ([BS,] 4, W, D, H) view, look_from (BS, 3)); an un-batched volume is shared by all views.
+        pose = (look_at, up, fov): they join the batch rule, and a fourth result holds them as rows per view."""
         if volume.ndim not in (4, 5) or look_from.ndim not in (1, 2):
             raise ValueError("expected volume ([BS,]4,D,H,W), look_from ([BS,]3)")
         if volume.shape[-4] != 4 or look_from.shape[-1] != 3:
             raise ValueError(f"expected volume ([BS,]4,D,H,W), look_from ([BS,]3); got {tuple(volume.shape)}, "
                              f"{tuple(look_from.shape)}")
         self._check_built_for(volume)
-        batched, _, lf = L.batch_rule(look_from, (volume, 5))
-        return batched, L.field_view_rgba(volume), lf
+        batched, _, lf, *posed = L.batch_rule(look_from, (volume, 5)) if pose is None else L.pose_rule(look_from, pose, (volume, 5))
+        return (batched, L.field_view_rgba(volume), lf, *posed)
 
-    def forward(self, volume, look_from):
-        """volume ([BS,]4,D,H,W), look_from ([BS,]3) -> ([BS,]4,H,W)."""
+    def forward(self, volume, look_from, look_at=None, up=None, fov=None):
+        """volume ([BS,]4,D,H,W), look_from ([BS,]3) -> ([BS,]4,H,W).
+        look_at, up ([BS,]3), fov ([BS,] degrees): the free camera for the image and the volume gradient; like
+        look_from they may not require grad. All None: the fixed camera."""
         if torch.is_grad_enabled() and look_from.requires_grad:
             raise ValueError("RaycasterRGBA has no gradient w.r.t. look_from: use volume_raycaster.Raycaster (scalar volume and "
                              "transfer function) for camera gradients, or pass look_from.detach()")
+        if L.has_pose(look_at, up, fov):
+            L.refuse_pose_grad("RaycasterRGBA", look_at=look_at, up=up, fov=fov)
+            batched, vol, lf, pose = self._determine_batch(volume, look_from, (look_at, up, fov))
+            return self._image(RgbaRaycastFunction.apply(self, vol, lf, self.sampling_rate, batched, self.jitter, pose), batched)
         batched, vol, lf = self._determine_batch(volume, look_from)
         res = RgbaRaycastFunction.apply(self, vol, lf, self.sampling_rate, batched, self.jitter)
         return self._image(res, batched)
 
-    def raycast_nondiff(self, volume, look_from, sampling_rate=None):
+    def raycast_nondiff(self, volume, look_from, sampling_rate=None, look_at=None, up=None, fov=None):
         """Non-differentiable render (never jittered); default rate 4x the module's, as Raycaster.raycast_nondiff."""
-        batched, vol, lf = self._determine_batch(volume, look_from)
-        with self._nondiff_rays(vol, lf, sampling_rate) as (sr, vol, cam, rays):
+        pose = None
+        if L.has_pose(look_at, up, fov):
+            batched, vol, lf, pose = self._determine_batch(volume, look_from, (look_at, up, fov))
+        else:
+            batched, vol, lf = self._determine_batch(volume, look_from)
+        with self._nondiff_rays(vol, lf, sampling_rate, pose) as (sr, vol, cam, rays, *_):
             out, steps = F.march_rgba_fwd(vol, cam, *rays, self.max_samples, sr, N.DR_MODE_NONDIFF)
             self._steps = L.unbatch(steps, batched)
             return L.image(L.unbatch(out, batched))

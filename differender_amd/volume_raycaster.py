@@ -333,14 +333,16 @@ class Raycaster(torch.nn.Module):
         self.vr = VolumeRaycaster(self.volume_shape, output_shape, max_samples=max_samples, tf_resolution=tf_shape,
                                   fov=fov, nearfar=(near, far))
 
-    def _determine_batch(self, volume, tf, look_from):
+    def _determine_batch(self, volume, tf, look_from, pose=None):
         """VR.py:551-571, without the copies: returns (batched, bs, vol, tf, lf) where vol is the
-        ([BS,] W, D, H) *view* of the input, tf is ([BS,] R, 4); un-batched inputs stay un-batched (shared)."""
+        ([BS,] W, D, H) *view* of the input, tf is ([BS,] R, 4); un-batched inputs stay un-batched (shared).
+        pose = (look_at, up, fov): they join the batch rule, and a sixth result holds them as rows per view (_layout.pose_rule)."""
         if volume.ndim not in (4, 5) or tf.ndim not in (2, 3) or look_from.ndim not in (1, 2):
             raise ValueError("expected volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3)")
-        batched, bs, lf = L.batch_rule(look_from, (volume, 5), (tf, 3))
+        inputs = ((volume, 5), (tf, 3))
+        batched, bs, lf, *posed = L.batch_rule(look_from, *inputs) if pose is None else L.pose_rule(look_from, pose, *inputs)
         # (the un-batched look_from stays (3,), as the reference hands it on)
-        return batched, bs, L.field_view(volume), tf.transpose(-1, -2), lf if batched else look_from
+        return (batched, bs, L.field_view(volume), tf.transpose(-1, -2), lf if batched else look_from, *posed)
 
     def _hints(self, tf, vol_in, sampling_rate, mode):
         """DR_HINT_* from the USER's TF tensor ([BS,] 4, R) -- the object that lives across iterations and whose version
@@ -350,8 +352,18 @@ class Raycaster(torch.nn.Module):
         return F.termination_hints(tf, vol_in.shape[-3:], sampling_rate, self.vr.max_samples, mode,
                                    alpha=lambda t: t[..., 3, :])
 
-    def raycast_nondiff(self, volume, tf, look_from, sampling_rate=None):
-        """VR.py:490-523: non-differentiable render (never jittered); default rate 4x the module's."""
+    def raycast_nondiff(self, volume, tf, look_from, sampling_rate=None, look_at=None, up=None, fov=None):
+        """VR.py:490-523: non-differentiable render (never jittered); default rate 4x the module's.
+        look_at, up ([BS,]3), fov ([BS,] degrees): the free camera, as in forward."""
+        if L.has_pose(look_at, up, fov):
+            batched, bs, vol_in, tf_in, lf_in, pose = self._determine_batch(volume, tf, look_from, (look_at, up, fov))
+            with L.nondiff_rays(vol_in, lf_in, sampling_rate, self.sampling_rate, self.vr.resolution, self.vr.fov_deg,
+                                self.vr.near, pose) as (sr, vol_in, cam, rays, pose9, fov_v):
+                out, steps = F.march_fwd(vol_in, tf_in.float().contiguous(), cam, *rays, self.vr.max_samples, sr,
+                                         N.DR_MODE_NONDIFF, fov_deg=self.vr.fov_deg, near=self.vr.near,
+                                         hints=self._hints(tf, vol_in, sr, N.DR_MODE_NONDIFF), pose=pose9, fov_v=fov_v)
+                self.vr._steps = L.unbatch(steps, batched)
+                return L.image(L.unbatch(out, batched))
         batched, bs, vol_in, tf_in, lf_in = self._determine_batch(volume, tf, look_from)
         with L.nondiff_rays(vol_in, lf_in, sampling_rate, self.sampling_rate, self.vr.resolution, self.vr.fov_deg,
                             self.vr.near) as (sr, vol_in, cam, rays):
@@ -361,8 +373,17 @@ class Raycaster(torch.nn.Module):
             self.vr._steps = L.unbatch(steps, batched)
             return L.image(L.unbatch(out, batched))
 
-    def forward(self, volume, tf, look_from):
-        """VR.py:525-548. volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3) -> ([BS,]4,H,W)."""
+    def forward(self, volume, tf, look_from, look_at=None, up=None, fov=None):
+        """VR.py:525-548. volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3) -> ([BS,]4,H,W).
+        look_at, up ([BS,]3), fov ([BS,] degrees, a 0-d tensor or a number): the free camera (pose.py), with
+        gradients for every one that requires grad; a missing one is the origin, +y, the module's fov. All None: the reference's
+        camera and this method as it always was."""
+        if L.has_pose(look_at, up, fov):
+            from .pose import PoseRaycastFunction
+            batched, bs, vol_in, tf_in, lf_in, pose = self._determine_batch(volume, tf, look_from, (look_at, up, fov))
+            res = PoseRaycastFunction.apply(self.vr, vol_in, tf_in, lf_in, *pose, self.sampling_rate, (batched, bs), self.jitter,
+                                            self._hints(tf, vol_in, self.sampling_rate, N.DR_MODE_DIFF))
+            return L.image(res)
         batched, bs, vol_in, tf_in, lf_in = self._determine_batch(volume, tf, look_from)
         res = RaycastFunction.apply(self.vr, vol_in, tf_in, lf_in, self.sampling_rate, (batched, bs), self.jitter,
                                     self._hints(tf, vol_in, self.sampling_rate, N.DR_MODE_DIFF))

@@ -223,6 +223,63 @@ int dr_march_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                      const int32_t *steps, const float *grad_out, const float *out_rgba,
                      double *d_cam, float *d_cam_ray, void *stream);
 
+/* The free camera: look_at, up and a per-view field of view beside look_from, and their gradients -- what the
+ * reference's camera fixes (it looks at the origin, up = +y, one scalar fov: VR.py:127-151).
+ *   view_dir = normalize(look_at - look_from), right = normalize(view_dir x up), up' = normalize(right x view_dir),
+ *   near_h = 2 tan(fov) near, near_w = near_h img_W / H, vd = normalize(near view_dir + u near_w right + v near_h up');
+ * slab clipping, sample count and jitter are dr_ray_setup_rows'. The light stays at look_from + (0,1,0) in world space: it does
+ * not follow `up`. `up` parallel to view_dir is degenerate (right = 0), as the fixed camera on the y axis is, and is not
+ * special-cased; a fov outside (0, pi/2) is not checked (the values live on the device: no synchronisation).
+ *   pose   [n_views][9] f32: look_from, look_at, up of every view. NULL: the fixed camera -- each entry below is then the
+ *          entry it is named after, which in turn is this one with pose = fov_v = NULL.
+ *   fov_v  [n_views] f32, radians, nullable (only with a pose): NULL takes fov_rad for every view, through the host's double
+ *          arithmetic, so that the default pose (look_at 0, up +y) gives dr_ray_setup_rows' buffers bit for bit; given, the
+ *          extents are formed per view on the device in double and rounded once.
+ * dr_ray_setup_pose_rows reads look_from from the pose (cam may be NULL then). The march entries read `cam` [n_views][3] as the
+ * ray origin as ever: it holds the pose's look_from rows. They hand the pose to the brick-centric kernels, whose pixel
+ * rectangles and line pre-test follow the camera's basis; without it the rays of a panned or rolled camera would fail the
+ * sample-count check and be marched one by one (correct, but off the fast path). A backward takes the pose of its forward. */
+int dr_ray_setup_pose_rows(const float *cam, int n_views, int W, int H, int img_W, int row0, int VX, int VY, int VZ,
+                           double fov_rad, double near_plane, float sampling_rate,
+                           uint32_t jitter_seed, uint32_t view_base,
+                           float *entry, float *exit_, float *rays, int32_t *nsamp,
+                           const float *pose, const float *fov_v, void *stream);
+int dr_march_fwd_rows_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                           int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                           const float *tf, int R, int64_t tf_view_stride,
+                           const float *cam, const float *entry, const float *exit_, const float *rays,
+                           const int32_t *nsamp, int n_views, int W, int H, int max_samples,
+                           float sampling_rate, double fov_rad, double near_plane, int mode, int variant,
+                           float *out_rgba, int32_t *steps, void *workspace, size_t workspace_bytes,
+                           int img_W, int row0, const float *pose, const float *fov_v, void *stream);
+int dr_march_bwd_rows_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                           int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                           const float *tf, int R, int64_t tf_view_stride,
+                           const float *cam, const float *entry, const float *exit_, const float *rays,
+                           const int32_t *nsamp, int n_views, int W, int H, int max_samples,
+                           float sampling_rate, double fov_rad, double near_plane, int variant,
+                           const float *grad_out, const float *out_rgba,
+                           float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                           float *d_tf, int64_t dtf_view_stride,
+                           void *workspace, size_t workspace_bytes, int img_W, int row0,
+                           const float *pose, const float *fov_v, void *stream);
+
+/* Gradient of the DR_MODE_DIFF march w.r.t. the pose: dr_march_bwd_cam for ten parameters, from the same per-ray sums and with
+ * the same frozen branches, H6, D1 and D5.
+ *   pose (not NULL), fov_v: those of the forward; the other arguments as for dr_march_bwd_cam
+ *   d_pose     [n_views][10] f64, ACCUMULATED into (caller zeroes): d look_from, d look_at, d up, d fov (per radian; with
+ *              fov_v NULL the gradient w.r.t. fov_rad); one atomic per component per workgroup
+ *   d_pose_ray [n_views][W][H][10] f32, nullable: each ray's contribution (overwritten) */
+int dr_march_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                      int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                      const float *tf, int R, int64_t tf_view_stride,
+                      const float *cam, const float *entry, const float *exit_, const float *rays,
+                      const int32_t *nsamp, int n_views, int W, int H, int max_samples,
+                      float sampling_rate, double fov_rad, double near_plane,
+                      uint32_t jitter_seed, uint32_t view_base, int img_W, int row0,
+                      const int32_t *steps, const float *grad_out, const float *out_rgba,
+                      const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream);
+
 /* The one exchange step of the path when views (or image bands) are sharded over the GPUs of a node: an in-place float32
  * SUM all-reduce of the shared gradients over RCCL / xGMI (the reference is single-device and has no
  * counterpart). For hosts without torch.distributed -- the Python package itself uses torch's "nccl" backend, which is the
@@ -432,6 +489,15 @@ int dr_project_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                        const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
                        double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
                        const float *grad_out, const int32_t *arg_max, double *d_cam, float *d_cam_ray, void *stream);
+
+/* dr_project_bwd_cam for the free camera's ten parameters (dr_march_bwd_pose's pose, fov_v, d_pose and d_pose_ray). */
+int dr_project_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                        int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                        const float *cam, const float *entry, const float *exit_, const float *rays,
+                        const int32_t *nsamp, int n_views, int W, int H, int max_samples, int mode,
+                        double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                        const float *grad_out, const int32_t *arg_max,
+                        const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream);
 
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
