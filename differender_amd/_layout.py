@@ -61,12 +61,17 @@ def has_pose(look_at, up, fov):
     return not (look_at is None and up is None and fov is None)
 
 
-def refuse_pose_grad(who, **tensors):
-    """Raycaster2D and RaycasterRGBA have no camera gradients: a camera tensor that requires grad is an error, not a silent None."""
+def wants_grad(*tensors):
+    """Whether autograd is on and one of the tensors (None and numbers allowed) requires grad."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+def refuse_pose_grad(who, hint="use volume_raycaster.Raycaster for camera gradients", **tensors):
+    """Raycaster2D, and RaycasterRGBA unless built with camera_grad=True, have no camera gradients: a camera tensor that requires
+    grad is an error, not a silent None. hint: what the caller can do instead, beside detaching the tensor."""
     for name, t in tensors.items():
-        if torch.is_grad_enabled() and torch.is_tensor(t) and t.requires_grad:
-            raise ValueError(f"{who} has no gradient w.r.t. {name}: use volume_raycaster.Raycaster for camera gradients, or "
-                             f"pass {name}.detach()")
+        if wants_grad(t):
+            raise ValueError(f"{who} has no gradient w.r.t. {name}: {hint}, or pass {name}.detach()")
 
 
 def reduce_to(d, shape, dtype):

@@ -79,6 +79,10 @@ SIGNATURES = {
                                _I, _I, _I, _I, _F, _I, _P, _P, _P]),
     "dr_march_rgba_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P,
                                _I, _I, _I, _I, _F, _P, _P, _P, _L, _L, _L, _L, _L, _P]),
+    "dr_march_rgba_bwd_cam": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P,
+                                   _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P]),
+    "dr_march_rgba_bwd_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P,
+                                    _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

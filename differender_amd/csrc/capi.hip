@@ -527,7 +527,7 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     return launch_on(vol, launch_march_tf2d_bwd, a, (hipStream_t)stream);
 }
 
-// what the two RGBA-volume entries check before any HIP call, and the MarchArgs they share
+// what the RGBA-volume entries check before any HIP call, and the MarchArgs they share
 static int fill_rgba(MarchArgs &a, RgbaArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
                      int64_t sz, int64_t sc, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,
                      const float *rays, const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate) {
@@ -571,6 +571,49 @@ int dr_march_rgba_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz; a.dvol_vs = dvol_view_stride;
     q.dsc = dsc;
     return launch_on(vol, launch_march_rgba_bwd, a, q, (hipStream_t)stream);
+}
+
+// dr_march_rgba_bwd_cam (pose null: d_cam [n_views][3]) and dr_march_rgba_bwd_pose (d_cam [n_views][10]): one implementation
+static int march_rgba_bwd_camera(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                                 int64_t sc, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,
+                                 const float *rays, const int32_t *nsamp, int n_views, int W, int H, int max_samples,
+                                 float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                                 const int32_t *steps, const float *grad_out, const float *out_rgba, const float *pose,
+                                 const float *fov_v, double *d_cam, float *d_cam_ray, void *stream) {
+    MarchArgs a;
+    RgbaArgs q;
+    const int rc = fill_rgba(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp,
+                             n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!steps || !grad_out || !out_rgba || !d_cam || !pose_fits(pose, fov_v)) return DR_EINVAL;
+    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
+    a.mode = DR_MODE_DIFF; a.pose = pose; a.fov_v = fov_v;
+    a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    CamArgs c;
+    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    return launch_on(vol, launch_march_rgba_bwd_cam, a, q, c, (hipStream_t)stream);
+}
+
+int dr_march_rgba_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                          int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                          const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate, double fov_rad,
+                          double near_plane, uint32_t jitter_seed, uint32_t view_base, const int32_t *steps,
+                          const float *grad_out, const float *out_rgba, double *d_cam, float *d_cam_ray, void *stream) {
+    return march_rgba_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp,
+                                 n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, jitter_seed, view_base, steps,
+                                 grad_out, out_rgba, nullptr, nullptr, d_cam, d_cam_ray, stream);
+}
+
+int dr_march_rgba_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                           int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_, const float *rays,
+                           const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate, double fov_rad,
+                           double near_plane, uint32_t jitter_seed, uint32_t view_base, const int32_t *steps,
+                           const float *grad_out, const float *out_rgba, const float *pose, const float *fov_v, double *d_pose,
+                           float *d_pose_ray, void *stream) {
+    if (!pose) return DR_EINVAL;
+    return march_rgba_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp,
+                                 n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, jitter_seed, view_base, steps,
+                                 grad_out, out_rgba, pose, fov_v, d_pose, d_pose_ray, stream);
 }
 
 // what the three projection entries check: fill_rays at the projections' fixed rate of 1 with max_samples >= 1, the mode, and

@@ -176,6 +176,8 @@ struct RgbaArgs {
 // weak, as launch_camera_grad: capi.o must load in a library linked without march_rgba.o
 __attribute__((weak)) int launch_march_rgba_fwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream);
 __attribute__((weak)) int launch_march_rgba_bwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream);
+// ... and its camera gradient: dr_march_rgba_bwd_cam / _bwd_pose, CamArgs as for launch_camera_grad
+__attribute__((weak)) int launch_march_rgba_bwd_cam(const MarchArgs &a, const RgbaArgs &q, const CamArgs &c, hipStream_t stream);
 
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,

@@ -6,6 +6,9 @@
 //   VEC: the channels of a voxel are neighbours in memory and every voxel is 16-B (f32) / 8-B (f16) aligned: a corner is ONE
 //   load instead of four. The host decides once per launch (rgba_vec_ok); both paths read the same values and do the same
 //   arithmetic in the same order, so their images are the same bits.
+// The camera gradient of the march is the third kernel here: D8's four per-ray sums (camera_grad.hip) with the
+// per-sample part of a four-channel volume, and dr_camera.h's once-per-ray tails and reductions.
+#include "dr_camera.h"
 #include "dr_tile.h"
 
 namespace dr {
@@ -54,6 +57,8 @@ __device__ __forceinline__ float4 ld_voxel4(const __half *p, int64_t sc) {
 __device__ __forceinline__ float4 mix4(float4 x, float4 y, float a) {
     return make_float4(mixf(x.x, y.x, a), mixf(x.y, y.y, a), mixf(x.z, y.z, a), mixf(x.w, y.w, a));
 }
+__device__ __forceinline__ float4 sub4(float4 x, float4 y) { return make_float4(x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w); }
+__device__ __forceinline__ float4 scale4(float4 x, float s) { return make_float4(x.x * s, x.y * s, x.z * s, x.w * s); }
 
 // tri_sample (dr_device.h) on four channels: one cell, eight corner fetches, the lerps x -> y -> z per channel
 template <typename VT, bool VEC>
@@ -188,6 +193,121 @@ __global__ __launch_bounds__(256) void march_rgba_bwd_kernel(RgbaParams<VT> P) {
     run.flush(dv, P.dsc, vol.VX, vol.VY, vol.VZ);
 }
 
+// tri_sample4's value (same corners, same mix4 order x -> y -> z, same bits) and, per channel, its slopes along the position's
+// three axes: dr_device.h's tri_sample_grad on four channels, with its formulas and its gates -- the cell is frozen, an axis
+// passes a gradient iff 0 < 0.5 p + 0.5 <= 1, and a high index clamped onto the low one gives equal corners and a zero slope.
+template <typename VT, bool VEC>
+__device__ __forceinline__ float4 tri_sample4_grad(const VolView<VT> &v, int64_t sc, const Cell &c, float px, float py, float pz,
+                                                   float4 &gx, float4 &gy, float4 &gz) {
+    const VT *b00 = v.p + c.x0 * v.sx + c.y0 * v.sy, *b10 = v.p + c.x1 * v.sx + c.y0 * v.sy;
+    const VT *b01 = v.p + c.x0 * v.sx + c.y1 * v.sy, *b11 = v.p + c.x1 * v.sx + c.y1 * v.sy;
+    const int64_t o0 = c.z0 * v.sz, o1 = c.z1 * v.sz;
+    const float4 v000 = ld_voxel4<VEC>(b00 + o0, sc), v100 = ld_voxel4<VEC>(b10 + o0, sc);
+    const float4 v010 = ld_voxel4<VEC>(b01 + o0, sc), v110 = ld_voxel4<VEC>(b11 + o0, sc);
+    const float4 v001 = ld_voxel4<VEC>(b00 + o1, sc), v101 = ld_voxel4<VEC>(b10 + o1, sc);
+    const float4 v011 = ld_voxel4<VEC>(b01 + o1, sc), v111 = ld_voxel4<VEC>(b11 + o1, sc);
+    const float4 a0 = mix4(v000, v100, c.fx), b0 = mix4(v010, v110, c.fx);
+    const float4 a1 = mix4(v001, v101, c.fx), b1 = mix4(v011, v111, c.fx);
+    const float4 zl = mix4(a0, b0, c.fy), zh = mix4(a1, b1, c.fy);
+    const float4 dfx = mix4(mix4(sub4(v100, v000), sub4(v110, v010), c.fy), mix4(sub4(v101, v001), sub4(v111, v011), c.fy), c.fz);
+    const float4 dfy = mix4(sub4(b0, a0), sub4(b1, a1), c.fz);
+    const float4 dfz = sub4(zh, zl);
+    const float yx = fmaf(0.5f, px, 0.5f), yy = fmaf(0.5f, py, 0.5f), yz = fmaf(0.5f, pz, 0.5f);
+    gx = (0.0f < yx && !(1.0f < yx)) ? scale4(dfx, 0.5f * v.scx) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gy = (0.0f < yy && !(1.0f < yy)) ? scale4(dfy, 0.5f * v.scy) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gz = (0.0f < yz && !(1.0f < yz)) ? scale4(dfz, 0.5f * v.scz) : make_float4(0.f, 0.f, 0.f, 0.f);
+    return mix4(zl, zh, c.fz);
+}
+
+// What the camera gradient reads beside the march's parameters (camera_grad.hip's CamParams; no row bands: the buffers are the
+// whole image)
+template <typename VT>
+struct RgbaCamParams : RgbaParams<VT> {
+    const int32_t *fwd_steps;   // the forward's live samples per ray
+    float near_, near_w, near_h;
+    uint32_t jitter_seed, view_base;
+    double *d_cam; float *d_cam_ray;
+    const float *pose, *fov_v;   // POSE: [views][9] look_from, look_at, up; [views] fov in radians, nullable
+    double near_d, aspect;       // ... the near plane and W / H as doubles, for a view's own extents
+};
+
+// Gradient of the differentiable RGBA march w.r.t. look_from ([views][3]) or, POSE, the free camera's ten parameters
+// (DESIGN.md D16). camera_grad_kernel's shape and frozen branches (n, the live samples, the jitter draw, the slab faces, the
+// cells); per sample P_s = dL/dpos_s = sum over the channels of the channel's adjoint times its slopes. There is no lighting,
+// so D8's H_s = D_s = 0 and G_s = P_s: four f32 sums per ray, the tail once per ray, f64 per workgroup.
+template <typename VT, bool VEC, bool POSE>
+__global__ __launch_bounds__(256) void march_rgba_cam_kernel(RgbaCamParams<VT> P) {
+    __shared__ double red[3][256];
+    const int view = blockIdx.y;
+    f3 dcam = make_f3(0.f, 0.f, 0.f);
+    PoseGrad dpose = pose_zero();
+    int i, j;
+    const bool in_img = tile_pixel(P.W, P.H, i, j);
+    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    // H6: a single-sample ray sits at 0/0 in the reference and contributes nothing
+    if (in_img && P.nsamp[p] > 1) {
+        VolView<VT> vol = P.vol;
+        vol.p += view * P.vol_vs;
+        const f3 lf = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
+        RayGeom rg;
+        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
+        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+        const int m = min(rgba_samples(rg.n, P.S, false), P.fwd_steps[p]);   // the forward's live samples (early termination frozen)
+
+        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
+        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+        f3 sP = make_f3(0.f, 0.f, 0.f), sTP = make_f3(0.f, 0.f, 0.f);
+        float s0 = 0.f, s1 = 0.f;
+        Composite c;
+        for (int s = 0; s < m; ++s) {
+            Sample sm;
+            sample_pos(rg, lf.x, lf.y, lf.z, s, sm.px, sm.py, sm.pz);
+            Cell cell;
+            tri_cell(vol, sm.px, sm.py, sm.pz, cell);
+            float4 gx, gy, gz;
+            const float4 v = tri_sample4_grad<VT, VEC>(vol, P.sc, cell, sm.px, sm.py, sm.pz, gx, gy, gz);
+            sm.r = v.x; sm.g = v.y; sm.b = v.z; sm.a = v.w;
+            sm.L = sm.Lraw = 1.0f; sm.flat = true;   // no shading, as march_rgba_bwd_kernel
+            sm.op = opacity_of_alpha(sm.a, P.inv_sr);
+            const float T = c.add(sm);
+            const bool last = s == m - 1;
+            SampleAdj ad;
+            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
+            const f3 Ps = make_f3(ad.r_bar * gx.x + ad.g_bar * gx.y + ad.b_bar * gx.z + ad.a_bar * gx.w,
+                                  ad.r_bar * gy.x + ad.g_bar * gy.y + ad.b_bar * gy.z + ad.a_bar * gy.w,
+                                  ad.r_bar * gz.x + ad.g_bar * gz.y + ad.b_bar * gz.z + ad.a_bar * gz.w);
+            const float f = (float)s / (float)(rg.n - 1);
+            const float t = mixf(rg.t0, rg.exit_, f);
+            const float gv = dot3(Ps, vd);
+            sP = f3_add(sP, Ps);
+            sTP = f3_fma(t, Ps, sTP);
+            s0 = fmaf(1.0f - f, gv, s0);
+            s1 = fmaf(f, gv, s1);
+        }
+
+        if (POSE) {
+            // once per ray: the ten pose gradients from the four sums (dr_camera.h), then D5
+            const PoseRay q = pose_ray(P.pose, P.fov_v, view, P.near_d, P.aspect, P.near_w, P.near_h, i, P.W, j, P.H, rg.n,
+                                       P.jitter_seed, P.view_base + (uint32_t)view);
+            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.near_, sP, sTP, s0 * q.A, fmaf(s0, 1.0f - q.A, s1)));
+        } else {
+            // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw behind grad t0
+            M3 J;
+            f3 g_tmin, g_tmax, g_t0;
+            float u;
+            camera_ray_tail(lf, vd, i, P.W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed, P.view_base + (uint32_t)view,
+                            J, g_tmin, g_tmax, g_t0, u);
+            dcam = f3_add(sP, mul_t(J, sTP));
+            dcam = f3_fma(s0, g_t0, dcam);
+            dcam = f3_fma(s1, g_tmax, dcam);
+            // D5: a NaN ray (NaN upstream gradient or pixel) contributes nothing, infinities are clamped
+            dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
+        }
+    }
+    if (POSE) pose_reduce(dpose, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    else camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+}
+
 // VEC: a voxel's channels are one aligned 16-B (f32) / 8-B (f16) load wherever the voxel lies
 static bool rgba_vec_ok(const MarchArgs &a, const RgbaArgs &q) {
     const size_t bytes = 4 * (a.vol_dtype == DR_F16 ? sizeof(__half) : sizeof(float));
@@ -216,6 +336,25 @@ int launch_march_rgba_fwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t str
 
 int launch_march_rgba_bwd(const MarchArgs &a, const RgbaArgs &q, hipStream_t stream) {
     return a.vol_dtype == DR_F16 ? rgba_bwd_dispatch<__half>(a, q, stream) : rgba_bwd_dispatch<float>(a, q, stream);
+}
+
+template <typename VT, bool POSE>
+static int rgba_cam_dispatch(const MarchArgs &a, const RgbaArgs &q, const CamArgs &c, hipStream_t stream) {
+    RgbaCamParams<VT> P{make_rgba_params<VT>(a, q)};
+    P.fwd_steps = c.steps;
+    near_plane_extents(a.fov_rad, a.near_plane, a.W, a.H, P.near_, P.near_w, P.near_h);
+    P.jitter_seed = c.jitter_seed; P.view_base = c.view_base;
+    P.d_cam = c.d_cam; P.d_cam_ray = c.d_cam_ray;
+    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)a.W / (double)a.H;
+    return launch_tiles(rgba_vec_ok(a, q) ? march_rgba_cam_kernel<VT, true, POSE> : march_rgba_cam_kernel<VT, false, POSE>, a, 0,
+                        stream, P);
+}
+
+// MarchArgs::pose null: d look_from into c.d_cam [n_views][3]; else the ten pose gradients into [n_views][10]
+int launch_march_rgba_bwd_cam(const MarchArgs &a, const RgbaArgs &q, const CamArgs &c, hipStream_t stream) {
+    if (a.pose)
+        return a.vol_dtype == DR_F16 ? rgba_cam_dispatch<__half, true>(a, q, c, stream) : rgba_cam_dispatch<float, true>(a, q, c, stream);
+    return a.vol_dtype == DR_F16 ? rgba_cam_dispatch<__half, false>(a, q, c, stream) : rgba_cam_dispatch<float, false>(a, q, c, stream);
 }
 
 }  // namespace dr

@@ -639,6 +639,37 @@ def march_rgba_bwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate,
     return d_vol
 
 
+def march_rgba_bwd_pose(vol4, pose, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
+                        near=0.1, jitter_seed=0, view_base=0, per_ray=False, fov_v=None):
+    """d pose of sum(march_rgba_fwd(...) * grad_out) (dr_march_rgba_bwd_pose): march_rgba_bwd_cam for the free
+    camera of ray_setup_pose, as march_bwd_pose is march_bwd_cam's. Returns d_pose (views, 10) float32 (the fov column per
+    radian) -- and, with per_ray=True, each ray's contribution (views, W, H, 10) as well."""
+    return march_rgba_bwd_cam(vol4, pose[:, :3], entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg,
+                              near, jitter_seed, view_base, per_ray, pose=pose, fov_v=fov_v)
+
+
+def march_rgba_bwd_cam(vol4, cam, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
+                       near=0.1, jitter_seed=0, view_base=0, per_ray=False, pose=None, fov_v=None):
+    """d look_from of sum(march_rgba_fwd(...) * grad_out) (dr_march_rgba_bwd_cam): cam (views, 3), the ray
+    buffers, jitter_seed and view_base those of the forward's ray_setup, `steps` and `out` those of march_rgba_fwd. Returns
+    d_cam (views, 3) float32 -- and, with per_ray=True, each ray's contribution (views, W, H, 3) as well."""
+    cam, V, W, H, rargs = _ray_args(vol4, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
+    steps = steps.to(torch.int32).contiguous()
+    vargs = _vol4_args(vol4, V)
+    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol4.device, per_ray, 3 if pose is None else 10)
+    if pose is None:
+        entry_point, pargs = N.lib().dr_march_rgba_bwd_cam, ()
+    else:   # (march_rgba_bwd_pose)
+        entry_point, pargs = N.lib().dr_march_rgba_bwd_pose, _pose_args(pose, fov_v, V)
+    with torch.cuda.device(vol4.device):
+        rc = entry_point(*vargs, *rargs, int(max_samples), float(sampling_rate), float(np.radians(fov_deg)), float(near),
+                         int(jitter_seed) & 0xFFFFFFFF, int(view_base), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(),
+                         *pargs[2:], d_cam.data_ptr(), _ptr(d_ray), _stream())
+    N.check(rc, "dr_march_rgba_bwd_cam" if pose is None else "dr_march_rgba_bwd_pose")
+    return _cam_grad_result(d_cam, d_ray)
+
+
 _PROJ_MODES = {"sum": N.DR_PROJ_SUM, "max": N.DR_PROJ_MAX}
 NO_SAMPLE_LIMIT = 2 ** 31 - 1   # a max_samples no ray reaches
 

@@ -448,6 +448,37 @@ int dr_march_rgba_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                       float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dsc, int64_t dvol_view_stride,
                       void *stream);
 
+/* Gradient of the differentiable dr_march_rgba_fwd w.r.t. the camera: dr_march_bwd_cam's chain (D8) for the
+ * four-channel volume, without lighting. It is the reverse-mode derivative of ray setup + march with the usual frozen branches:
+ * the sample count n, the live samples (`steps` of dr_march_rgba_fwd: m = min(n, max_samples, steps)), the jitter draw, the slab
+ * faces picked for entry and exit, every sample's trilinear cell and every clamp predicate. A ray with n <= 1 contributes
+ * nothing (H6). A ray whose upstream gradient or pixel is NaN (an alpha > 1 at a rate != 1 makes such a pixel) contributes
+ * nothing and infinities are clamped to +-1e30 (D5).
+ *   dr_march_rgba_bwd_cam   ACCUMULATES d look_from into d_cam [n_views][3] (f64, caller zeroes) and writes each ray's
+ *                           contribution to d_cam_ray [n_views][W][H][3] (f32, nullable, overwritten)
+ *   dr_march_rgba_bwd_pose  the same for the free camera: d_pose [n_views][10] = d look_from, d look_at, d up,
+ *                           d fov PER RADIAN; d_pose_ray [n_views][W][H][10]; pose [n_views][9] required, fov_v nullable
+ * fov_rad, near_plane, jitter_seed, view_base (and pose, fov_v) must be those of the dr_ray_setup[_pose_rows] call that made the
+ * buffers. Bands of image rows are not supported: the buffers are whole images. No per-sample or per-ray atomics, and nothing
+ * is written to the volume's gradient.
+ * Invalid arguments (null required pointers -- steps, d_cam and for _pose pose included --, fov_v without pose, n_views, W or
+ * H <= 0, a volume extent < 2, max_samples < 1, an unknown dtype, a non-finite or non-positive sampling rate) return DR_EINVAL
+ * before any HIP call. */
+int dr_march_rgba_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                          int64_t sx, int64_t sy, int64_t sz, int64_t sc, int64_t vol_view_stride,
+                          const float *cam, const float *entry, const float *exit_, const float *rays,
+                          const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                          double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                          const int32_t *steps, const float *grad_out, const float *out_rgba,
+                          double *d_cam, float *d_cam_ray, void *stream);
+int dr_march_rgba_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                           int64_t sx, int64_t sy, int64_t sz, int64_t sc, int64_t vol_view_stride,
+                           const float *cam, const float *entry, const float *exit_, const float *rays,
+                           const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                           double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                           const int32_t *steps, const float *grad_out, const float *out_rgba,
+                           const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream);
+
 /* X-ray line-integral and maximum-intensity projections: the two standard projections of a scalar volume beside
  * compositing, differentiable w.r.t. the volume and the camera position. The samples are exactly those of the march, from the
  * ray buffers of dr_ray_setup (jitter included): s < m = min(n, max_samples), pos_s = look_from + mix(t0, exit, s/(n-1)) vd,
