@@ -83,6 +83,11 @@ SIGNATURES = {
                                    _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P]),
     "dr_march_rgba_bwd_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P,
                                     _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the lit march: dr_march_fwd / _bwd in their plain form plus light, mode (and d_light, d_light_ray)
+    "dr_march_lit_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                              _I, _I, _I, _I, _F, _P, _I, _P, _P, _P]),
+    "dr_march_lit_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                              _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

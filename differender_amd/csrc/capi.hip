@@ -527,6 +527,42 @@ int dr_march_tf2d_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, in
     return launch_on(vol, launch_march_tf2d_bwd, a, (hipStream_t)stream);
 }
 
+int dr_march_lit_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                     int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                     const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W, int H,
+                     int max_samples, float sampling_rate, const float *light, int mode, float *out_rgba, int32_t *steps,
+                     void *stream) {
+    MarchArgs a;
+    int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
+                         rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!light || !out_rgba) return DR_EINVAL;
+    if (mode != DR_MODE_DIFF && mode != DR_MODE_NONDIFF) return DR_EINVAL;
+    a.mode = mode; a.out = out_rgba; a.steps = steps;
+    LitArgs q{};
+    q.light = light;
+    return launch_on(vol, launch_march_lit_fwd, a, q, (hipStream_t)stream);
+}
+
+int dr_march_lit_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                     int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                     const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W, int H,
+                     int max_samples, float sampling_rate, const float *light, int mode, const float *grad_out,
+                     const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                     float *d_tf, int64_t dtf_view_stride, double *d_light, float *d_light_ray, void *stream) {
+    MarchArgs a;
+    int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
+                         rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!light || mode != DR_MODE_DIFF) return DR_EINVAL;
+    rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf, dtf_view_stride);
+    if (rc) return rc;
+    if (!d_vol && !d_tf && !d_light && !d_light_ray) return 0;  // nothing requested
+    LitArgs q{};
+    q.light = light; q.d_light = d_light; q.d_light_ray = d_light_ray;
+    return launch_on(vol, launch_march_lit_bwd, a, q, (hipStream_t)stream);
+}
+
 // what the RGBA-volume entries check before any HIP call, and the MarchArgs they share
 static int fill_rgba(MarchArgs &a, RgbaArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
                      int64_t sz, int64_t sc, int64_t vol_view_stride, const float *cam, const float *entry, const float *exit_,

@@ -179,6 +179,17 @@ __attribute__((weak)) int launch_march_rgba_bwd(const MarchArgs &a, const RgbaAr
 // ... and its camera gradient: dr_march_rgba_bwd_cam / _bwd_pose, CamArgs as for launch_camera_grad
 __attribute__((weak)) int launch_march_rgba_bwd_cam(const MarchArgs &a, const RgbaArgs &q, const CamArgs &c, hipStream_t stream);
 
+// March with a free light and Phong material (march_lit.hip): what dr_march_lit_fwd / _bwd take beside their
+// MarchArgs (the 1-D march's, without workspace, variant or bands)
+struct LitArgs {
+    const float *light;      // [n_views][10]: position, colour, ambient, diffuse, specular, shininess
+    double *d_light;         // backward: [n_views][10], accumulated, nullable
+    float *d_light_ray;      // backward: [n_views][W][H][10] per-ray contributions, overwritten, nullable
+};
+// weak, as launch_camera_grad: capi.o must load in a library linked without march_lit.o
+__attribute__((weak)) int launch_march_lit_fwd(const MarchArgs &a, const LitArgs &q, hipStream_t stream);
+__attribute__((weak)) int launch_march_lit_bwd(const MarchArgs &a, const LitArgs &q, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -14,7 +14,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd", "march_bwd_cam", "march_bwd_pose", "project_bwd_pose", "march_tf2d_fwd", "march_tf2d_bwd", "march_rgba_fwd", "march_rgba_bwd", "project_fwd", "project_bwd",
+__all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd", "march_bwd_cam", "march_bwd_pose", "project_bwd_pose", "march_tf2d_fwd", "march_tf2d_bwd", "march_lit_fwd", "march_lit_bwd", "default_light", "march_rgba_fwd", "march_rgba_bwd", "project_fwd", "project_bwd",
            "project_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
@@ -594,6 +594,73 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
                                        out.data_ptr(), *dv, *dt, _stream())
     N.check(rc, "dr_march_tf2d_bwd")
     return d_vol, d_tf
+
+
+def default_light(cam):
+    """The reference's lighting (VR.py:91-95, 281-299) as the (views, 10) rows march_lit_fwd reads, for the cameras cam
+    (views, 3): a white light at look_from + (0, 1, 0) formed in float32, ambient 0.4, diffuse 0.8, specular 0.3, shininess 32."""
+    cam = cam.to(torch.float32).reshape(-1, 3)
+    light = cam.new_empty((cam.shape[0], 10))
+    light[:, :3] = cam + cam.new_tensor([0.0, 1.0, 0.0])
+    light[:, 3:] = cam.new_tensor([1.0, 1.0, 1.0, 0.4, 0.8, 0.3, 32.0])
+    return light
+
+
+def _light_arg(light, n_views, device):
+    """light (views, 10) as the float32 contiguous device tensor the kernels read (kept by the caller until its call is issued)."""
+    if not torch.is_tensor(light) or light.ndim != 2 or tuple(light.shape) != (n_views, 10):
+        raise ValueError(f"light must be a (views, 10) tensor with views = {n_views}: position, colour, ambient, diffuse, "
+                         "specular, shininess")
+    _require_gpu(light, "light")
+    return light.to(device=device, dtype=torch.float32).contiguous()
+
+
+def march_lit_fwd(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampling_rate, mode=N.DR_MODE_DIFF, want_steps=True):
+    """The 1-D TF march with a free light and Phong material (dr_march_lit_fwd): the plain kernels' march_fwd with
+    light (views, 10) float32 = the light's WORLD position (3), its colour (3), ambient, diffuse, specular, shininess per view.
+    Returns out (views,W,H,4) and steps (views,W,H) int32 (or None). default_light(cam) gives the bits of
+    march_fwd(variant=DR_VARIANT_BASELINE)."""
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    out, steps = _fwd_buffers(V, W, H, vol.device, want_steps)
+    vargs = _vol_args(vol, V)
+    targs = _tf_args(tf, V)
+    light = _light_arg(light, V, vol.device)
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_march_lit_fwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), light.data_ptr(), int(mode),
+                                      out.data_ptr(), _ptr(steps), _stream())
+    N.check(rc, "dr_march_lit_fwd")
+    return out, steps
+
+
+def march_lit_bwd(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampling_rate, grad_out, out, want_vol=True,
+                  want_tf=True, want_light=True, per_ray=False):
+    """Adjoint of the differentiable march_lit_fwd w.r.t. vol, tf and light (dr_march_lit_bwd). Returns (d_vol, d_tf, d_light),
+    each None when not wanted -- d_light (views, 10) float32 in light's order -- and, with per_ray=True, a fourth result: each
+    ray's contribution to d_light, (views, W, H, 10) float32. A shared (un-batched) vol / tf receives one gradient accumulated
+    over all views. NaN propagates into d_vol and d_tf (the plain kernels' convention: the caller applies nan_to_num, as
+    lighting.RaycasterLit does); a NaN ray contributes nothing to d_light (D5)."""
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
+    vargs = _vol_args(vol, V)
+    targs = _tf_args(tf, V)
+    light = _light_arg(light, V, vol.device)
+    d_vol, dv = _d_vol(vol, want_vol)
+    d_tf = None
+    dt = (None, 0)
+    if want_tf:
+        d_tf = torch.zeros_like(tf)
+        dt = (d_tf.data_ptr(), d_tf.stride(0) if tf.ndim == 3 else 0)
+    d_light = torch.zeros((V, 10), dtype=torch.float64, device=vol.device) if want_light else None
+    d_ray = torch.empty((V, W, H, 10), dtype=torch.float32, device=vol.device) if per_ray else None
+    if want_vol or want_tf or want_light or per_ray:
+        with torch.cuda.device(vol.device):
+            rc = N.lib().dr_march_lit_bwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), light.data_ptr(),
+                                          N.DR_MODE_DIFF, grad_out.data_ptr(), out.data_ptr(), *dv, *dt, _ptr(d_light),
+                                          _ptr(d_ray), _stream())
+        N.check(rc, "dr_march_lit_bwd")
+    if d_light is not None:
+        d_light = torch.nan_to_num(d_light.float())   # D5: a sum beyond the float range saturates
+    return (d_vol, d_tf, d_light, d_ray) if per_ray else (d_vol, d_tf, d_light)
 
 
 def _vol4_args(vol4, n_views):

@@ -479,6 +479,47 @@ int dr_march_rgba_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int V
                            const int32_t *steps, const float *grad_out, const float *out_rgba,
                            const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream);
 
+/* The 1-D TF march with a free light and Phong material. The reference shades every sample with a white light
+ * at look_from + (0, 1, 0), ambient 0.4, diffuse 0.8, specular 0.3 and shininess 32 (VR.py:91-95, 281-299); here these are ten
+ * parameters per view, and the backward returns their gradients. Everything else is dr_march_fwd's program as its plain kernels
+ * run it (VR.py:261-306, 363-372; DR_MODE_NONDIFF: VR.py:308-361): positions, jitter, sample count, max_samples clip, TF
+ * lookup, opacity correction, the six normal taps, flat normals (D1), termination at A >= 0.99, the non-differentiable mode's
+ * alpha > 1e-3 skip and final clamp. One lane per ray (the shape of DR_VARIANT_BASELINE): no workspace, no brick path, no
+ * camera gradient, no bands of rows.
+ *   light    [n_views][10] f32 on the device: p (3) the light's WORLD position, lc (3) its colour, ka, kd, ks the ambient,
+ *            diffuse and specular weights, sh the shininess
+ * Per shaded sample, in f32 with dr_march_fwd's rounding (VR.py:287-299):
+ *   ld = normalized(pos - p), m = n.ld, ndl = max(m, 0), rf = ld - 2 m n, q = -rf.vd, rdv = max(q, 0)  (flat normal: ndl = rdv = 0)
+ *   P = rdv^sh: five squarings when sh == 32, else the specified power of the opacity correction (D6; 0^sh = 0)
+ *   Lraw = fma(kd, ndl, ks P) + ka, L = min(1, Lraw) in DR_MODE_DIFF and Lraw in DR_MODE_NONDIFF
+ *   C_k = fma(T, (L c_k op) lc_k, C_k), A = fma(T, op, A)
+ * With p = look_from + (0, 1, 0) formed in f32, lc = 1 and 0.4, 0.8, 0.3, 32 the image and `steps` are the bits of dr_march_fwd
+ * under DR_VARIANT_BASELINE. A light that coincides with a sample gives NaN, which propagates as in the plain kernels.
+ * The backward (DR_MODE_DIFF) is the reverse-mode derivative of this program with dr_march_bwd's frozen branches (the sample
+ * count, the termination test re-evaluated as the forward did, every max / min predicate by Taichi's rules), hand-derived and
+ * tape-free. d_vol (element strides, dvol_view_stride 0 = one gradient for a shared volume) and d_tf (dtf_view_stride likewise)
+ * are f32 and ACCUMULATED (caller zeroes). d_light [n_views][10] is f64 and ACCUMULATED (caller zeroes): ten f32 sums per ray,
+ * a NaN sum dropped and infinities clamped to +-1e30 once per ray (D5), f64 per workgroup, one atomic per component and
+ * workgroup. d_light_ray [n_views][W][H][10] f32 is OVERWRITTEN with each ray's contribution. Each of the four is nullable and
+ * work for an absent one is not done; with all four NULL the call returns 0 before any HIP call.
+ * Invalid arguments (null required pointers -- light included --, n_views, W or H <= 0, a volume extent < 2, R < 1,
+ * max_samples < 0, a non-positive sampling rate, an unknown mode or dtype; a mode other than DR_MODE_DIFF in the backward)
+ * return DR_EINVAL before any HIP call. */
+int dr_march_lit_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                     int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                     const float *tf, int R, int64_t tf_view_stride,
+                     const float *cam, const float *entry, const float *exit_, const float *rays,
+                     const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                     const float *light, int mode, float *out_rgba, int32_t *steps, void *stream);
+int dr_march_lit_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                     int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                     const float *tf, int R, int64_t tf_view_stride,
+                     const float *cam, const float *entry, const float *exit_, const float *rays,
+                     const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                     const float *light, int mode, const float *grad_out, const float *out_rgba,
+                     float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                     float *d_tf, int64_t dtf_view_stride, double *d_light, float *d_light_ray, void *stream);
+
 /* X-ray line-integral and maximum-intensity projections: the two standard projections of a scalar volume beside
  * compositing, differentiable w.r.t. the volume and the camera position. The samples are exactly those of the march, from the
  * ray buffers of dr_ray_setup (jitter included): s < m = min(n, max_samples), pos_s = look_from + mix(t0, exit, s/(n-1)) vd,
