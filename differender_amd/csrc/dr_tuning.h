@@ -28,6 +28,14 @@
 #ifndef DR_BWD_UNEVEN
 #define DR_BWD_UNEVEN 7   // candidates dealt to a later wave for every 8 of an earlier one (0: even); 7: -1.1 %, 6: -0.5 %, 5: +2 %
 #endif
+// B1's d_volume scatter from the row-transposed lane layout (dr_wave.h: row_transpose): the pass runs in lane order up to the
+// adjoint, then lane 16 r + c scatters the sample of lane 4 c + r, so that the ~3.5 samples of a cell sit in different 16-lane
+// rows, where duplicate addresses cost the LDS nothing. 0: scatter in lane order. Headline step 9.212 -> 8.687 ms (-5.7 %),
+// backward 6.905 -> 6.403 ms (-7.3 %), four alternating runs per build; camera inside -7.7 %, d_volume only -4.2 %, f16 + jitter
+// -5.3 %, 8 views at 256^3 -3.1 %, tf1 -1.9 %, CT-like -0.75 % (profiles/rowscatter_ab.txt, gate: profiles/rowscatter_microbench.txt)
+#ifndef DR_BWD_ROW_SCATTER
+#define DR_BWD_ROW_SCATTER 1
+#endif
 // brick-centric backward w.r.t. the TF only (no gradient box, 33 KB of LDS): FOUR-wave workgroups, four per CU -- 3.22 ms against
 // 3.80 with the 8-wave shape at 512^3 (profiles/r03_ab_experiments.txt); 96 VGPRs for a fifth workgroup spill 132 B per lane: 4.08 ms
 #ifndef DR_FNT_BWDTF

@@ -1,5 +1,6 @@
 // dr_wave.h -- cross-lane building blocks of the brick kernels (gfx950 wave64): DPP moves, segmented wave scans of the
-// front-to-back "over" operator, of sums and of products, whole-wave shifts. No LDS traffic anywhere in this file.
+// front-to-back "over" operator, of sums and of products, whole-wave shifts: DPP only, no LDS traffic -- and, at the end, the
+// row transposition of the wave through the LDS crossbar (ds_bpermute_b32; no bank access either).
 // Shared by march_flat.hip (per-brick passes) and tf_tape.hip (the TF-only backward over the per-sample tape).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -169,6 +170,19 @@ __device__ __forceinline__ Over shfl_up1_over(const Over &v) {
     Over r;
     r.c0 = wave_up1(v.c0, 0.f); r.c1 = wave_up1(v.c1, 0.f); r.c2 = wave_up1(v.c2, 0.f); r.a = wave_up1(v.a, 0.f);
     return r;
+}
+
+// ---- row transposition of the wave (the one place of this file that goes through the LDS crossbar) ---------------------
+// Seen as a 4 x 16 matrix of lanes (rows = the 16-lane groups the LDS serves together), lane 16 r + c receives what lane
+// 4 c + r holds: four NEIGHBOURING lanes end up in four different rows. ds_bpermute_b32 moves the value through the LDS
+// crossbar: no bank is touched and no VALU issue slot taken (5.5 cycles of the LDS pipe per wave-instruction,
+// profiles/rowscatter_microbench.txt). All 64 lanes must be enabled: a disabled source lane delivers nothing useful.
+__device__ __forceinline__ int row_transpose_src(int lane) { return ((lane & 15) << 2) | (lane >> 4); }
+// the byte address ds_bpermute_b32 takes for that source lane (a per-lane constant)
+__device__ __forceinline__ int row_transpose_addr(int lane) { return 4 * row_transpose_src(lane); }
+__device__ __forceinline__ int row_transpose(int v, int addr) { return __builtin_amdgcn_ds_bpermute(addr, v); }
+__device__ __forceinline__ float row_transpose(float v, int addr) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
 }
 
 }  // namespace dr

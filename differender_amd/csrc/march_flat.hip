@@ -514,8 +514,10 @@ __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, con
         if (valid && (hi || lo)) scatter4<ACC>(dst + (hi ? 2 * SZ : -SZ), SX, SY, hi ? cz[3] : cz[0], XY, fs);
         if (__any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SZ, SX, SY, cz[0], XY, fs); }
     }
-    // (Consecutive lanes are consecutive samples of a ray, ~3.5 per cell: these eight adds collide in the LDS, ~7 cycles
-    // per duplicate address. Summing the runs across lanes first was tried twice: +1.0 ms of VALU for 0.4 ms of LDS.)
+    // (In lane order consecutive lanes are consecutive samples of a ray, ~3.5 per cell: these eight adds would collide in the
+    // LDS, ~7 cycles per duplicate address INSIDE a 16-lane row, none across rows. Summing the runs across lanes first was tried
+    // twice: +1.0 ms of VALU for 0.4 ms of LDS. The box scatter therefore arrives here row-transposed -- scatter_sample_rows
+    // below: a cell's samples sit in different rows; backward -7.3 %, profiles/rowscatter_ab.txt.)
     if (valid) scatter8<ACC>(dst, SX, SY, SZ, acc, fs);
 }
 // the common destination: the brick's LDS gradient box, centre cell at element cbase_i
@@ -523,6 +525,47 @@ template <int ACC>
 __device__ __forceinline__ void scatter_sample(unsigned long long *dbox, const TapCoords &t, bool valid, int cbase_i,
                                                float I_bar, const float (&gq)[3], const FixScale &fs) {
     scatter_sample<ACC>(dbox + cbase_i, (int)BOX_SX, (int)BOX_SY, 1, t, valid, I_bar, gq, fs);
+}
+// ... from the ROW-TRANSPOSED lane layout (DR_BWD_ROW_SCATTER, dr_tuning.h). The pass computes in lane order -- the tap reads keep
+// their broadcasts, the scans their neighbours -- and only here, in front of the scatter, lane 16 r + c takes over the sample of
+// lane 4 c + r: what scatter_sample consumes travels through the LDS crossbar in 14 ds_bpermute_b32 -- one word with the centre
+// cell, the six "tap stays in the centre's cell" flags and the validity, the nine fractions, the four adjoints. Integer adds
+// commute (ACC_FIX: the box ends bit-identical; the pass's scale is wave-uniform) and ACC_F64 only changes the order of its
+// double adds. Must be called with all 64 lanes enabled (a lane without a sample, or past the end of the wave's samples,
+// passes valid = false and arrives as such).
+template <int ACC>
+__device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, const TapCoords &t, bool valid, int cbase_i, int lane,
+                                                    float I_bar, const float (&gq)[3], const FixScale &fs) {
+#if DR_BWD_ROW_SCATTER
+    static_assert(BOX_LDS <= (1 << 12), "the centre cell's box element takes the low 12 bits of the packed word");
+    // (the cell is formed again here, not taken from cbase_i: its select would only be undone, and the main kernels need one
+    // register less this way; the validity rides in the word's sign bit: a select here and a compare there, against a 64-bit shift of the ballot
+    // by the source lane)
+    const int w_own = (t.lx * BOX_SX + t.ly * BOX_SY + t.lz) | ((int)(t.lxp != t.lx) << 12) | ((int)(t.lxm != t.lx) << 13) |
+                      ((int)(t.lyp != t.ly) << 14) | ((int)(t.lym != t.ly) << 15) | ((int)(t.lzp != t.lz) << 16) |
+                      ((int)(t.lzm != t.lz) << 17) | (int)0x80000000u;
+    // (the source lane's address is made here, per pass: hoisted out of the sample loops it would be one more register to
+    // keep alive across shading and the adjoint, where the kernel has none to spare)
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    const int a = row_transpose_addr(l);
+    const float I2 = row_transpose(I_bar, a);
+    const float g2[3] = {row_transpose(gq[0], a), row_transpose(gq[1], a), row_transpose(gq[2], a)};
+    const int w = row_transpose(valid ? w_own : 0, a);
+    TapCoords u;
+    u.fx = row_transpose(t.fx, a); u.fy = row_transpose(t.fy, a); u.fz = row_transpose(t.fz, a);
+    u.fxp = row_transpose(t.fxp, a); u.fxm = row_transpose(t.fxm, a);
+    u.fyp = row_transpose(t.fyp, a); u.fym = row_transpose(t.fym, a);
+    u.fzp = row_transpose(t.fzp, a); u.fzm = row_transpose(t.fzm, a);
+    // tap_line only asks whether a tap's cell IS the centre's: cells relative to the centre's
+    u.lx = u.ly = u.lz = 0;
+    u.lxp = (w >> 12) & 1; u.lxm = -((w >> 13) & 1);
+    u.lyp = (w >> 14) & 1; u.lym = -((w >> 15) & 1);
+    u.lzp = (w >> 16) & 1; u.lzm = -((w >> 17) & 1);
+    scatter_sample<ACC>(dbox, u, w < 0, w & 0xfff, I2, g2, fs);
+#else
+    scatter_sample<ACC>(dbox, t, valid, cbase_i, I_bar, gq, fs);
+#endif
 }
 
 // Backward: the largest and the smallest non-zero |grad_out| (per pixel: its largest component) over the brick's
@@ -1231,7 +1274,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                             I_bar = acc_sanitise(I_bar);
                             gq[0] = acc_sanitise(gq[0]); gq[1] = acc_sanitise(gq[1]); gq[2] = acc_sanitise(gq[2]);
                         }
-                        scatter_sample<ACC_F64>(L.dbox, t, valid, cbase_i, I_bar, gq, fs);
+                        scatter_sample_rows<ACC_F64>(L.dbox, t, valid, cbase_i, lane, I_bar, gq, fs);
                     } else {
                         // Beyond the range of the fixed-point box (2^12 x the brick's largest upstream gradient: the
                         // normalisation of a nearly vanishing volume gradient amplifies by 1/|grad|, 1e7 and more where
@@ -1261,7 +1304,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                             FixScale fw = fs;
                             const float mul = fix_wave_scale(wmax, fw);
                             const float gs[3] = {gq[0] * mul, gq[1] * mul, gq[2] * mul};
-                            scatter_sample<ACC_FIX>(L.dbox, t, in_box, cbase_i, I_bar * mul, gs, fw);
+                            scatter_sample_rows<ACC_FIX>(L.dbox, t, in_box, cbase_i, lane, I_bar * mul, gs, fw);
                         }
                     }
                 }
