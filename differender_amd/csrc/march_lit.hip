@@ -130,7 +130,9 @@ __global__ __launch_bounds__(256) void march_lit_bwd_kernel(LitParams<VT> P) {
                 }
             }
         }
-        if (LIGHT) lg = light_finite(lg);   // D5, once per ray
+        // D5, once per ray. A NaN channel of the upstream gradient drops the whole ray, not only the sums it reaches: d lc_k
+        // reads go_k alone and no lighting sum reads go.a, and a ray that gave some of its ten columns would be no gradient
+        if (LIGHT) lg = (go.x == go.x && go.y == go.y && go.z == go.z && go.w == go.w) ? light_finite(lg) : light_zero();
     }
     if (P.d_tf && TABLES == 2) {
         __syncthreads();

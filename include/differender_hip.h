@@ -499,8 +499,8 @@ int dr_march_rgba_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int V
  * count, the termination test re-evaluated as the forward did, every max / min predicate by Taichi's rules), hand-derived and
  * tape-free. d_vol (element strides, dvol_view_stride 0 = one gradient for a shared volume) and d_tf (dtf_view_stride likewise)
  * are f32 and ACCUMULATED (caller zeroes). d_light [n_views][10] is f64 and ACCUMULATED (caller zeroes): ten f32 sums per ray,
- * a NaN sum dropped and infinities clamped to +-1e30 once per ray (D5), f64 per workgroup, one atomic per component and
- * workgroup. d_light_ray [n_views][W][H][10] f32 is OVERWRITTEN with each ray's contribution. Each of the four is nullable and
+ * a NaN sum dropped and infinities clamped to +-1e30 once per ray, and all ten sums of a ray dropped whose upstream gradient
+ * holds a NaN in any channel (D5), f64 per workgroup, one atomic per component and workgroup. d_light_ray [n_views][W][H][10] f32 is OVERWRITTEN with each ray's contribution. Each of the four is nullable and
  * work for an absent one is not done; with all four NULL the call returns 0 before any HIP call.
  * Invalid arguments (null required pointers -- light included --, n_views, W or H <= 0, a volume extent < 2, R < 1,
  * max_samples < 0, a non-positive sampling rate, an unknown mode or dtype; a mode other than DR_MODE_DIFF in the backward)

@@ -16,11 +16,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import light_cases as LC  # noqa: E402
 import light_reference as LR  # noqa: E402
+from light_gpu import C, DEV, bound as _bound, compare as _compare, raw_bwd as _raw_bwd, upload as _upload  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda")
-C = lambda t: t.detach().double().cpu().numpy()
 
 
 def _F():
@@ -31,13 +29,6 @@ def _F():
 def _N():
     from differender_amd import _native as N
     return N
-
-
-def _upload(sc):
-    """A light_cases scene on the device -> (vol, tf, cam, light)."""
-    f = lambda a: torch.from_numpy(np.ascontiguousarray(a)).float().to(DEV)
-    vol = f(sc["vol"])
-    return (vol.half() if sc["f16"] else vol), f(sc["tf"]), f(sc["cam"]), f(sc["light"])
 
 
 def _cams(views, first=0.9):
@@ -75,63 +66,6 @@ def test_reference_lighting_is_the_baseline_bit_for_bit(hiplib, mode, vdt, sr):
 
 
 # --- 2. other lights and materials against the float64 transliteration (and 5: every LDS tier) -----------------------------------
-
-def _bound(got, want, want32, what, per_column=False, err32=None):
-    """D8's bar: error <= 3 x the f32 transliteration's own error + 1e-5 of the largest reference element. per_column: the
-    bar must ALSO hold for each of the last axis's columns by itself -- the ten lighting gradients differ by three orders of
-    magnitude, and the small ones would otherwise hide under the floor of the large ones. err32: the f32 transliteration's own
-    error where it is not max |want32 - want| (the columns' errors, for per_column)."""
-    if per_column:
-        for k in range(want.shape[-1]):
-            _bound(got[..., k], want[..., k], want32[..., k], f"{what}[{k}]", err32=None if err32 is None else err32[k])
-    err, scale = np.abs(got - want).max(), np.abs(want).max()
-    err32 = np.abs(want32 - want).max() if err32 is None else np.max(err32)
-    print(f"{what}: err {err:.3e} err32 {err32:.3e} scale {scale:.3e}")
-    assert scale > 0, what
-    assert np.isfinite(got).all(), what
-    assert err <= 3.0 * err32 + 1e-5 * scale, (what, err / scale, err32 / scale)
-
-
-def _compare(name):
-    F = _F()
-    sc = LC.scene(name)
-    vol, tf, cam, light = _upload(sc)
-    S, sr = sc["max_samples"], sc["sr"]
-    e, x, r, n = F.ray_setup(cam, sc["WH"], vol.shape, sr, jitter_seed=sc["jitter"])
-    out, steps = F.march_lit_fwd(vol, tf, cam, light, e, x, r, n, S, sr)
-    st = LC.reference_state(sc, C(e), C(x), C(r), n.cpu().numpy(), steps.cpu().numpy())
-    gm = torch.from_numpy(st["gm"]).float().to(DEV)
-    d_vol, d_tf, d_light, d_ray = F.march_lit_bwd(vol, tf, cam, light, e, x, r, n, S, sr, gm, out, per_ray=True)
-    ref, ref32, mask = st["ref"], st["ref32"], st["mask"]
-    m4 = mask[..., None]
-    _bound(C(out) * m4, ref["rgba"] * m4, ref32["rgba"] * m4, "rgba")
-    _bound(C(d_vol), ref["dvol"], ref32["dvol"], "dvol")
-    _bound(C(d_tf), ref["dtf"], ref32["dtf"], "dtf")
-    _bound(C(d_ray) * m4, ref["dlight_ray"] * m4, ref32["dlight_ray"] * m4, "dlight_ray")
-    # ... and column by column, over the rays together: the ten gradients differ by three orders of magnitude, and the small
-    # ones would hide under the floor of the large ones. A column's LARGEST per-ray error is one ray's rounding noise in the
-    # cancellation-prone terms (the normal, the light direction's projection), which two f32 programs of different operation
-    # order do not share; the rays' absolute errors SUMMED are a statistic both programs do share.
-    sum_abs = lambda a: (np.abs(a) * m4).sum((0, 1, 2))
-    col, col32, colref = sum_abs(C(d_ray) - ref["dlight_ray"]), sum_abs(ref32["dlight_ray"] - ref["dlight_ray"]), sum_abs(ref["dlight_ray"])
-    for k in range(10):
-        print(f"dlight_ray summed abs error [{k}]: err {col[k]:.3e} err32 {col32[k]:.3e} scale {colref[k]:.3e}")
-        assert colref[k] > 0 and col[k] <= 3.0 * col32[k] + 1e-5 * colref[k], (k, col[k] / colref[k], col32[k] / colref[k])
-    # the sums, from the kept rays only: the kernels' own (the others have a zero upstream gradient and add exact zeros), and
-    # the per-ray output re-summed
-    want = (ref["dlight_ray"] * m4).sum((1, 2))
-    want32 = (ref32["dlight_ray"] * m4).sum((1, 2))
-    _bound(C(d_light), want, want32, "dlight")
-    _bound((C(d_ray) * m4).sum((1, 2)), want, want32, "dlight resummed")
-    # ... and column by column. A column's sum is ONE number per view, and the f32 transliteration's error in it can cancel to
-    # nothing by chance (1e-7 of the sum, where single rays are off by 1e-5 of it in both f32 programs): its own error is taken
-    # before that cancellation, as the rays' absolute errors summed.
-    l1 = (np.abs(ref32["dlight_ray"] - ref["dlight_ray"]) * m4).sum((1, 2)).max(0)
-    _bound(C(d_light), want, want32, "dlight by column", per_column=True, err32=l1)
-    _bound((C(d_ray) * m4).sum((1, 2)), want, want32, "dlight resummed by column", per_column=True, err32=l1)
-    assert (C(d_ray)[~mask] == 0).all()
-    return sc, st, dict(n=n.cpu().numpy(), steps=steps.cpu().numpy(), d_light=C(d_light))
-
 
 @pytest.mark.parametrize("name", sorted(LC.CASES))
 def test_against_the_f64_transliteration(hiplib, name):
@@ -203,18 +137,6 @@ def test_flat_volume_has_the_closed_form(hiplib, ka):
 
 
 # --- 4. nullable outputs and accumulation ---------------------------------------------------------------------------------------
-
-def _raw_bwd(vol, tf, cam, light, rays, S, sr, go, out, d_vol=None, d_tf=None, d_light=None, d_ray=None):
-    """dr_march_lit_bwd on the caller's own output buffers (functional.march_lit_bwd allocates zeroed ones)."""
-    F, N = _F(), _N()
-    cam, V, W, H, rargs = F._ray_args(vol, cam, *rays)
-    dv = (None, 0, 0, 0, 0) if d_vol is None else (d_vol.data_ptr(), *d_vol.stride(), 0)
-    rc = N.lib().dr_march_lit_bwd(*F._vol_args(vol, V), *F._tf_args(tf, V), *rargs, S, sr, light.data_ptr(), N.DR_MODE_DIFF,
-                                  go.data_ptr(), out.data_ptr(), *dv, F._ptr(d_tf), 0, F._ptr(d_light), F._ptr(d_ray),
-                                  torch.cuda.current_stream().cuda_stream)
-    assert rc == 0
-    torch.cuda.synchronize()
-
 
 def test_nullable_outputs_and_accumulation(hiplib):
     """Each output alone is what the call with all four gives: d_vol and d_tf up to the order of their float atomics (k < 1e3

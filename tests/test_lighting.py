@@ -1,6 +1,8 @@
 """The differentiable light and Phong material, DESIGN.md D17, without a GPU: the float64 transliteration
 (tests/light_reference.py) against the reference program at the reference's lighting and against central differences, the
-masking rule on every scene of the GPU tests, RaycasterLit's argument checks, and the C ABI's."""
+masking rule on every scene of the GPU tests (and what each edge scene is for), the non-differentiable transliteration against
+make_setup_nondiff_golden.raycast_nondiff, per-view inputs of the transliteration, RaycasterLit's argument checks, and the C
+ABI's."""
 import ctypes
 import os
 import re
@@ -102,17 +104,149 @@ def test_both_transliterations_keep_enough_rays(oracle, name):
     """tests/test_gpu_lighting.py compares on the rays light_cases.kept_rays keeps (at least 80 % of the live ones, asserted
     there): here on the oracle's float64 ray buffers, there on the kernels' float32 ones. Also what each scene is for."""
     sc = LC.scene(name)
-    W, H = sc["WH"]
-    bufs = [oracle.ray_setup(c, W, H, sc["vol"].shape, sr=sc["sr"], jitter_seed=sc["jitter"], view=v, dtype=np.float64)
-            for v, c in enumerate(sc["cam"])]
-    inp = LC.inputs(sc, *(np.stack([b[k] for b in bufs]) for k in range(4)))
-    mask, f64 = LC.kept_rays(sc, inp)
+    inp = LC.oracle_inputs(sc, oracle)
+    mask, f64, _ = LC.kept_rays(sc, inp)
     n, S = inp["n"], sc["max_samples"]
     if name == "ert_opaque":
         assert (f64["steps"] < np.minimum(n, S))[mask].any()
     if name == "clip_S23":
         assert (n > S)[mask].any() and (f64["steps"][mask] <= S).all()
     assert (f64["rgba"][mask][:, 3] > 0).all()
+
+
+# what each edge scene is for, asserted on the float64 transliteration so that a scene cannot quietly stop exercising its path
+EARLY = {"sh_half_opaque_sr2", "nd_opaque0_sr4", "nd_overexposed"}            # kept rays stop before their last sample
+BRIGHT = {"nd_thin0_no_clip", "nd_opaque0_sr4", "nd_overexposed", "nd_sh32"}  # kept rays composite samples with Lraw > 1
+WITH_GRADIENTS = {"light_far", "kd_zero"}                                     # (besides the zero-column and per-view scenes)
+
+
+@pytest.mark.parametrize("name", list(LC.EDGE_CASES) + list(LC.NONDIFF_CASES))
+def test_edge_scenes_keep_enough_rays_and_reach_their_paths(oracle, name):
+    """test_both_transliterations_keep_enough_rays for the scenes of tests/test_gpu_lighting_edges.py, the non-differentiable
+    ones through the non-differentiable transliteration and its `near` (the skip threshold's band)."""
+    sc = LC.scene(name)
+    inp = LC.oracle_inputs(sc, oracle)
+    mask, f64, f32 = LC.kept_rays(sc, inp)
+    n, S, light = inp["n"], sc["max_samples"], sc["light"]
+    assert (f64["rgba"][mask][:, 3] > 0).any()
+    if name in EARLY:
+        assert (f64["steps"] < (n if sc["nondiff"] else np.minimum(n, S)))[mask].any()
+    if sc["nondiff"]:
+        assert (f64["rgba"] <= 1.0).all() and (f32["rgba"] <= 1.0).all()
+        # a kept ray skips a sample (alpha <= 1e-3) and composites another
+        assert ((f64["skipped"] > 0) & (f64["skipped"] < f64["steps"]) & (f64["rgba"][..., 3] > 0))[mask].sum() >= 10
+        if name in BRIGHT:
+            assert (f64["bright"] > 0)[mask].any()                 # composited with L = Lraw > 1: nothing clamps the lighting
+        if name == "nd_thin0_no_clip":
+            assert (f64["steps"] > S)[mask].any() and S == 23      # no max_samples clip
+        if name == "nd_overexposed":
+            over = (f64["raw"][..., :3] > 1.0).any(-1) & mask
+            assert over.sum() >= 10 and (f64["rgba"][over][:, :3].max(-1) == 1.0).all()   # only the final min(1, .) holds them
+        if name == "nd_sh32":
+            assert light[0, 9] == 32.0 and (light[0, :9] != LR.reference_light(sc["cam"])[0, :9]).all()
+        if name == "nd_f16_volume":
+            assert sc["f16"] and np.array_equal(sc["vol"], sc["vol"].astype(np.float16).astype(np.float64))
+        if name == "nd_per_view":
+            assert sc["vol"].ndim == 4 and sc["tf"].ndim == 3 and len(light) == 3
+        return
+    if name == "light_inside":
+        assert (np.abs(light[0, :3]) < 1.0).all()                  # inside the box [-1, 1]^3 that ray_setup intersects
+    if name.startswith("sh_"):
+        assert light[0, 9] == {"sh_half": 0.5, "sh_half_opaque_sr2": 0.5, "sh_one": 1.0, "sh_zero": 0.0, "sh_200": 200.0}[name]
+    if name in ("R2", "R6_three_views"):
+        assert 48 * sc["tf"].shape[0] < 320                         # TF + double d_tf table: shorter than the reduction's scratch
+    if name.startswith("image_"):
+        assert mask.all() and mask.size < 64                        # every pixel is live and kept; less than one wave of them
+    if not (sc["zero"] or sc["per_view"] or name in WITH_GRADIENTS):
+        return
+    st = LC.reference_state(sc, inp["entry"], inp["exit"], inp["rays"], n)
+    ref, ref32 = st["ref"], st["ref32"]
+    cols = np.abs(ref["dlight_ray"]).sum((0, 1, 2))
+    for r in (ref, ref32):
+        assert np.isfinite(r["dlight_ray"]).all()
+        for k in range(10):
+            if k in sc["zero"]:
+                assert (r["dlight_ray"][..., k] == 0).all() and (r["dlight"][:, k] == 0).all(), k   # exactly, ray by ray
+            else:
+                assert np.abs(r["dlight_ray"][..., k]).sum() > 0, k
+    if name == "light_far":
+        assert cols[:3].max() < 1e-3 * cols[3:8].min()              # d p: three orders below d lc, d ka and d kd
+        assert cols[:3].max() < cols[3:].min()                      # ... and the smallest column of all
+    if sc["per_view"]:
+        V = len(light)
+        assert ref["dvol"].shape == sc["vol"].shape and ref["dtf"].shape == sc["tf"].shape
+        for k in ("dvol", "dtf"):
+            big = np.abs(ref[k]).max()
+            assert all(np.abs(ref[k][a] - ref[k][b]).max() > 1e-3 * big for a in range(V) for b in range(a))
+
+
+# --- 3b. the non-differentiable transliteration and the per-view inputs of `run` ----------------------------------------------------
+
+def _golden_nondiff(name):
+    """A committed setup_nondiff_* fixture -> (the fixture, the non-differentiable transliteration at the reference's lighting on
+    the fixture's ray buffers, the rays both march). make_setup_nondiff_golden.raycast_nondiff (numpy, its own helpers)
+    reproduces the fixture's image exactly. Single-sample rays are left out (H6: `run` does not march them)."""
+    import make_setup_nondiff_golden as NG
+    z = np.load(os.path.join(HERE, "golden", f"setup_nondiff_{name}.npz"))
+    W, H = z["n"].shape
+    want, live, _ = NG.raycast_nondiff(z["vol"], z["tf"], z["cam"], z["entry"].reshape(-1), z["exit"].reshape(-1),
+                                       z["rays"].reshape(-1, 3), z["n"].reshape(-1).astype(np.int64), float(z["sr"]))
+    assert np.array_equal(want.reshape(W, H, 4), z["rgba"]) and np.array_equal(live.reshape(W, H), z["live"])
+    inp = dict(vol=z["vol"], tf=z["tf"], cam=z["cam"][None], entry=np.nan_to_num(z["entry"])[None], exit=np.nan_to_num(z["exit"])[None],
+               rays=z["rays"][None], n=z["n"][None], sr=float(z["sr"]), max_samples=1)   # (max_samples is not read: no clip)
+    got = LR.run(inp, LR.reference_light(z["cam"]), mode="nondiff")
+    ok = z["n"] > 1
+    assert ok.sum() > 100 and (got["steps"][0] == z["live"])[ok].all() and (z["live"] > 1)[ok].any()
+    assert (got["raw"][0][ok] >= got["rgba"][0][ok]).all()
+    return z, got, ok
+
+
+def test_reference_lighting_reproduces_the_golden_raycast_nondiff():
+    """At the reference's lighting the non-differentiable transliteration is make_setup_nondiff_golden.raycast_nondiff to 1e-14,
+    on the fixture at rate 8 whose rays terminate early."""
+    z, got, ok = _golden_nondiff("e_sr8_ert")
+    assert (z["live"] < z["n"])[ok].any() and z["rgba"][ok].max() > 0.9
+    assert np.abs(got["rgba"][0] - z["rgba"])[ok].max() <= 1e-14
+
+
+def test_reference_lighting_skips_the_samples_the_golden_raycast_nondiff_skips():
+    """The fixture whose TF has stretches of alpha 0 (none of the others skips a sample): equal live counts, and the alpha
+    channel -- which holds every skip decision and nothing of the lighting -- to 1e-14. The colours are printed, not asserted
+    at that bar: the two float64 programs normalise the normal and the light direction in different operation orders, r.v differs
+    by an ulp or two, r.v^32 multiplies that by 32 per sample, and the colours of this fixture end 1.6e-14 apart (1.3e-14 on
+    c_far_sr03, 3.0e-14 on b_aniso_sr4, 5e-15 on the other two)."""
+    z, got, ok = _golden_nondiff("a_orbit_sr1")
+    assert ((got["skipped"][0] > 0) & (got["skipped"][0] < got["steps"][0]))[ok].sum() > 50
+    print("colour difference", np.abs(got["rgba"][0] - z["rgba"])[ok][:, :3].max())
+    assert np.abs(got["rgba"][0] - z["rgba"])[ok][:, 3].max() <= 1e-14 and z["rgba"][ok][:, 3].max() > 0.5
+
+
+def test_per_view_copies_of_shared_inputs_are_the_shared_run(oracle):
+    """`run` with V copies of one volume and TF as per-view inputs: every view's image and per-ray d_light are the shared run's
+    to the bit, each view's d_vol / d_tf is the shared run of that view alone, and they sum to the shared run's."""
+    inp, L = _small_scene(LC.SIDE)
+    cam2 = oracle.in_circles(2.9).astype(np.float64)
+    e, x, r, n = oracle.ray_setup(cam2, 6, 5, inp["vol"].shape, sr=1.0, dtype=np.float64)
+    two = lambda a, b: np.concatenate([a, b[None]])
+    inp = dict(inp, cam=two(inp["cam"], cam2), entry=two(inp["entry"], e), exit=two(inp["exit"], x), rays=two(inp["rays"], r),
+               n=two(inp["n"], n), grad_out=np.random.RandomState(8).standard_normal((2, 6, 5, 4)))
+    L = np.stack([L[0], np.asarray(LC.VIEW_B, np.float64)])
+    shared = LR.run(inp, L)
+    per = LR.run(dict(inp, vol=np.stack([inp["vol"]] * 2), tf=np.stack([inp["tf"]] * 2)), L)
+    assert per["dvol"].shape == (2, *inp["vol"].shape) and per["dtf"].shape == (2, 8, 4)
+    for k in ("rgba", "steps", "near", "clamped", "dlight_ray", "dlight"):
+        assert np.array_equal(per[k], shared[k]), k
+    only = lambda v: np.arange(2)[:, None, None] == v + np.zeros((2, 6, 5), int)
+    for k in ("dvol", "dtf"):
+        big = np.abs(shared[k]).max()
+        assert big > 0 and np.abs(per[k].sum(0) - shared[k]).max() <= 1e-13 * big, k
+        for v in range(2):
+            alone = LR.run(inp, L, pixels=only(v))[k]
+            assert np.abs(per[k][v]).max() > 0 and np.abs(per[k][v] - alone).max() <= 1e-13 * big, (k, v)
+    for mode in ("diff", "nondiff"):
+        a = LR.run(inp, L, want_grad=False, mode=mode)
+        b = LR.run(dict(inp, vol=np.stack([inp["vol"]] * 2), tf=np.stack([inp["tf"]] * 2)), L, want_grad=False, mode=mode)
+        assert all(np.array_equal(a[k], b[k]) for k in a), mode
 
 
 # --- 4. the module's argument checks, before any device call ----------------------------------------------------------------------
