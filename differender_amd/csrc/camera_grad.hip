@@ -27,11 +27,7 @@ template <typename VT>
 struct CamParams : RayParams<VT> {
     const int32_t *fwd_steps;   // the forward's live samples per ray
     int img_W, row0;
-    float near_, near_w, near_h;
-    uint32_t jitter_seed, view_base;
-    double *d_cam; float *d_cam_ray;
-    const float *pose, *fov_v;   // POSE: [views][9] look_from, look_at, up; [views] fov in radians, nullable
-    double near_d, aspect;       // ... the near plane and img_W / H as doubles, for a view's own extents
+    CamFields cf;               // (aspect: img_W / H)
 };
 
 // POSE: the gradient w.r.t. the free camera's ten parameters (look_from, look_at, up, fov) from the same four sums -- only the
@@ -47,21 +43,21 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
     PoseGrad dpose = pose_zero();
     int i, j;
     const bool in_img = tile_pixel(P.W, P.H, i, j);
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
     // H6: a single-sample ray sits at 0/0 in the reference and contributes nothing
     if (in_img && P.nsamp[p] > 1) {
-        VolView<VT> vol = P.vol;
-        vol.p += view * P.vol_vs;
-        const f3 lf = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
+        Ray<VT> ray;   // (open_ray's parts: the loads keep the order they had, which the generated code follows)
+        open_view(ray, view, P.vol, P.vol_vs, P.cam);
+        const VolView<VT> &vol = ray.vol;
+        const f3 lf = ray.cam;
         const f3 light = make_f3(lf.x + 0.0f, lf.y + 1.0f, lf.z + 0.0f);
-        RayGeom rg;
-        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+        open_geom<false>(ray, p, P.entry, P.exit_, P.rays, P.nsamp);
+        const RayGeom &rg = ray.rg;
+        const f3 vd = ray.vd;
         int nmarch = rg.n > P.S ? P.S : rg.n;
         nmarch = min(nmarch, P.fwd_steps[p]);   // the forward's live samples (early termination frozen)
-
-        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
-        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+        open_adjoint(ray, p, P.grad_out, P.out_fwd);
+        const float4 go = ray.go, of = ray.of;
         const float delta = 1e-3f;
         f3 sP = make_f3(0.f, 0.f, 0.f), sTG = make_f3(0.f, 0.f, 0.f);
         float s0 = 0.f, s1 = 0.f;
@@ -120,16 +116,16 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
 
         if (POSE) {
             // once per ray: the ten pose gradients from the four sums (dr_camera.h), then D5
-            const PoseRay q = pose_ray(P.pose, P.fov_v, view, P.near_d, P.aspect, P.near_w, P.near_h, i + P.row0, P.img_W, j, P.H,
-                                       rg.n, P.jitter_seed, P.view_base + (uint32_t)view);
-            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.near_, sP, sTG, s0 * q.A, fmaf(s0, 1.0f - q.A, s1)));
+            const PoseRay q = pose_ray(P.cf.pose, P.cf.fov_v, view, P.cf.near_d, P.cf.aspect, P.cf.near_w, P.cf.near_h, i + P.row0,
+                                       P.img_W, j, P.H, rg.n, P.cf.jitter_seed, P.cf.view_base + (uint32_t)view);
+            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.cf.near_, sP, sTG, s0 * q.A, fmaf(s0, 1.0f - q.A, s1)));
         } else {
             // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw behind grad t0
             M3 J;
             f3 g_tmin, g_tmax, g_t0;
             float u;
-            camera_ray_tail(lf, vd, i + P.row0, P.img_W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed,
-                            P.view_base + (uint32_t)view, J, g_tmin, g_tmax, g_t0, u);
+            camera_ray_tail(lf, vd, i + P.row0, P.img_W, j, P.H, P.cf.near_, P.cf.near_w, P.cf.near_h, rg.n, P.cf.jitter_seed,
+                            P.cf.view_base + (uint32_t)view, J, g_tmin, g_tmax, g_t0, u);
             dcam = f3_add(sP, mul_t(J, sTG));
             dcam = f3_fma(s0, g_t0, dcam);
             dcam = f3_fma(s1, g_tmax, dcam);
@@ -137,18 +133,16 @@ __global__ __launch_bounds__(256) void camera_grad_kernel(CamParams<VT> P) {
             dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
         }
     }
-    if (POSE) pose_reduce(dpose, in_img, p, view, P.d_cam_ray, P.d_cam, red);
-    else camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    if (POSE) pose_reduce(dpose, in_img, p, view, P.cf.d_cam_ray, P.cf.d_cam, red);
+    else camera_reduce(dcam, in_img, p, view, P.cf.d_cam_ray, P.cf.d_cam, red);
 }
 
 template <typename VT>
 static int cam_dispatch(const MarchArgs &a, const CamArgs &c, hipStream_t stream) {
     CamParams<VT> P{make_ray_params<VT>(a)};
     P.fwd_steps = c.steps; P.img_W = a.img_W; P.row0 = a.row0;
-    near_plane_extents(a.fov_rad, a.near_plane, a.img_W, a.H, P.near_, P.near_w, P.near_h);
-    P.jitter_seed = c.jitter_seed; P.view_base = c.view_base;
-    P.d_cam = c.d_cam; P.d_cam_ray = c.d_cam_ray;
-    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)a.img_W / (double)a.H;
+    P.cf = fill_cam_fields(a, c.jitter_seed, c.view_base, c.d_cam, c.d_cam_ray);
+    // (not dr_tile.h's table_tier: tests/test_gpu_camera_grad_edges.py reads the limit from the statement below)
     if (a.pose) {   // (the table tiers of the fixed camera, below)
         const size_t lds_p = (size_t)a.R * sizeof(float4);
         if (lds_p <= 48 * 1024) return launch_tiles(camera_grad_kernel<VT, true, true>, a, lds_p, stream, P);

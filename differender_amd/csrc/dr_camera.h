@@ -1,8 +1,11 @@
 // dr_camera.h -- the chain rule of the camera position look_from through ray setup, shared by the camera
 // gradients of the march (camera_grad.hip) and of the projections (projection.hip): the Jacobian of the ray direction, the
-// gradients of the slab distances, and the rows of the faces a ray's entry and exit picked (VR.py:28-53, 127-151).
+// gradients of the slab distances, and the rows of the faces a ray's entry and exit picked (VR.py:28-53, 127-151); the
+// once-per-ray tails and the reductions (march_rgba.hip's camera gradient too), and the kernel parameters every camera backward
+// adds to its march's, with their one builder.
 #pragma once
 #include "dr_device.h"
+#include "dr_kernels.h"
 
 namespace dr {
 
@@ -105,6 +108,24 @@ inline void near_plane_extents(double fov_rad, double near_plane, int img_W, int
     const double h = 2.0 * tan(fov_rad) * near_plane;
     const double w = h * ((double)img_W / (double)H);
     near_ = (float)near_plane; near_w = (float)w; near_h = (float)h;
+}
+
+// What a camera backward reads beside its march's parameters: the near plane as ray_setup.hip formed it, the jitter seed, the
+// outputs, and the free camera (a kernel's parameter struct embeds this after its own fields).
+struct CamFields {
+    float near_, near_w, near_h;
+    uint32_t jitter_seed, view_base;
+    double *d_cam; float *d_cam_ray;
+    const float *pose, *fov_v;   // POSE: [views][9] look_from, look_at, up; [views] fov in radians, nullable
+    double near_d, aspect;       // ... the near plane and img_W / H as doubles, for a view's own extents
+};
+inline CamFields fill_cam_fields(const MarchArgs &a, uint32_t jitter_seed, uint32_t view_base, double *d_cam, float *d_cam_ray) {
+    CamFields f;
+    near_plane_extents(a.fov_rad, a.near_plane, a.img_W, a.H, f.near_, f.near_w, f.near_h);   // (img_W = W unless a band)
+    f.jitter_seed = jitter_seed; f.view_base = view_base;
+    f.d_cam = d_cam; f.d_cam_ray = d_cam_ray;
+    f.pose = a.pose; f.fov_v = a.fov_v; f.near_d = a.near_plane; f.aspect = (double)a.img_W / (double)a.H;
+    return f;
 }
 
 // Once per ray: J = d vd / d look_from and the rows of the slab faces the forward picked (VR.py:28-53, same arithmetic as

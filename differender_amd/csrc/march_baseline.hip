@@ -29,27 +29,22 @@ __global__ __launch_bounds__(256) void march_fwd_baseline_kernel(MarchParams<VT>
 
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    VolView<VT> vol = P.vol;
-    vol.p += view * P.vol_vs;
-    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-    const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
-
-    RayGeom rg;
-    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-    const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-    const int nmarch = (MODE == DR_MODE_DIFF && rg.n > P.S) ? P.S : rg.n;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
+    Ray<VT> ray;
+    open_ray<false>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp);
+    const f3 light = make_f3(ray.cam.x + 0.0f, ray.cam.y + 1.0f, ray.cam.z + 0.0f);
+    const int nmarch = (MODE == DR_MODE_DIFF && ray.rg.n > P.S) ? P.S : ray.rg.n;
 
     Composite c;
     int cnt = 0;
     for (int s = 0; s < nmarch; ++s) {
         if (!(c.A < 0.99f)) break;
         Sample sm;
-        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
-        classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
+        sample_pos(ray, s, sm.px, sm.py, sm.pz);
+        classify(ray.vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
         ++cnt;
         if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
-        shade(vol, light, vd, MODE == DR_MODE_DIFF, sm);
+        shade(ray.vol, light, ray.vd, MODE == DR_MODE_DIFF, sm);
         c.add(sm);
     }
     reinterpret_cast<float4 *>(P.out)[p] = c.pixel(MODE == DR_MODE_NONDIFF);
@@ -59,14 +54,12 @@ __global__ __launch_bounds__(256) void march_fwd_baseline_kernel(MarchParams<VT>
 // TABLES: what the workgroup keeps in LDS --
 //   2: [R] TF + [R][4] d_tf accumulators in double (48 R bytes: R <= 3392);
 //   1: the TF only; d_tf contributions go straight to the caller's tensor with float atomics (16 R bytes: R <= 10176; at such
-//      resolutions a texel collects few samples of a workgroup, so the summation noise the double table exists for -- below -- is
+//      resolutions a texel collects few samples of a workgroup, so the summation noise the double table exists for -- dtf_add -- is
 //      not a concern);
 //   0: nothing: the TF is read where it lies (any R; the reference has no limit on the TF resolution).
 template <typename VT, int TABLES>
 __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT> P) {
-    // TABLES == 2: [R] TF, then [R][4] dTF accumulators in DOUBLE: thousands of samples of a workgroup land on a few texels (all of them on
-    // one when R = 1), and f32 atomics in thread order put 1e-3 of summation noise on d_tf at sampling rate 16 (fuzz seed 603239,
-    // round 4); the oracle sums d_tf in double for the same reason (its d_tf accumulators), so this keeps the twin a twin
+    // TABLES == 2: [R] TF, then [R][4] d_tf accumulators in double (dr_tile.h's dtf_add says why: fuzz seed 603239)
     extern __shared__ __attribute__((aligned(16))) float4 lds_tf_[];
     const int view = blockIdx.y;
     double *lds_dtf = reinterpret_cast<double *>(lds_tf_ + P.R);
@@ -81,38 +74,29 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
     if (stale_ws && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
         atomicAdd(const_cast<unsigned int *>(P.ws_mark) + 6, 1u);   // header word 9 (ST_STALE_BWD): the host layer warns
     // (flag 1: irregular rays; 2 = rays of the exact pass, whose backward is ray_exact_bwd_kernel's)
-    if (active && P.only_flagged && !stale_ws) active = P.only_flagged[((size_t)view * P.W + i) * P.H + j] == 1;
+    if (active && P.only_flagged && !stale_ws) active = P.only_flagged[ray_index(P.W, P.H, view, i, j)] == 1;
     if (active) {
-        const size_t p = ((size_t)view * P.W + i) * P.H + j;
-        VolView<VT> vol = P.vol;
-        vol.p += view * P.vol_vs;
         GradView dv = P.dvol;
         const bool want_vol = dv.p != nullptr;
         const bool want_tf = P.d_tf != nullptr;
-        if (want_vol) dv.p += view * P.dvol_vs;
-        const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-        const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
-
-        RayGeom rg;
-        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-        const int nmarch = rg.n > P.S ? P.S : rg.n;
-
-        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
-        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
-        const float delta = 1e-3f;
+        const size_t p = ray_index(P.W, P.H, view, i, j);
+        Ray<VT> ray;
+        open_ray<true>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp, P.grad_out, P.out_fwd,
+                       want_vol ? &dv : nullptr, P.dvol_vs);
+        const f3 light = make_f3(ray.cam.x + 0.0f, ray.cam.y + 1.0f, ray.cam.z + 0.0f);
+        const int nmarch = ray.rg.n > P.S ? P.S : ray.rg.n;
 
         Composite c;
         for (int s = 0; s < nmarch; ++s) {
             if (!(c.A < 0.99f)) break;
             Sample sm;
-            sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
-            classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
-            shade(vol, light, vd, true, sm);
+            sample_pos(ray, s, sm.px, sm.py, sm.pz);
+            classify(ray.vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
+            shade(ray.vol, light, ray.vd, true, sm);
             const float T = c.add(sm);
             const bool last = (s == nmarch - 1) || !(c.A < 0.99f);
             SampleAdj ad;
-            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
+            sample_adjoint(sm, ray.vd, T, c.suffix(ray.go, ray.of), last, ray.go, P.inv_sr, ad);
             float I_bar = want_vol ? intensity_adjoint(sm, lds_tf[sm.lo], lds_tf[sm.hi], ad, P.tf_len) : 0.0f;
             if (P.only_flagged) {
                 // second pass of the brick-centric backward (irregular rays): that path promises finite gradients, so a NaN
@@ -122,35 +106,9 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
                 ad.a_bar = finite_or_zero(ad.a_bar); ad.gx = finite_or_zero(ad.gx); ad.gy = finite_or_zero(ad.gy);
                 ad.gz = finite_or_zero(ad.gz); I_bar = finite_or_zero(I_bar);
             }
-
-            if (want_tf && TABLES < 2) {
-                const float w0 = 1.0f - sm.fr, w1 = sm.fr;
-                float *d0 = dtf_g + 4 * sm.lo, *d1 = dtf_g + 4 * sm.hi;
-                const float v8[8] = {w0 * ad.r_bar, w0 * ad.g_bar, w0 * ad.b_bar, w0 * ad.a_bar, w1 * ad.r_bar, w1 * ad.g_bar, w1 * ad.b_bar, w1 * ad.a_bar};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (P.only_flagged) { atomic_add_sat(d0 + q, v8[q]); atomic_add_sat(d1 + q, v8[4 + q]); }
-                    else { unsafeAtomicAdd(d0 + q, v8[q]); unsafeAtomicAdd(d1 + q, v8[4 + q]); }
-                }
-            } else if (want_tf) {
-                const float w0 = 1.0f - sm.fr, w1 = sm.fr;
-                double *d0 = lds_dtf + 4 * sm.lo, *d1 = lds_dtf + 4 * sm.hi;   // (the products are f32, as in the oracle)
-                atomicAdd(d0 + 0, (double)(w0 * ad.r_bar)); atomicAdd(d0 + 1, (double)(w0 * ad.g_bar));
-                atomicAdd(d0 + 2, (double)(w0 * ad.b_bar)); atomicAdd(d0 + 3, (double)(w0 * ad.a_bar));
-                atomicAdd(d1 + 0, (double)(w1 * ad.r_bar)); atomicAdd(d1 + 1, (double)(w1 * ad.g_bar));
-                atomicAdd(d1 + 2, (double)(w1 * ad.b_bar)); atomicAdd(d1 + 3, (double)(w1 * ad.a_bar));
-            }
-            if (want_vol) {
-                tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz, I_bar);
-                if (!sm.flat) {
-                    tri_scatter_global(vol, dv, sm.px + delta, sm.py, sm.pz, ad.gx);
-                    tri_scatter_global(vol, dv, sm.px - delta, sm.py, sm.pz, -ad.gx);
-                    tri_scatter_global(vol, dv, sm.px, sm.py + delta, sm.pz, ad.gy);
-                    tri_scatter_global(vol, dv, sm.px, sm.py - delta, sm.pz, -ad.gy);
-                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz + delta, ad.gz);
-                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz - delta, -ad.gz);
-                }
-            }
+            if (want_tf && TABLES < 2) dtf_add(dtf_g, sm, ad, P.only_flagged != nullptr);
+            else if (want_tf) dtf_add(lds_dtf, sm, ad);
+            if (want_vol) scatter_taps(ray.vol, dv, sm, I_bar, ad.gx, ad.gy, ad.gz);
         }
     }
     if (P.d_tf && TABLES == 2) {
@@ -176,15 +134,14 @@ static MarchParams<VT> make_params(const MarchArgs &a) {
 
 template <typename VT>
 static int fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
-    size_t lds = (size_t)a.R * sizeof(float4);
-    const bool tf_lds = lds <= LDS_PER_CU;   // (R <= 10176; a larger TF is read from global memory)
-    if (!tf_lds) lds = 0;
+    const TableTier t = table_tier(a.R, false);   // (R <= 10176; a larger TF is read from global memory)
+    const bool tf_lds = t.tables == 1;
     const MarchParams<VT> P = make_params<VT>(a);
     if (a.mode == DR_MODE_DIFF)
         return launch_tiles(tf_lds ? march_fwd_baseline_kernel<VT, DR_MODE_DIFF, true> : march_fwd_baseline_kernel<VT, DR_MODE_DIFF, false>,
-                            a, lds, stream, P);
+                            a, t.lds, stream, P);
     return launch_tiles(tf_lds ? march_fwd_baseline_kernel<VT, DR_MODE_NONDIFF, true> : march_fwd_baseline_kernel<VT, DR_MODE_NONDIFF, false>,
-                        a, lds, stream, P);
+                        a, t.lds, stream, P);
 }
 
 int launch_march_fwd_baseline(const MarchArgs &a, hipStream_t stream) {
@@ -194,12 +151,10 @@ int launch_march_fwd_baseline(const MarchArgs &a, hipStream_t stream) {
 template <typename VT>
 static int bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     // TF + its double-precision gradient table in LDS while they fit (R <= 3392), then the TF alone (R <= 10176), then nothing
-    const size_t lds2 = (size_t)a.R * (sizeof(float4) + 4 * sizeof(double)), lds1 = (size_t)a.R * sizeof(float4);
-    const int tables = lds2 <= LDS_PER_CU ? 2 : (lds1 <= LDS_PER_CU ? 1 : 0);
-    const size_t lds = tables == 2 ? lds2 : (tables == 1 ? lds1 : 0);
+    const TableTier t = table_tier(a.R, true);
     const MarchParams<VT> P = make_params<VT>(a);
-    return launch_tiles(tables == 2 ? march_bwd_baseline_kernel<VT, 2> : (tables == 1 ? march_bwd_baseline_kernel<VT, 1> : march_bwd_baseline_kernel<VT, 0>),
-                        a, lds, stream, P);
+    return launch_tiles(t.tables == 2 ? march_bwd_baseline_kernel<VT, 2> : (t.tables == 1 ? march_bwd_baseline_kernel<VT, 1> : march_bwd_baseline_kernel<VT, 0>),
+                        a, t.lds, stream, P);
 }
 
 int launch_march_bwd_baseline(const MarchArgs &a, hipStream_t stream) {

@@ -3,13 +3,13 @@
 // (VR.py:91-95, 281-299); here these are ten per-view parameters light[view][10] (dr_light.h), and the backward also returns
 // their gradients. Everything else is march_baseline.hip's: one lane per ray, a wave per 8x8 pixel tile, direct global gathers,
 // the TF in LDS, global float atomics for d_vol; positions, jitter, n, the max_samples clip, the TF lookup, the six normal taps,
-// D1's flat normals and the termination at A >= 0.99 are the same statements. At the reference's values the forward image is
+// D1's flat normals and the termination at A >= 0.99 are the same statements, and what surrounds the sample loops is the same
+// code (dr_tile.h: open_ray's parts, dtf_add, scatter_taps). At the reference's values the forward image is
 // DR_VARIANT_BASELINE's bit for bit.
 //
 // Forward   : VR.py:261-306 + 363-372; nondiff: VR.py:308-361.
 // Backward  : march_bwd_baseline_kernel's tape-free walk (same frozen branches) with sample_adjoint_lit; the ten lighting sums
 //   are f32 per ray, D5 once per ray, f64 per workgroup, one f64 atomic per component and workgroup (light_reduce).
-// The kernels have their own parameter struct and the shared helpers are not edited: every other kernel compiles as before.
 #include "dr_light.h"
 #include "dr_tile.h"
 
@@ -29,28 +29,24 @@ __global__ __launch_bounds__(256) void march_lit_fwd_kernel(LitParams<VT> P) {
 
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    VolView<VT> vol = P.vol;
-    vol.p += view * P.vol_vs;
-    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
+    const size_t p = ray_index(P.W, P.H, view, i, j);
+    Ray<VT> ray;
+    open_view(ray, view, P.vol, P.vol_vs, P.cam);
     const Light lt = load_light(P.light + 10 * view);   // uniform per blockIdx.y: scalar loads, once
     const bool sh32 = lt.sh == 32.0f;
-
-    RayGeom rg;
-    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-    const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-    const int nmarch = (MODE == DR_MODE_DIFF && rg.n > P.S) ? P.S : rg.n;
+    open_geom<false>(ray, p, P.entry, P.exit_, P.rays, P.nsamp);
+    const int nmarch = (MODE == DR_MODE_DIFF && ray.rg.n > P.S) ? P.S : ray.rg.n;
 
     CompositeLit c;
     int cnt = 0;
     for (int s = 0; s < nmarch; ++s) {
         if (!(c.A < 0.99f)) break;
         Sample sm;
-        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
-        classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
+        sample_pos(ray, s, sm.px, sm.py, sm.pz);
+        classify(ray.vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
         ++cnt;
         if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
-        shade_lit(vol, lt, sh32, vd, MODE == DR_MODE_DIFF, sm);
+        shade_lit(ray.vol, lt, sh32, ray.vd, MODE == DR_MODE_DIFF, sm);
         c.add_lit(sm, lt.lc);
     }
     reinterpret_cast<float4 *>(P.out)[p] = c.pixel(MODE == DR_MODE_NONDIFF);
@@ -69,66 +65,35 @@ __global__ __launch_bounds__(256) void march_lit_bwd_kernel(LitParams<VT> P) {
 
     int i, j;
     const bool active = tile_pixel(P.W, P.H, i, j);
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
     LightGrad lg = light_zero();
     if (active) {
-        VolView<VT> vol = P.vol;
-        vol.p += view * P.vol_vs;
         GradView dv = P.dvol;
         const bool want_vol = dv.p != nullptr;
         const bool want_tf = P.d_tf != nullptr;
-        if (want_vol) dv.p += view * P.dvol_vs;
-        const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
+        Ray<VT> ray;
+        open_view(ray, view, P.vol, P.vol_vs, P.cam, want_vol ? &dv : nullptr, P.dvol_vs);
         const Light lt = load_light(P.light + 10 * view);
         const bool sh32 = lt.sh == 32.0f;
-
-        RayGeom rg;
-        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-        const int nmarch = rg.n > P.S ? P.S : rg.n;
-
-        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
-        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
-        const float delta = 1e-3f;
+        open_geom<true>(ray, p, P.entry, P.exit_, P.rays, P.nsamp, P.grad_out, P.out_fwd);
+        const int nmarch = ray.rg.n > P.S ? P.S : ray.rg.n;
+        const float4 go = ray.go;
 
         CompositeLit c;
         for (int s = 0; s < nmarch; ++s) {
             if (!(c.A < 0.99f)) break;
             Sample sm;
-            sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
-            classify(vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
-            const float Pw = shade_lit(vol, lt, sh32, vd, true, sm);
+            sample_pos(ray, s, sm.px, sm.py, sm.pz);
+            classify(ray.vol, lds_tf, P.R, P.tf_len, P.inv_sr, sm);
+            const float Pw = shade_lit(ray.vol, lt, sh32, ray.vd, true, sm);
             const float T = c.add_lit(sm, lt.lc);
             const bool last = (s == nmarch - 1) || !(c.A < 0.99f);
             SampleAdj ad;
-            sample_adjoint_lit<LIGHT>(sm, Pw, lt, sh32, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad, lg);
-
-            if (want_tf && TABLES < 2) {
-                const float w0 = 1.0f - sm.fr, w1 = sm.fr;
-                float *d0 = dtf_g + 4 * sm.lo, *d1 = dtf_g + 4 * sm.hi;
-                const float v8[8] = {w0 * ad.r_bar, w0 * ad.g_bar, w0 * ad.b_bar, w0 * ad.a_bar, w1 * ad.r_bar, w1 * ad.g_bar, w1 * ad.b_bar, w1 * ad.a_bar};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { unsafeAtomicAdd(d0 + q, v8[q]); unsafeAtomicAdd(d1 + q, v8[4 + q]); }
-            } else if (want_tf) {
-                const float w0 = 1.0f - sm.fr, w1 = sm.fr;
-                double *d0 = lds_dtf + 4 * sm.lo, *d1 = lds_dtf + 4 * sm.hi;   // (the products are f32, as in the baseline)
-                atomicAdd(d0 + 0, (double)(w0 * ad.r_bar)); atomicAdd(d0 + 1, (double)(w0 * ad.g_bar));
-                atomicAdd(d0 + 2, (double)(w0 * ad.b_bar)); atomicAdd(d0 + 3, (double)(w0 * ad.a_bar));
-                atomicAdd(d1 + 0, (double)(w1 * ad.r_bar)); atomicAdd(d1 + 1, (double)(w1 * ad.g_bar));
-                atomicAdd(d1 + 2, (double)(w1 * ad.b_bar)); atomicAdd(d1 + 3, (double)(w1 * ad.a_bar));
-            }
-            if (want_vol) {
-                const float I_bar = intensity_adjoint(sm, lds_tf[sm.lo], lds_tf[sm.hi], ad, P.tf_len);
-                tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz, I_bar);
-                if (!sm.flat) {
-                    tri_scatter_global(vol, dv, sm.px + delta, sm.py, sm.pz, ad.gx);
-                    tri_scatter_global(vol, dv, sm.px - delta, sm.py, sm.pz, -ad.gx);
-                    tri_scatter_global(vol, dv, sm.px, sm.py + delta, sm.pz, ad.gy);
-                    tri_scatter_global(vol, dv, sm.px, sm.py - delta, sm.pz, -ad.gy);
-                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz + delta, ad.gz);
-                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz - delta, -ad.gz);
-                }
-            }
+            sample_adjoint_lit<LIGHT>(sm, Pw, lt, sh32, ray.vd, T, c.suffix(go, ray.of), last, go, P.inv_sr, ad, lg);
+            if (want_tf && TABLES < 2) dtf_add(dtf_g, sm, ad, false);
+            else if (want_tf) dtf_add(lds_dtf, sm, ad);
+            if (want_vol)
+                scatter_taps(ray.vol, dv, sm, intensity_adjoint(sm, lds_tf[sm.lo], lds_tf[sm.hi], ad, P.tf_len), ad.gx, ad.gy, ad.gz);
         }
         // D5, once per ray. A NaN channel of the upstream gradient drops the whole ray, not only the sums it reaches: d lc_k
         // reads go_k alone and no lighting sum reads go.a, and a ray that gave some of its ten columns would be no gradient
@@ -155,15 +120,14 @@ static LitParams<VT> make_lit_params(const MarchArgs &a, const LitArgs &q) {
 
 template <typename VT>
 static int lit_fwd_dispatch(const MarchArgs &a, const LitArgs &q, hipStream_t stream) {
-    size_t lds = (size_t)a.R * sizeof(float4);
-    const bool tf_lds = lds <= LDS_PER_CU;   // (R <= 10176; a larger TF is read from global memory)
-    if (!tf_lds) lds = 0;
+    const TableTier t = table_tier(a.R, false);   // (R <= 10176; a larger TF is read from global memory)
+    const bool tf_lds = t.tables == 1;
     const LitParams<VT> P = make_lit_params<VT>(a, q);
     if (a.mode == DR_MODE_DIFF)
         return launch_tiles(tf_lds ? march_lit_fwd_kernel<VT, DR_MODE_DIFF, true> : march_lit_fwd_kernel<VT, DR_MODE_DIFF, false>,
-                            a, lds, stream, P);
+                            a, t.lds, stream, P);
     return launch_tiles(tf_lds ? march_lit_fwd_kernel<VT, DR_MODE_NONDIFF, true> : march_lit_fwd_kernel<VT, DR_MODE_NONDIFF, false>,
-                        a, lds, stream, P);
+                        a, t.lds, stream, P);
 }
 
 int launch_march_lit_fwd(const MarchArgs &a, const LitArgs &q, hipStream_t stream) {
@@ -172,16 +136,14 @@ int launch_march_lit_fwd(const MarchArgs &a, const LitArgs &q, hipStream_t strea
 
 template <typename VT, bool LIGHT>
 static int lit_bwd_dispatch(const MarchArgs &a, const LitArgs &q, hipStream_t stream) {
-    // the baseline's tiers: TF + its double-precision gradient table in LDS while they fit (R <= 3392), then the TF alone
-    // (R <= 10176), then nothing; never less than the reduction's own bytes
-    const size_t lds2 = (size_t)a.R * (sizeof(float4) + 4 * sizeof(double)), lds1 = (size_t)a.R * sizeof(float4);
-    const int tables = lds2 <= LDS_PER_CU ? 2 : (lds1 <= LDS_PER_CU ? 1 : 0);
-    size_t lds = tables == 2 ? lds2 : (tables == 1 ? lds1 : 0);
-    if (LIGHT && lds < LIGHT_RED_BYTES) lds = LIGHT_RED_BYTES;
+    // the baseline's tiers, and never less than the reduction's own bytes
+    static_assert(table_tier(2, true, LIGHT_RED_BYTES).tables == 2 && table_tier(2, true, LIGHT_RED_BYTES).lds == LIGHT_RED_BYTES,
+                  "a short table: the reduction's bytes");
+    const TableTier t = table_tier(a.R, true, LIGHT ? LIGHT_RED_BYTES : 0);
     const LitParams<VT> P = make_lit_params<VT>(a, q);
-    return launch_tiles(tables == 2 ? march_lit_bwd_kernel<VT, 2, LIGHT>
-                                    : (tables == 1 ? march_lit_bwd_kernel<VT, 1, LIGHT> : march_lit_bwd_kernel<VT, 0, LIGHT>),
-                        a, lds, stream, P);
+    return launch_tiles(t.tables == 2 ? march_lit_bwd_kernel<VT, 2, LIGHT>
+                                      : (t.tables == 1 ? march_lit_bwd_kernel<VT, 1, LIGHT> : march_lit_bwd_kernel<VT, 0, LIGHT>),
+                        a, t.lds, stream, P);
 }
 
 int launch_march_lit_bwd(const MarchArgs &a, const LitArgs &q, hipStream_t stream) {

@@ -54,12 +54,6 @@ __device__ __forceinline__ float4 ld_voxel4(const __half *p, int64_t sc) {
     return make_float4(__half2float(p[0]), __half2float(p[sc]), __half2float(p[2 * sc]), __half2float(p[3 * sc]));
 }
 
-__device__ __forceinline__ float4 mix4(float4 x, float4 y, float a) {
-    return make_float4(mixf(x.x, y.x, a), mixf(x.y, y.y, a), mixf(x.z, y.z, a), mixf(x.w, y.w, a));
-}
-__device__ __forceinline__ float4 sub4(float4 x, float4 y) { return make_float4(x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w); }
-__device__ __forceinline__ float4 scale4(float4 x, float s) { return make_float4(x.x * s, x.y * s, x.z * s, x.w * s); }
-
 // tri_sample (dr_device.h) on four channels: one cell, eight corner fetches, the lerps x -> y -> z per channel
 template <typename VT, bool VEC>
 __device__ __forceinline__ float4 tri_sample4(const VolView<VT> &v, int64_t sc, const Cell &c) {
@@ -83,21 +77,18 @@ __global__ __launch_bounds__(256) void march_rgba_fwd_kernel(RgbaParams<VT> P) {
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
     const int view = blockIdx.y;
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    VolView<VT> vol = P.vol;
-    vol.p += view * P.vol_vs;
-    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-
-    RayGeom rg;
-    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-    const int m = rgba_samples(rg.n, P.S, NONDIFF);
+    const size_t p = ray_index(P.W, P.H, view, i, j);
+    Ray<VT> ray;
+    open_ray<false>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp);
+    const VolView<VT> &vol = ray.vol;
+    const int m = rgba_samples(ray.rg.n, P.S, NONDIFF);
 
     Composite c;
     int cnt = 0;
     for (int s = 0; s < m; ++s) {
         if (!(c.A < 0.99f)) break;
         Sample sm;
-        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
+        sample_pos(ray, s, sm.px, sm.py, sm.pz);
         Cell cell;
         tri_cell(vol, sm.px, sm.py, sm.pz, cell);
         const float4 v = tri_sample4<VT, VEC>(vol, P.sc, cell);
@@ -155,27 +146,19 @@ __global__ __launch_bounds__(256) void march_rgba_bwd_kernel(RgbaParams<VT> P) {
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
     const int view = blockIdx.y;
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    VolView<VT> vol = P.vol;
-    vol.p += view * P.vol_vs;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
     GradView dv = P.dvol;
-    dv.p += view * P.dvol_vs;
-    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-
-    RayGeom rg;
-    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-    const int m = rgba_samples(rg.n, P.S, false);
-    const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-
-    const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
-    const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+    Ray<VT> ray;
+    open_ray<true>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp, P.grad_out, P.out_fwd, &dv, P.dvol_vs);
+    const VolView<VT> &vol = ray.vol;
+    const int m = rgba_samples(ray.rg.n, P.S, false);
 
     Composite c;
     VoxelRun run;
     for (int s = 0; s < m; ++s) {
         if (!(c.A < 0.99f)) break;
         Sample sm;
-        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
+        sample_pos(ray, s, sm.px, sm.py, sm.pz);
         Cell cell;
         tri_cell(vol, sm.px, sm.py, sm.pz, cell);
         const float4 v = tri_sample4<VT, VEC>(vol, P.sc, cell);
@@ -185,7 +168,7 @@ __global__ __launch_bounds__(256) void march_rgba_bwd_kernel(RgbaParams<VT> P) {
         const float T = c.add(sm);
         const bool last = (s == m - 1) || !(c.A < 0.99f);
         SampleAdj ad;
-        sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
+        sample_adjoint(sm, ray.vd, T, c.suffix(ray.go, ray.of), last, ray.go, P.inv_sr, ad);
         const float adj[4] = {ad.r_bar, ad.g_bar, ad.b_bar, ad.a_bar};
         if (!run.same(cell)) { run.flush(dv, P.dsc, vol.VX, vol.VY, vol.VZ); run.start(cell); }
         run.add(cell, adj);
@@ -224,11 +207,7 @@ __device__ __forceinline__ float4 tri_sample4_grad(const VolView<VT> &v, int64_t
 template <typename VT>
 struct RgbaCamParams : RgbaParams<VT> {
     const int32_t *fwd_steps;   // the forward's live samples per ray
-    float near_, near_w, near_h;
-    uint32_t jitter_seed, view_base;
-    double *d_cam; float *d_cam_ray;
-    const float *pose, *fov_v;   // POSE: [views][9] look_from, look_at, up; [views] fov in radians, nullable
-    double near_d, aspect;       // ... the near plane and W / H as doubles, for a view's own extents
+    CamFields cf;               // (aspect: W / H)
 };
 
 // Gradient of the differentiable RGBA march w.r.t. look_from ([views][3]) or, POSE, the free camera's ten parameters
@@ -243,25 +222,22 @@ __global__ __launch_bounds__(256) void march_rgba_cam_kernel(RgbaCamParams<VT> P
     PoseGrad dpose = pose_zero();
     int i, j;
     const bool in_img = tile_pixel(P.W, P.H, i, j);
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
     // H6: a single-sample ray sits at 0/0 in the reference and contributes nothing
     if (in_img && P.nsamp[p] > 1) {
-        VolView<VT> vol = P.vol;
-        vol.p += view * P.vol_vs;
-        const f3 lf = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
-        RayGeom rg;
-        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+        Ray<VT> ray;
+        open_ray<false>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp);
+        const VolView<VT> &vol = ray.vol;
+        const RayGeom &rg = ray.rg;
+        const f3 lf = ray.cam, vd = ray.vd;
         const int m = min(rgba_samples(rg.n, P.S, false), P.fwd_steps[p]);   // the forward's live samples (early termination frozen)
-
-        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
-        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
+        open_adjoint(ray, p, P.grad_out, P.out_fwd);
         f3 sP = make_f3(0.f, 0.f, 0.f), sTP = make_f3(0.f, 0.f, 0.f);
         float s0 = 0.f, s1 = 0.f;
         Composite c;
         for (int s = 0; s < m; ++s) {
             Sample sm;
-            sample_pos(rg, lf.x, lf.y, lf.z, s, sm.px, sm.py, sm.pz);
+            sample_pos(ray, s, sm.px, sm.py, sm.pz);
             Cell cell;
             tri_cell(vol, sm.px, sm.py, sm.pz, cell);
             float4 gx, gy, gz;
@@ -272,7 +248,7 @@ __global__ __launch_bounds__(256) void march_rgba_cam_kernel(RgbaCamParams<VT> P
             const float T = c.add(sm);
             const bool last = s == m - 1;
             SampleAdj ad;
-            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
+            sample_adjoint(sm, ray.vd, T, c.suffix(ray.go, ray.of), last, ray.go, P.inv_sr, ad);
             const f3 Ps = make_f3(ad.r_bar * gx.x + ad.g_bar * gx.y + ad.b_bar * gx.z + ad.a_bar * gx.w,
                                   ad.r_bar * gy.x + ad.g_bar * gy.y + ad.b_bar * gy.z + ad.a_bar * gy.w,
                                   ad.r_bar * gz.x + ad.g_bar * gz.y + ad.b_bar * gz.z + ad.a_bar * gz.w);
@@ -287,16 +263,16 @@ __global__ __launch_bounds__(256) void march_rgba_cam_kernel(RgbaCamParams<VT> P
 
         if (POSE) {
             // once per ray: the ten pose gradients from the four sums (dr_camera.h), then D5
-            const PoseRay q = pose_ray(P.pose, P.fov_v, view, P.near_d, P.aspect, P.near_w, P.near_h, i, P.W, j, P.H, rg.n,
-                                       P.jitter_seed, P.view_base + (uint32_t)view);
-            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.near_, sP, sTP, s0 * q.A, fmaf(s0, 1.0f - q.A, s1)));
+            const PoseRay q = pose_ray(P.cf.pose, P.cf.fov_v, view, P.cf.near_d, P.cf.aspect, P.cf.near_w, P.cf.near_h, i, P.W, j,
+                                       P.H, rg.n, P.cf.jitter_seed, P.cf.view_base + (uint32_t)view);
+            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.cf.near_, sP, sTP, s0 * q.A, fmaf(s0, 1.0f - q.A, s1)));
         } else {
             // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw behind grad t0
             M3 J;
             f3 g_tmin, g_tmax, g_t0;
             float u;
-            camera_ray_tail(lf, vd, i, P.W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed, P.view_base + (uint32_t)view,
-                            J, g_tmin, g_tmax, g_t0, u);
+            camera_ray_tail(lf, vd, i, P.W, j, P.H, P.cf.near_, P.cf.near_w, P.cf.near_h, rg.n, P.cf.jitter_seed,
+                            P.cf.view_base + (uint32_t)view, J, g_tmin, g_tmax, g_t0, u);
             dcam = f3_add(sP, mul_t(J, sTP));
             dcam = f3_fma(s0, g_t0, dcam);
             dcam = f3_fma(s1, g_tmax, dcam);
@@ -304,8 +280,8 @@ __global__ __launch_bounds__(256) void march_rgba_cam_kernel(RgbaCamParams<VT> P
             dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
         }
     }
-    if (POSE) pose_reduce(dpose, in_img, p, view, P.d_cam_ray, P.d_cam, red);
-    else camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    if (POSE) pose_reduce(dpose, in_img, p, view, P.cf.d_cam_ray, P.cf.d_cam, red);
+    else camera_reduce(dcam, in_img, p, view, P.cf.d_cam_ray, P.cf.d_cam, red);
 }
 
 // VEC: a voxel's channels are one aligned 16-B (f32) / 8-B (f16) load wherever the voxel lies
@@ -342,10 +318,7 @@ template <typename VT, bool POSE>
 static int rgba_cam_dispatch(const MarchArgs &a, const RgbaArgs &q, const CamArgs &c, hipStream_t stream) {
     RgbaCamParams<VT> P{make_rgba_params<VT>(a, q)};
     P.fwd_steps = c.steps;
-    near_plane_extents(a.fov_rad, a.near_plane, a.W, a.H, P.near_, P.near_w, P.near_h);
-    P.jitter_seed = c.jitter_seed; P.view_base = c.view_base;
-    P.d_cam = c.d_cam; P.d_cam_ray = c.d_cam_ray;
-    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)a.W / (double)a.H;
+    P.cf = fill_cam_fields(a, c.jitter_seed, c.view_base, c.d_cam, c.d_cam_ray);
     return launch_tiles(rgba_vec_ok(a, q) ? march_rgba_cam_kernel<VT, true, POSE> : march_rgba_cam_kernel<VT, false, POSE>, a, 0,
                         stream, P);
 }

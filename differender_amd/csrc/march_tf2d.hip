@@ -28,10 +28,6 @@ __device__ __forceinline__ void axis_index(float x, int R, int &i0, int &i1, flo
     i1 = min(i0 + 1, R - 1);
 }
 
-__device__ __forceinline__ float4 mix4(float4 x, float4 y, float a) {
-    return make_float4(mixf(x.x, y.x, a), mixf(x.y, y.y, a), mixf(x.z, y.z, a), mixf(x.w, y.w, a));
-}
-
 // sm.I and sm.gnorm must be set; writes sm.r, g, b, a and sm.op
 template <typename VT>
 __device__ __forceinline__ void classify2d(const Tf2dParams<VT> &P, const float4 *tf, Sample &sm, Tf2dSample &t) {
@@ -81,31 +77,26 @@ __global__ __launch_bounds__(256) void march_tf2d_fwd_kernel(Tf2dParams<VT> P) {
 
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    VolView<VT> vol = P.vol;
-    vol.p += view * P.vol_vs;
-    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-    const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
-
-    RayGeom rg;
-    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-    const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-    const int nmarch = (MODE == DR_MODE_DIFF && rg.n > P.S) ? P.S : rg.n;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
+    Ray<VT> ray;
+    open_ray<false>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp);
+    const f3 light = make_f3(ray.cam.x + 0.0f, ray.cam.y + 1.0f, ray.cam.z + 0.0f);
+    const int nmarch = (MODE == DR_MODE_DIFF && ray.rg.n > P.S) ? P.S : ray.rg.n;
 
     Composite c;
     int cnt = 0;
     for (int s = 0; s < nmarch; ++s) {
         if (!(c.A < 0.99f)) break;
         Sample sm;
-        sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
-        sm.I = tri_sample(vol, sm.px, sm.py, sm.pz);
+        sample_pos(ray, s, sm.px, sm.py, sm.pz);
+        sm.I = tri_sample(ray.vol, sm.px, sm.py, sm.pz);
         ++cnt;
         if (SKIP) {
             int v0, v1; float fv;
             axis_index(sm.I * P.tf_len, P.R, v0, v1, fv);
             if (fmaxf(rowmax[v0], rowmax[v1]) <= TF2D_SKIP_BELOW) continue;
         }
-        shade(vol, light, vd, MODE == DR_MODE_DIFF, sm);   // the taps: sm.gnorm
+        shade(ray.vol, light, ray.vd, MODE == DR_MODE_DIFF, sm);   // the taps: sm.gnorm
         Tf2dSample t;
         classify2d(P, tf, sm, t);
         if (MODE == DR_MODE_NONDIFF && !(sm.a > 1e-3f)) continue;
@@ -118,7 +109,6 @@ __global__ __launch_bounds__(256) void march_tf2d_fwd_kernel(Tf2dParams<VT> P) {
 __device__ __forceinline__ float dot4(float4 x, const SampleAdj &ad) {
     return x.x * ad.r_bar + x.y * ad.g_bar + x.z * ad.b_bar + x.w * ad.a_bar;
 }
-__device__ __forceinline__ float4 sub4(float4 x, float4 y) { return make_float4(x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w); }
 
 // d_tf2d contributions of a run of samples in one table cell (the four corner texels i..), summed in f32
 struct CellRun {
@@ -155,39 +145,30 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
 
     int i, j;
     if (tile_pixel(P.W, P.H, i, j)) {
-        const size_t p = ((size_t)view * P.W + i) * P.H + j;
-        VolView<VT> vol = P.vol;
-        vol.p += view * P.vol_vs;
         GradView dv = P.dvol;
         const bool want_vol = dv.p != nullptr;
         const bool want_tf = P.d_tf != nullptr;
-        if (want_vol) dv.p += view * P.dvol_vs;
-        const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-        const f3 light = make_f3(cx + 0.0f, cy + 1.0f, cz + 0.0f);
-
-        RayGeom rg;
-        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
-        const int nmarch = rg.n > P.S ? P.S : rg.n;
-
-        const float4 go = reinterpret_cast<const float4 *>(P.grad_out)[p];
-        const float4 of = reinterpret_cast<const float4 *>(P.out_fwd)[p];
-        const float delta = 1e-3f;
+        const size_t p = ray_index(P.W, P.H, view, i, j);
+        Ray<VT> ray;
+        open_ray<true>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp, P.grad_out, P.out_fwd,
+                       want_vol ? &dv : nullptr, P.dvol_vs);
+        const f3 light = make_f3(ray.cam.x + 0.0f, ray.cam.y + 1.0f, ray.cam.z + 0.0f);
+        const int nmarch = ray.rg.n > P.S ? P.S : ray.rg.n;
 
         Composite c;
         CellRun run;
         for (int s = 0; s < nmarch; ++s) {
             if (!(c.A < 0.99f)) break;
             Sample sm;
-            sample_pos(rg, cx, cy, cz, s, sm.px, sm.py, sm.pz);
-            sm.I = tri_sample(vol, sm.px, sm.py, sm.pz);
-            shade(vol, light, vd, true, sm);
+            sample_pos(ray, s, sm.px, sm.py, sm.pz);
+            sm.I = tri_sample(ray.vol, sm.px, sm.py, sm.pz);
+            shade(ray.vol, light, ray.vd, true, sm);
             Tf2dSample t;
             classify2d(P, tf, sm, t);
             const float T = c.add(sm);
             const bool last = (s == nmarch - 1) || !(c.A < 0.99f);
             SampleAdj ad;
-            sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
+            sample_adjoint(sm, ray.vd, T, c.suffix(ray.go, ray.of), last, ray.go, P.inv_sr, ad);
 
             if (want_tf) {
                 // d rgba / d T[.][.]: the four bilinear weights
@@ -219,20 +200,14 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
                 // through I: the value-axis slope (1 - fg)(b - a) + fg (d - c), times RV - 1, iff 0 < xv
                 const float fv_bar = (1.0f - t.fg) * dot4(sub4(t.b, t.a), ad) + t.fg * dot4(sub4(t.d, t.c), ad);
                 const float I_bar = (0.0f < t.xv) ? fv_bar * P.tf_len : 0.0f;
-                tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz, I_bar);
+                tri_scatter_global(ray.vol, dv, sm.px, sm.py, sm.pz, I_bar);
                 if (!sm.flat) {
                     // through u = |grad| g_scale: the gradient-axis slope hi - lo, times (RG - 1) g_scale, iff 0 < xg, onto the
                     // taps along grad / |grad| -- beside the normal's own adjoint (sample_adjoint)
                     const float fg_bar = dot4(sub4(t.hi, t.lo), ad);
                     const float u_bar = (0.0f < t.xg) ? fg_bar * P.lg : 0.0f;
                     const float k = (u_bar * P.g_scale) * sm.ginv;
-                    const float gx = fmaf(k, sm.grad.x, ad.gx), gy = fmaf(k, sm.grad.y, ad.gy), gz = fmaf(k, sm.grad.z, ad.gz);
-                    tri_scatter_global(vol, dv, sm.px + delta, sm.py, sm.pz, gx);
-                    tri_scatter_global(vol, dv, sm.px - delta, sm.py, sm.pz, -gx);
-                    tri_scatter_global(vol, dv, sm.px, sm.py + delta, sm.pz, gy);
-                    tri_scatter_global(vol, dv, sm.px, sm.py - delta, sm.pz, -gy);
-                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz + delta, gz);
-                    tri_scatter_global(vol, dv, sm.px, sm.py, sm.pz - delta, -gz);
+                    scatter_normal_taps(ray.vol, dv, sm, fmaf(k, sm.grad.x, ad.gx), fmaf(k, sm.grad.y, ad.gy), fmaf(k, sm.grad.z, ad.gz));
                 }
             }
         }
@@ -250,15 +225,15 @@ __global__ __launch_bounds__(256) void march_tf2d_bwd_kernel(Tf2dParams<VT> P) {
 template <typename VT>
 static int tf2d_fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     const size_t NT = (size_t)a.R * a.RG;
-    size_t lds = NT * sizeof(float4) + (a.mode == DR_MODE_NONDIFF ? (size_t)a.R * sizeof(float) : 0);
-    const bool tf_lds = lds <= LDS_PER_CU;
-    if (!tf_lds) lds = 0;
+    // (beside the table, the non-differentiable mode's largest alpha of each row)
+    const TableTier t = table_tier(NT, false, 0, a.mode == DR_MODE_NONDIFF ? (size_t)a.R * sizeof(float) : 0);
+    const bool tf_lds = t.tables == 1;
     const Tf2dParams<VT> P{make_ray_params<VT>(a)};
     if (a.mode == DR_MODE_DIFF)
         return launch_tiles(tf_lds ? march_tf2d_fwd_kernel<VT, DR_MODE_DIFF, true> : march_tf2d_fwd_kernel<VT, DR_MODE_DIFF, false>,
-                            a, lds, stream, P);
+                            a, t.lds, stream, P);
     return launch_tiles(tf_lds ? march_tf2d_fwd_kernel<VT, DR_MODE_NONDIFF, true> : march_tf2d_fwd_kernel<VT, DR_MODE_NONDIFF, false>,
-                        a, lds, stream, P);
+                        a, t.lds, stream, P);
 }
 
 template <typename VT>
@@ -266,12 +241,10 @@ static int tf2d_bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     const size_t NT = (size_t)a.R * a.RG;
     // (a backward without d_tf2d keeps no gradient table: at 64 x 32 texels the f64 table alone would limit a CU to one
     // workgroup)
-    const size_t lds2 = NT * (sizeof(float4) + 4 * sizeof(double)), lds1 = NT * sizeof(float4);
-    const int tables = (a.d_tf && lds2 <= LDS_PER_CU) ? 2 : (lds1 <= LDS_PER_CU ? 1 : 0);
-    const size_t lds = tables == 2 ? lds2 : (tables == 1 ? lds1 : 0);
+    const TableTier t = table_tier(NT, a.d_tf != nullptr);
     const Tf2dParams<VT> P{make_ray_params<VT>(a)};
-    return launch_tiles(tables == 2 ? march_tf2d_bwd_kernel<VT, 2> : (tables == 1 ? march_tf2d_bwd_kernel<VT, 1> : march_tf2d_bwd_kernel<VT, 0>),
-                        a, lds, stream, P);
+    return launch_tiles(t.tables == 2 ? march_tf2d_bwd_kernel<VT, 2> : (t.tables == 1 ? march_tf2d_bwd_kernel<VT, 1> : march_tf2d_bwd_kernel<VT, 0>),
+                        a, t.lds, stream, P);
 }
 
 int launch_march_tf2d_fwd(const MarchArgs &a, hipStream_t stream) {

@@ -15,12 +15,8 @@ namespace dr {
 
 template <typename VT>
 struct ProjParams : RayParams<VT> {
-    int32_t *arg_max;               // MAX: the forward writes it, the backwards read it
-    float near_, near_w, near_h;    // camera backward
-    uint32_t jitter_seed, view_base;
-    double *d_cam; float *d_cam_ray;
-    const float *pose, *fov_v;      // camera backward of the free camera, as CamParams of camera_grad.hip
-    double near_d, aspect;
+    int32_t *arg_max;   // MAX: the forward writes it, the backwards read it
+    CamFields cf;       // camera backward
 };
 
 // samples of a ray (n <= 1: none, as H6)
@@ -33,18 +29,17 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(ProjParams<VT> P) {
     int i, j;
     if (!tile_pixel(P.W, P.H, i, j)) return;
     const int view = blockIdx.y;
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
-    VolView<VT> vol = P.vol;
-    vol.p += view * P.vol_vs;
-    const float cx = P.cam[3 * view], cy = P.cam[3 * view + 1], cz = P.cam[3 * view + 2];
-    RayGeom rg;
-    load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
+    const size_t p = ray_index(P.W, P.H, view, i, j);
+    Ray<VT> ray;
+    open_ray<false>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp);
+    const VolView<VT> &vol = ray.vol;
+    const RayGeom &rg = ray.rg;
     const int m = proj_samples(rg.n, P.S);
     if (MODE == DR_PROJ_SUM) {
         float acc = 0.0f;
         for (int s = 0; s < m; ++s) {
             float px, py, pz;
-            sample_pos(rg, cx, cy, cz, s, px, py, pz);
+            sample_pos(ray, s, px, py, pz);
             acc += tri_sample(vol, px, py, pz);
         }
         P.out[p] = m > 0 ? proj_delta(rg) * acc : 0.0f;
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(ProjParams<VT> P) {
         int arg = -1;
         for (int s = 0; s < m; ++s) {
             float px, py, pz;
-            sample_pos(rg, cx, cy, cz, s, px, py, pz);
+            sample_pos(ray, s, px, py, pz);
             const float v = tri_sample(vol, px, py, pz);
             if (arg < 0 || v > best) { best = v; arg = s; }
         }
@@ -63,7 +58,8 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(ProjParams<VT> P) {
 }
 
 // Volume backward, one lane per ray with global float atomics per tap: SUM (every sample, weight g D) -- the yardstick of the
-// windowed kernel and DR_VARIANT_BASELINE -- and MAX (the one stored argmax sample, weight g).
+// windowed kernel and DR_VARIANT_BASELINE -- and MAX (the one stored argmax sample, weight g). (Its prologue is its own: through
+// open_ray the MAX kernel's scalar loads merge differently.)
 template <typename VT, int MODE>
 __global__ __launch_bounds__(256) void project_bwd_plain_kernel(ProjParams<VT> P) {
     int i, j;
@@ -275,14 +271,13 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
     PoseGrad dpose = pose_zero();
     int i, j;
     const bool in_img = tile_pixel(P.W, P.H, i, j);
-    const size_t p = ((size_t)view * P.W + i) * P.H + j;
+    const size_t p = ray_index(P.W, P.H, view, i, j);
     if (in_img && P.nsamp[p] > 1) {
-        VolView<VT> vol = P.vol;
-        vol.p += view * P.vol_vs;
-        const f3 lf = make_f3(P.cam[3 * view], P.cam[3 * view + 1], P.cam[3 * view + 2]);
-        RayGeom rg;
-        load_ray(P.entry, P.exit_, P.rays, P.nsamp, p, rg);
-        const f3 vd = make_f3(rg.vx, rg.vy, rg.vz);
+        Ray<VT> ray;
+        open_ray<false>(ray, view, p, P.vol, P.vol_vs, P.cam, P.entry, P.exit_, P.rays, P.nsamp);
+        const VolView<VT> &vol = ray.vol;
+        const RayGeom &rg = ray.rg;
+        const f3 lf = ray.cam, vd = ray.vd;
         const int m = proj_samples(rg.n, P.S);
         const float g = P.grad_out[p];
         f3 sP = make_f3(0.f, 0.f, 0.f), sTP = make_f3(0.f, 0.f, 0.f);
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
         }
         for (; s < s_stop; ++s) {
             float px, py, pz;
-            sample_pos(rg, lf.x, lf.y, lf.z, s, px, py, pz);
+            sample_pos(ray, s, px, py, pz);
             f3 gI;
             smu += tri_sample_grad(vol, px, py, pz, gI);
             const float f = (float)s / (float)(rg.n - 1);
@@ -310,19 +305,19 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
         }
         if (POSE) {
             // once per ray: the ten pose gradients from the same sums (dr_camera.h; a projection is never a band), then D5
-            const PoseRay q = pose_ray(P.pose, P.fov_v, view, P.near_d, P.aspect, P.near_w, P.near_h, i, P.W, j, P.H, rg.n,
-                                       P.jitter_seed, P.view_base + (uint32_t)view);
+            const PoseRay q = pose_ray(P.cf.pose, P.cf.fov_v, view, P.cf.near_d, P.cf.aspect, P.cf.near_w, P.cf.near_h, i, P.W, j,
+                                       P.H, rg.n, P.cf.jitter_seed, P.cf.view_base + (uint32_t)view);
             const float nf = (float)rg.n;
             const float E = (MODE == DR_PROJ_SUM && m > 0) ? ((g * smu) / nf) * (1.0f - q.jit / nf) : 0.0f;
-            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.near_, f3_scale(coef, sP), f3_scale(coef, sTP), coef * (s0 * q.A) - E,
-                                              coef * fmaf(s0, 1.0f - q.A, s1) + E));
+            dpose = pose_finite(pose_ray_grad(lf, q, vd, P.cf.near_, f3_scale(coef, sP), f3_scale(coef, sTP),
+                                              coef * (s0 * q.A) - E, coef * fmaf(s0, 1.0f - q.A, s1) + E));
         } else {
             // once per ray: J_vd, the rows of the slab faces the forward picked and the jitter draw (a projection is never a band)
             M3 J;
             f3 g_tmin, g_tmax, g_t0;
             float u;
-            camera_ray_tail(lf, vd, i, P.W, j, P.H, P.near_, P.near_w, P.near_h, rg.n, P.jitter_seed, P.view_base + (uint32_t)view, J,
-                            g_tmin, g_tmax, g_t0, u);
+            camera_ray_tail(lf, vd, i, P.W, j, P.H, P.cf.near_, P.cf.near_w, P.cf.near_h, rg.n, P.cf.jitter_seed,
+                            P.cf.view_base + (uint32_t)view, J, g_tmin, g_tmax, g_t0, u);
             const float nf = (float)rg.n;
             f3 dpos = f3_add(sP, mul_t(J, sTP));
             dpos = f3_fma(s0, g_t0, dpos);
@@ -336,18 +331,15 @@ __global__ __launch_bounds__(256) void project_cam_kernel(ProjParams<VT> P) {
             dcam = make_f3(finite_or_zero(dcam.x), finite_or_zero(dcam.y), finite_or_zero(dcam.z));
         }
     }
-    if (POSE) pose_reduce(dpose, in_img, p, view, P.d_cam_ray, P.d_cam, red);
-    else camera_reduce(dcam, in_img, p, view, P.d_cam_ray, P.d_cam, red);
+    if (POSE) pose_reduce(dpose, in_img, p, view, P.cf.d_cam_ray, P.cf.d_cam, red);
+    else camera_reduce(dcam, in_img, p, view, P.cf.d_cam_ray, P.cf.d_cam, red);
 }
 
 template <typename VT>
 static ProjParams<VT> proj_params(const MarchArgs &a, const ProjArgs &q) {
     ProjParams<VT> P{make_ray_params<VT>(a)};
     P.arg_max = q.arg_max;
-    near_plane_extents(a.fov_rad, a.near_plane, a.img_W, a.H, P.near_, P.near_w, P.near_h);   // (fill_proj: img_W = W)
-    P.jitter_seed = q.jitter_seed; P.view_base = q.view_base;
-    P.d_cam = q.d_cam; P.d_cam_ray = q.d_cam_ray;
-    P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)a.img_W / (double)a.H;
+    P.cf = fill_cam_fields(a, q.jitter_seed, q.view_base, q.d_cam, q.d_cam_ray);   // (fill_proj: img_W = W)
     return P;
 }
 
