@@ -99,6 +99,17 @@ __device__ __forceinline__ FlatLds flat_carve(unsigned char *smem, int R) {
     return L;
 }
 
+// The LDS d_tf table of a backward workgroup: 4 R doubles behind the TF. CM = false: [texel][4], component q of texel k at
+// element 4 k + q -- a 16-lane group that adds one component to different texels walks 32 B apart and meets four bank positions
+// only. CM = true (B1 under DR_BWD_DTF_ROWS): component-major [4][R], consecutive texels in consecutive 8-byte words. The
+// zeroing walks all 4 R elements whatever the layout; the flush walks the CALLER's order g = 4 k + q (coalesced global atomics,
+// dtf64_add) and reads element dtf_slot_of(g); both stay below 4 R for every R (tests/test_bwd_dtf_table.py).
+constexpr bool DTF_CM_B1 = DR_BWD_DTF_ROWS != 0;
+template <bool CM>
+__host__ __device__ constexpr int dtf_slot(int R, int k, int q) { return CM ? q * R + k : 4 * k + q; }
+template <bool CM>
+__host__ __device__ constexpr int dtf_slot_of(int R, int g) { return dtf_slot<CM>(R, g >> 2, g & 3); }
+
 // Walk of the brick's BOX^3 voxel box by a workgroup: 16 lanes per row of BOX (= 15) elements along the axis
 // with the smallest global stride ("a"), FNT/16 rows per pass; rows are numbered r = b + BOX*d over the other two
 // axes. All index arithmetic is 32-bit: the brick origin is folded into a uniform base pointer, in-box offsets
@@ -480,8 +491,9 @@ __device__ __forceinline__ void tap_line(int l0, int lp, int lm, float fp, float
 // times the centre's weights of the other two axes. Planes l0, l0+1 are the centre cell's own: everything that
 // lands there is summed into the centre's 8 corners first (8 LDS adds); what remains per axis is one outside
 // plane of 4 voxels (l0+2 or l0-1; both only when delta >= 0.5 voxel, i.e. dim > 1000: rare uniform branch).
-// 8 + 3*4 = 20 LDS adds per sample instead of 8 per tap.
-template <int ACC, typename PT, typename ST>
+// 8 + 3*4 = 20 LDS adds per sample instead of 8 per tap. NARROW (delta < 0.5 voxel: +delta past l0+1 AND -delta below l0 would
+// take 2 delta > 1) compiles the three "both planes" tests out.
+template <int ACC, bool NARROW, typename PT, typename ST>
 __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, const TapCoords &t, bool valid,
                                                float I_bar, const float (&gq)[3], const FixScale &fs) {
     const float X[2] = {1.0f - t.fx, t.fx}, Y[2] = {1.0f - t.fy, t.fy}, Z[2] = {1.0f - t.fz, t.fz};
@@ -502,17 +514,17 @@ __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, con
     {   // x: outside plane l0+2 (coefficient cx[3]) or l0-1 (cx[0])
         const bool hi = cx[3] != 0.0f, lo = cx[0] != 0.0f;
         if (valid && (hi || lo)) scatter4<ACC>(dst + (hi ? 2 * SX : -SX), SY, SZ, hi ? cx[3] : cx[0], YZ, fs);
-        if (__any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SX, SY, SZ, cx[0], YZ, fs); }
+        if (!NARROW && __any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SX, SY, SZ, cx[0], YZ, fs); }
     }
     {   // y
         const bool hi = cy[3] != 0.0f, lo = cy[0] != 0.0f;
         if (valid && (hi || lo)) scatter4<ACC>(dst + (hi ? 2 * SY : -SY), SX, SZ, hi ? cy[3] : cy[0], XZ, fs);
-        if (__any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SY, SX, SZ, cy[0], XZ, fs); }
+        if (!NARROW && __any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SY, SX, SZ, cy[0], XZ, fs); }
     }
     {   // z
         const bool hi = cz[3] != 0.0f, lo = cz[0] != 0.0f;
         if (valid && (hi || lo)) scatter4<ACC>(dst + (hi ? 2 * SZ : -SZ), SX, SY, hi ? cz[3] : cz[0], XY, fs);
-        if (__any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SZ, SX, SY, cz[0], XY, fs); }
+        if (!NARROW && __any(valid && hi && lo)) { if (valid && hi && lo) scatter4<ACC>(dst - SZ, SX, SY, cz[0], XY, fs); }
     }
     // (In lane order consecutive lanes are consecutive samples of a ray, ~3.5 per cell: these eight adds would collide in the
     // LDS, ~7 cycles per duplicate address INSIDE a 16-lane row, none across rows. Summing the runs across lanes first was tried
@@ -521,10 +533,10 @@ __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, con
     if (valid) scatter8<ACC>(dst, SX, SY, SZ, acc, fs);
 }
 // the common destination: the brick's LDS gradient box, centre cell at element cbase_i
-template <int ACC>
+template <int ACC, bool NARROW>
 __device__ __forceinline__ void scatter_sample(unsigned long long *dbox, const TapCoords &t, bool valid, int cbase_i,
                                                float I_bar, const float (&gq)[3], const FixScale &fs) {
-    scatter_sample<ACC>(dbox + cbase_i, (int)BOX_SX, (int)BOX_SY, 1, t, valid, I_bar, gq, fs);
+    scatter_sample<ACC, NARROW>(dbox + cbase_i, (int)BOX_SX, (int)BOX_SY, 1, t, valid, I_bar, gq, fs);
 }
 // ... from the ROW-TRANSPOSED lane layout (DR_BWD_ROW_SCATTER, dr_tuning.h). The pass computes in lane order -- the tap reads keep
 // their broadcasts, the scans their neighbours -- and only here, in front of the scatter, lane 16 r + c takes over the sample of
@@ -533,7 +545,7 @@ __device__ __forceinline__ void scatter_sample(unsigned long long *dbox, const T
 // commute (ACC_FIX: the box ends bit-identical; the pass's scale is wave-uniform) and ACC_F64 only changes the order of its
 // double adds. Must be called with all 64 lanes enabled (a lane without a sample, or past the end of the wave's samples,
 // passes valid = false and arrives as such).
-template <int ACC>
+template <int ACC, bool NARROW>
 __device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, const TapCoords &t, bool valid, int cbase_i, int lane,
                                                     float I_bar, const float (&gq)[3], const FixScale &fs) {
 #if DR_BWD_ROW_SCATTER
@@ -562,10 +574,44 @@ __device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, co
     u.lxp = (w >> 12) & 1; u.lxm = -((w >> 13) & 1);
     u.lyp = (w >> 14) & 1; u.lym = -((w >> 15) & 1);
     u.lzp = (w >> 16) & 1; u.lzm = -((w >> 17) & 1);
-    scatter_sample<ACC>(dbox, u, w < 0, w & 0xfff, I2, g2, fs);
+    scatter_sample<ACC, NARROW>(dbox, u, w < 0, w & 0xfff, I2, g2, fs);
 #else
-    scatter_sample<ACC>(dbox, t, valid, cbase_i, I_bar, gq, fs);
+    scatter_sample<ACC, NARROW>(dbox, t, valid, cbase_i, I_bar, gq, fs);
 #endif
+}
+
+// B1's d_tf adds of a pass of short runs from the same ROW-TRANSPOSED layout (DR_BWD_DTF_ROWS, dr_tuning.h): lane 16 r + c takes
+// over the d_tf inputs of the sample of lane 4 c + r -- (L op T) gC.rgb, a_bar, the fraction, and one word with both texels
+// (R <= 2030: 11 bits each) and the validity in the sign bit -- in six ds_bpermute_b32, forms the eight products and adds them
+// in double into the component-major table. The ~1.7 samples of a run sit in different 16-lane rows, consecutive texels in
+// consecutive 8-byte words: no run sums across lanes (24 v_add_f32_dpp + 24 v_cndmask + the run bookkeeping per pass), and each
+// sample's products are rounded on their own instead of the run's total. A NaN or an absurd product is dropped or clamped per
+// receiving lane. Must be called with all 64 lanes enabled, like scatter_sample_rows.
+__device__ __forceinline__ void dtf_rows_add(unsigned long long *dtf, int R, int lane, bool valid, int lo, int hi, float fr,
+                                             float cx, float cy, float cz, float a_bar) {
+    static_assert(DTF64_R <= (1 << 11), "a texel index takes 11 bits of the packed word");
+    int l = lane;
+    asm volatile("" : "+v"(l));   // (the source lane's address is made per pass: see scatter_sample_rows)
+    const int a = row_transpose_addr(l);
+    const float gx = row_transpose(cx, a), gy = row_transpose(cy, a), gz = row_transpose(cz, a);
+    const float ab = row_transpose(a_bar, a), f = row_transpose(fr, a);
+    const int w = row_transpose(valid ? (lo | (hi << 11) | (int)0x80000000u) : 0, a);
+    const bool v2 = w < 0;
+    const float w0 = 1.0f - f;
+    const float v8[8] = {w0 * gx, w0 * gy, w0 * gz, w0 * ab, f * gx, f * gy, f * gz, f * ab};
+    // sum of magnitudes (>= the largest one; full-rate adds, and a NaN propagates into the test)
+    const float vmax = ((fabsf(v8[0]) + fabsf(v8[1])) + (fabsf(v8[2]) + fabsf(v8[3]))) +
+                       ((fabsf(v8[4]) + fabsf(v8[5])) + (fabsf(v8[6]) + fabsf(v8[7])));
+    unsigned long long *d0 = dtf + dtf_slot<true>(R, w & 0x7ff, 0), *d1 = dtf + dtf_slot<true>(R, (w >> 11) & 0x7ff, 0);
+    if (__any(v2 && !(vmax <= ACC_LIM))) {  // a NaN or an absurd product: the sanitising path
+        if (v2) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q * R, acc_sanitise(v8[q])); acc_add_f64(d1 + q * R, acc_sanitise(v8[4 + q])); }
+        }
+    } else if (v2) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q * R, v8[q]); acc_add_f64(d1 + q * R, v8[4 + q]); }
+    }
 }
 
 // Backward: the largest and the smallest non-zero |grad_out| (per pixel: its largest component) over the brick's
@@ -618,6 +664,12 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
     constexpr int FNW = FNT / 64;
     constexpr bool BWD_TF = BWD && !WANT_VOL;             // backward w.r.t. the TF only
     constexpr int KS = BWD ? (BWD_TF ? DR_BWDTF_K : 1) : KF;  // consecutive samples per lane
+    // scatter_sample without its three "both outside planes" tests, where delta < 0.5 voxel rules them out. (The d_volume-only
+    // main kernel keeps them: without, the register-minimising scheduler leaves it 118 VGPRs and 36 B of scratch per lane.)
+    constexpr bool ONE_OUTSIDE = NARROW && WANT_TF;
+    // layout of L.dtf (dtf_slot): component-major in B1's main kernel. The work-item kernel keeps the [texel][4] table and the run sums:
+    // it lives with scratch already, and either part of the new path costs it 8 B per lane more
+    constexpr bool DTF_CM = DTF_CM_B1 && BWD && WANT_VOL && WANT_TF && !HEAVY;
     const int nbricks = P.g.NBx * P.g.NBy * P.g.NBz;
     int *live_flag = &const_cast<BrickCtxRec *>(P.ctx)[(size_t)view * nbricks + slot].live;   // "this brick holds live samples of the view"
     const bool count_stats = (slot & 63) == 0;   // diagnostics counters (ST_UNLIT_SKIPPED, ST_EMPTY_BRICKS) are SAMPLED: one workgroup in 64
@@ -1225,6 +1277,12 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     // first lane of this lane's run = highest run-start bit at or below the lane (lane 0 always starts one)
                     const unsigned long long starts = __ballot(run_start);
                     const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
+#if DR_BWD_DTF_ROWS
+                    // a pass of many short runs adds every sample from the transposed lanes; few long runs keep their sums
+                    if (DTF_CM && __popcll(starts) >= DR_BWD_DTF_DIRECT_MIN) {   // wave-uniform
+                        dtf_rows_add(L.dtf, P.R, lane, valid, sm.lo, sm.hi, sm.fr, ad.Lop * go.x, ad.Lop * go.y, ad.Lop * go.z, ad.a_bar);
+                    } else {
+#endif
                     const int rs = 63 - __clzll((long long)(starts & upto));
                     const float w0 = 1.0f - sm.fr, w1 = sm.fr;
                     float tv[4] = {w0 * ad.Lop, w1 * ad.Lop, w0 * ad.a_bar, w1 * ad.a_bar};
@@ -1237,23 +1295,27 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     const float vmax = ((fabsf(v8[0]) + fabsf(v8[1])) + (fabsf(v8[2]) + fabsf(v8[3]))) +
                                        ((fabsf(v8[4]) + fabsf(v8[5])) + (fabsf(v8[6]) + fabsf(v8[7])));
                     // d_tf accumulates in double; a NaN or an absurd run total takes the sanitising path
+                    const int qs = DTF_CM ? P.R : 1;   // elements between the components of a texel (dtf_slot)
                     if (__any(emit && !(vmax <= ACC_LIM))) {
                         if (emit) {
-                            unsigned long long *d0 = L.dtf + 4 * sm.lo, *d1 = L.dtf + 4 * sm.hi;
+                            unsigned long long *d0 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.lo, 0), *d1 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.hi, 0);
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                acc_add_f64(d0 + q, acc_sanitise(v8[q]));
-                                acc_add_f64(d1 + q, acc_sanitise(v8[4 + q]));
+                                acc_add_f64(d0 + q * qs, acc_sanitise(v8[q]));
+                                acc_add_f64(d1 + q * qs, acc_sanitise(v8[4 + q]));
                             }
                         }
                     } else if (emit) {
-                        unsigned long long *d0 = L.dtf + 4 * sm.lo, *d1 = L.dtf + 4 * sm.hi;
+                        unsigned long long *d0 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.lo, 0), *d1 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.hi, 0);
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            acc_add_f64(d0 + q, v8[q]);
-                            acc_add_f64(d1 + q, v8[4 + q]);
+                            acc_add_f64(d0 + q * qs, v8[q]);
+                            acc_add_f64(d1 + q * qs, v8[4 + q]);
                         }
                     }
+#if DR_BWD_DTF_ROWS
+                    }
+#endif
                 }
                 if (WANT_VOL) {
                     // d_volume: fixed-point adds into the LDS gradient box (dr_brick_common.h). A 32-bit addend
@@ -1274,7 +1336,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                             I_bar = acc_sanitise(I_bar);
                             gq[0] = acc_sanitise(gq[0]); gq[1] = acc_sanitise(gq[1]); gq[2] = acc_sanitise(gq[2]);
                         }
-                        scatter_sample_rows<ACC_F64>(L.dbox, t, valid, cbase_i, lane, I_bar, gq, fs);
+                        scatter_sample_rows<ACC_F64, ONE_OUTSIDE>(L.dbox, t, valid, cbase_i, lane, I_bar, gq, fs);
                     } else {
                         // Beyond the range of the fixed-point box (2^12 x the brick's largest upstream gradient: the
                         // normalisation of a nearly vanishing volume gradient amplifies by 1/|grad|, 1e7 and more where
@@ -1289,7 +1351,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                                 const GradView dv = P.dvol;
                                 float *gdst = dv.p + ((long long)view * P.dvol_vs + (long long)(c.ox + t.lx) * dv.sx +
                                                       (long long)(c.oy + t.ly) * dv.sy + (long long)(c.oz + t.lz) * dv.sz);
-                                scatter_sample<ACC_GLOBAL>(gdst, (long long)dv.sx, (long long)dv.sy, (long long)dv.sz, t, over, I_bar, gq, fs);
+                                scatter_sample<ACC_GLOBAL, ONE_OUTSIDE>(gdst, (long long)dv.sx, (long long)dv.sy, (long long)dv.sz, t, over, I_bar, gq, fs);
                             }
                             in_box = valid && !over;
                             I_bar = fix_clamp(I_bar, fs);
@@ -1304,7 +1366,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                             FixScale fw = fs;
                             const float mul = fix_wave_scale(wmax, fw);
                             const float gs[3] = {gq[0] * mul, gq[1] * mul, gq[2] * mul};
-                            scatter_sample_rows<ACC_FIX>(L.dbox, t, in_box, cbase_i, lane, I_bar * mul, gs, fw);
+                            scatter_sample_rows<ACC_FIX, ONE_OUTSIDE>(L.dbox, t, in_box, cbase_i, lane, I_bar * mul, gs, fw);
                         }
                     }
                 }
@@ -1355,7 +1417,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
     }
     if (WANT_TF) {   // (into the call's double table: dtf_commit_kernel hands the sums to the caller's tensor)
         for (int k = threadIdx.x; k < 4 * P.R; k += FNT) {
-            const unsigned long long raw = L.dtf[k];
+            const unsigned long long raw = L.dtf[dtf_slot_of<DTF_CM>(P.R, k)];
             if (raw != 0ull) dtf64_add(P.dtf64, view, k, raw);
         }
     }
@@ -1473,6 +1535,15 @@ int flat_bwd_vol_launch(const MarchArgs &a, BrickParams<VT> P, dim3 grid1, bool 
 }
 template int flat_bwd_vol_launch<float>(const MarchArgs &, BrickParams<float>, dim3, bool, hipStream_t);
 template int flat_bwd_vol_launch<__half>(const MarchArgs &, BrickParams<__half>, dim3, bool, hipStream_t);
+// Host view of B1's LDS d_tf table at resolution R (tests/test_bwd_dtf_table.py; not part of the public header): add_slot[4 k + q] =
+// the element the sample loop adds component q of texel k to, flush_slot[g] = the element the flush hands to entry g of the
+// caller's [texel][4] order; returns the number of elements the zeroing walks.
+extern "C" int dr_b1_dtf_table_map(int R, int *add_slot, int *flush_slot) {
+    for (int k = 0; k < R; ++k)
+        for (int q = 0; q < 4; ++q) add_slot[4 * k + q] = dtf_slot<DTF_CM_B1>(R, k, 0) + q * (DTF_CM_B1 ? R : 1);
+    for (int g = 0; g < 4 * R; ++g) flush_slot[g] = dtf_slot_of<DTF_CM_B1>(R, g);
+    return 4 * R;
+}
 #else
 
 template <typename VT>
