@@ -36,22 +36,6 @@
 #ifndef DR_BWD_ROW_SCATTER
 #define DR_BWD_ROW_SCATTER 1
 #endif
-// B1's d_tf adds from the same transposed layout, into a component-major LDS table [4][R] (march_flat.hip: dtf_rows_add): a pass
-// that holds at least DR_BWD_DTF_DIRECT_MIN runs of samples between the same two texels (segment starts and lanes without a sample
-// count as runs) moves six words per sample to lane 16 r + c <- 4 c + r and every lane adds its own eight products; a pass of fewer,
-// longer runs keeps the run sums across lanes (seg_scan_sum<4>) and adds from the run-end lanes. 0: run sums into [texel][4].
-// MEASURED AND LEFT OFF. The gate (profiles/dtfrows_microbench.txt) promised the scan's ~110 cycles of VALU issue per pass for LDS
-// work a VALU-bound kernel hides; in B1 the LDS is not free (48 % busy with the box scatter and the taps) and the adds cost more
-// than the scan: headline step, same device, alternating runs (profiles/dtfrows_ab.txt), against 8.68 ms with the run sums --
-//   direct from 4 runs per pass on 12.05 ms | 8: 9.38 | 16: 8.81 | 32: 8.67 (level) | never, [4][R] table alone: 8.57 = the [texel][4]
-//   table's 8.55 within the spread; CT-like scene 5.44: 8.10 | 5.92 | 5.72 | 5.57 | 5.45.
-// Neither the direct adds nor the component-major table pays at any threshold; the work-item kernel never takes either (scratch).
-#ifndef DR_BWD_DTF_ROWS
-#define DR_BWD_DTF_ROWS 0
-#endif
-#ifndef DR_BWD_DTF_DIRECT_MIN
-#define DR_BWD_DTF_DIRECT_MIN 8   // runs per pass from which a pass adds directly under DR_BWD_DTF_ROWS (rows above)
-#endif
 // brick-centric backward w.r.t. the TF only (no gradient box, 33 KB of LDS): FOUR-wave workgroups, four per CU -- 3.22 ms against
 // 3.80 with the 8-wave shape at 512^3 (profiles/r03_ab_experiments.txt); 96 VGPRs for a fifth workgroup spill 132 B per lane: 4.08 ms
 #ifndef DR_FNT_BWDTF

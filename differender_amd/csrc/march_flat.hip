@@ -19,7 +19,7 @@
 // add/mul/fma, v_mov and v_add_u32 issue in 2 cycles, everything else in 4 (rcp/rsq 8).
 // Reference functions replaced: VR.py:261-372 and the autodiff twins VR.py:460-461,470-471.
 #include "dr_brick_common.h"
-#include "dr_wave.h"
+#include "dr_dtf.h"
 #include "dr_tuning.h"
 
 namespace dr {
@@ -99,16 +99,10 @@ __device__ __forceinline__ FlatLds flat_carve(unsigned char *smem, int R) {
     return L;
 }
 
-// The LDS d_tf table of a backward workgroup: 4 R doubles behind the TF. CM = false: [texel][4], component q of texel k at
-// element 4 k + q -- a 16-lane group that adds one component to different texels walks 32 B apart and meets four bank positions
-// only. CM = true (B1 under DR_BWD_DTF_ROWS): component-major [4][R], consecutive texels in consecutive 8-byte words. The
-// zeroing walks all 4 R elements whatever the layout; the flush walks the CALLER's order g = 4 k + q (coalesced global atomics,
-// dtf64_add) and reads element dtf_slot_of(g); both stay below 4 R for every R (tests/test_bwd_dtf_table.py).
-constexpr bool DTF_CM_B1 = DR_BWD_DTF_ROWS != 0;
-template <bool CM>
-__host__ __device__ constexpr int dtf_slot(int R, int k, int q) { return CM ? q * R + k : 4 * k + q; }
-template <bool CM>
-__host__ __device__ constexpr int dtf_slot_of(int R, int g) { return dtf_slot<CM>(R, g >> 2, g & 3); }
+// The LDS d_tf table of a backward workgroup: 4 R doubles behind the TF, [texel][4]: component q of texel k at element 4 k + q, the
+// caller's own order (the flush hands element g to entry g: coalesced global atomics, dtf64_add). A 16-lane group that adds one
+// component to different texels walks 32 B apart and meets four bank positions only; the component-major table that would spread
+// them was measured and is no faster (tools/README.md, closed experiments: the d_tf rows).
 
 // Walk of the brick's BOX^3 voxel box by a workgroup: 16 lanes per row of BOX (= 15) elements along the axis
 // with the smallest global stride ("a"), FNT/16 rows per pass; rows are numbered r = b + BOX*d over the other two
@@ -580,38 +574,12 @@ __device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, co
 #endif
 }
 
-// B1's d_tf adds of a pass of short runs from the same ROW-TRANSPOSED layout (DR_BWD_DTF_ROWS, dr_tuning.h): lane 16 r + c takes
-// over the d_tf inputs of the sample of lane 4 c + r -- (L op T) gC.rgb, a_bar, the fraction, and one word with both texels
-// (R <= 2030: 11 bits each) and the validity in the sign bit -- in six ds_bpermute_b32, forms the eight products and adds them
-// in double into the component-major table. The ~1.7 samples of a run sit in different 16-lane rows, consecutive texels in
-// consecutive 8-byte words: no run sums across lanes (24 v_add_f32_dpp + 24 v_cndmask + the run bookkeeping per pass), and each
-// sample's products are rounded on their own instead of the run's total. A NaN or an absurd product is dropped or clamped per
-// receiving lane. Must be called with all 64 lanes enabled, like scatter_sample_rows.
-__device__ __forceinline__ void dtf_rows_add(unsigned long long *dtf, int R, int lane, bool valid, int lo, int hi, float fr,
-                                             float cx, float cy, float cz, float a_bar) {
-    static_assert(DTF64_R <= (1 << 11), "a texel index takes 11 bits of the packed word");
-    int l = lane;
-    asm volatile("" : "+v"(l));   // (the source lane's address is made per pass: see scatter_sample_rows)
-    const int a = row_transpose_addr(l);
-    const float gx = row_transpose(cx, a), gy = row_transpose(cy, a), gz = row_transpose(cz, a);
-    const float ab = row_transpose(a_bar, a), f = row_transpose(fr, a);
-    const int w = row_transpose(valid ? (lo | (hi << 11) | (int)0x80000000u) : 0, a);
-    const bool v2 = w < 0;
-    const float w0 = 1.0f - f;
-    const float v8[8] = {w0 * gx, w0 * gy, w0 * gz, w0 * ab, f * gx, f * gy, f * gz, f * ab};
-    // sum of magnitudes (>= the largest one; full-rate adds, and a NaN propagates into the test)
-    const float vmax = ((fabsf(v8[0]) + fabsf(v8[1])) + (fabsf(v8[2]) + fabsf(v8[3]))) +
-                       ((fabsf(v8[4]) + fabsf(v8[5])) + (fabsf(v8[6]) + fabsf(v8[7])));
-    unsigned long long *d0 = dtf + dtf_slot<true>(R, w & 0x7ff, 0), *d1 = dtf + dtf_slot<true>(R, (w >> 11) & 0x7ff, 0);
-    if (__any(v2 && !(vmax <= ACC_LIM))) {  // a NaN or an absurd product: the sanitising path
-        if (v2) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q * R, acc_sanitise(v8[q])); acc_add_f64(d1 + q * R, acc_sanitise(v8[4 + q])); }
-        }
-    } else if (v2) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q * R, v8[q]); acc_add_f64(d1 + q * R, v8[4 + q]); }
-    }
+// The alpha pre-pass found the segment in slot sgi of the ray of pixel plq unlit: its bit in the ray's layer mask tells the colour
+// march to drop it. Layer = (slot - pixel) / NP through the float reciprocal: exact, the quotient is an integer below 128 and the
+// error of the product below 1e-4.
+__device__ __forceinline__ void mark_unlit(unsigned long long *unlit, int lm_words, int view, int sgi, int plq, int NP) {
+    const int lay = (int)((float)(sgi - plq) * __builtin_amdgcn_rcpf((float)NP) + 0.5f);
+    atomicOr(unlit + ((size_t)view * lm_words + (lay >> 6)) * NP + plq, 1ull << (lay & 63));
 }
 
 // Backward: the largest and the smallest non-zero |grad_out| (per pixel: its largest component) over the brick's
@@ -667,9 +635,6 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
     // scatter_sample without its three "both outside planes" tests, where delta < 0.5 voxel rules them out. (The d_volume-only
     // main kernel keeps them: without, the register-minimising scheduler leaves it 118 VGPRs and 36 B of scratch per lane.)
     constexpr bool ONE_OUTSIDE = NARROW && WANT_TF;
-    // layout of L.dtf (dtf_slot): component-major in B1's main kernel. The work-item kernel keeps the [texel][4] table and the run sums:
-    // it lives with scratch already, and either part of the new path costs it 8 B per lane more
-    constexpr bool DTF_CM = DTF_CM_B1 && BWD && WANT_VOL && WANT_TF && !HEAVY;
     const int nbricks = P.g.NBx * P.g.NBy * P.g.NBz;
     int *live_flag = &const_cast<BrickCtxRec *>(P.ctx)[(size_t)view * nbricks + slot].live;   // "this brick holds live samples of the view"
     const bool count_stats = (slot & 63) == 0;   // diagnostics counters (ST_UNLIT_SKIPPED, ST_EMPTY_BRICKS) are SAMPLED: one workgroup in 64
@@ -836,9 +801,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                         P.seg_rgba[seg_view + sgi] = make_float4(0.f, 0.f, 0.f, 0.f);
                         if constexpr (ALPHA != 0) {
                             if (P.lm_words > 0) {   // tell the colour march that this segment is done (see flat_build_entries)
-                                const int plq = __float_as_int(r1e.w);
-                                const int lay = (int)((float)(sgi - plq) * __builtin_amdgcn_rcpf((float)NP) + 0.5f);
-                                atomicOr(P.unlit + ((size_t)view * P.lm_words + (lay >> 6)) * NP + plq, 1ull << (lay & 63));
+                                mark_unlit(P.unlit, P.lm_words, view, sgi, __float_as_int(r1e.w), NP);
                             }
                         }
                     }
@@ -959,13 +922,8 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                         P.seg_rgba[seg_view + sgi] = make_float4(0.f, 0.f, 0.f, 1.0f - Tl);
                         {
                             // every sample of the ray in this brick was marched (the pre-pass has no live limit) and none is lit: tell the
-                            // colour march (flat_build_entries). Layer = (slot - pixel) / NP through the float reciprocal: exact, the
-                            // quotient is an integer below 128 and the error of the product below 1e-4.
-                            if (!seg_lit && P.lm_words > 0) {
-                                const int plq = __float_as_int(r1.w);
-                                const int lay = (int)((float)(sgi - plq) * __builtin_amdgcn_rcpf((float)NP) + 0.5f);
-                                atomicOr(P.unlit + ((size_t)view * P.lm_words + (lay >> 6)) * NP + plq, 1ull << (lay & 63));
-                            }
+                            // colour march (flat_build_entries)
+                            if (!seg_lit && P.lm_words > 0) mark_unlit(P.unlit, P.lm_words, view, sgi, __float_as_int(r1.w), NP);
                         }
                     }
                 }
@@ -1018,12 +976,8 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                 const bool cont = (carry_e == e_first);
                 const int e_last = __builtin_amdgcn_readlane(e, 63);
                 const bool more = (f0 + 64 * ks < fb) && (offs[e_last + 1] > f0 + 64 * ks);
-                Over2 inc2 = seg_scan_over2(el2, lane, sl), exc2;
-                exc2.w = wave_up1(inc2.w, 0.f); exc2.a = wave_up1(inc2.a, 0.f);
-                if (lane == sl) { exc2.w = 0.f; exc2.a = 0.f; }
-                if (cont && e == e_first) { inc2 = over2(carry2, inc2); exc2 = over2(carry2, exc2); }
-                carry2.w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc2.w), 63));
-                carry2.a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc2.a), 63));
+                Over2 inc2;
+                const Over2 exc2 = scan_over2_carried(el2, lane, sl, cont, e, e_first, carry2, inc2);
                 carry_e = more ? e_last : -1;
                 // adjoints of the lane's samples, front to back (tape-free identity, as sample_adjoint)
                 float tv[KS][4];
@@ -1066,31 +1020,9 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                 float V[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) V[q] = split ? tv[1][q] : tv[0][q] + tv[1][q];
-                const unsigned long long starts = __ballot(start);
-                const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-                const int rs = 63 - __clzll((long long)(starts & upto));  // first lane of this lane's outgoing run (lane 0 starts one)
-                seg_scan_sum<4>(V, lane, rs);
-                const unsigned long long contm = __ballot(contl);
-                const bool run_end = lane == 63 || !((contm >> ((lane + 1) & 63)) & 1ull);
-                auto emit = [&](bool em, const float (&tq)[4], int lo, int hi) {
-                    const float v8[8] = {tq[0] * go.x, tq[0] * go.y, tq[0] * go.z, tq[2], tq[1] * go.x, tq[1] * go.y, tq[1] * go.z, tq[3]};
-                    const float vmax = ((fabsf(v8[0]) + fabsf(v8[1])) + (fabsf(v8[2]) + fabsf(v8[3]))) +
-                                       ((fabsf(v8[4]) + fabsf(v8[5])) + (fabsf(v8[6]) + fabsf(v8[7])));
-                    unsigned long long *d0 = L.dtf + 4 * lo, *d1 = L.dtf + 4 * hi;
-                    if (__any(em && !(vmax <= ACC_LIM))) {  // a NaN or an absurd run total: the sanitising path
-                        if (em) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q, acc_sanitise(v8[q])); acc_add_f64(d1 + q, acc_sanitise(v8[4 + q])); }
-                        }
-                    } else if (em) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q, v8[q]); acc_add_f64(d1 + q, v8[4 + q]); }
-                    }
-                };
-                emit((vA || vB) && run_end, V, key_out, hi_out);
-                if (__any(split)) {  // uniform
-                    // (the DPP moves are pinned in front of the select: the compiler otherwise turns `contl ? dpp : 0` into an
-                    // exec-masked region around the v_mov_dpp, and a DPP move whose SOURCE lane is masked off writes nothing)
+                const bool run_end = dtf_split_runs(lane, contl, start, V);
+                dtf_run_add(L.dtf, key_out, hi_out, (vA || vB) && run_end, V, go);
+                if (__any(split)) {  // uniform; the DPP moves are pinned in front of the select (dr_dtf.h: dtf_split_runs)
                     float Pv[4], H[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) Pv[q] = wave_up1(V[q], 0.f);   // inclusive sum of the previous lane's outgoing run
@@ -1098,7 +1030,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(Pv[q]));
 #pragma unroll
                     for (int q = 0; q < 4; ++q) H[q] = (contl ? Pv[q] : 0.0f) + tv[0][q];
-                    emit(split, H, klo[0], khi[0]);
+                    dtf_run_add(L.dtf, klo[0], khi[0], split, H, go);
                 }
                 continue;
             }
@@ -1271,18 +1203,14 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     // texels. Sum each run across lanes (DPP) and let its last lane do the eight LDS adds. Runs stop
                     // at segment boundaries, so the upstream colour gradient go.xyz is constant over a run and
                     // (r,g,b)_bar = (L*op*T) * go.xyz is applied to the run total: 4 scanned values, not 8.
+                    // (B1 keeps its own spelling of lane_run_sums and dtf_run_add, dr_dtf.h, as of scan_over2_carried above: through
+                    // the helpers the register-minimising scheduler of this translation unit gives other code)
                     const int key = valid ? sm.lo : -1 - lane;
                     const int key_prev = wave_up1(key, key);
                     const bool run_start = lane == 0 || key != key_prev || lane == sl;
                     // first lane of this lane's run = highest run-start bit at or below the lane (lane 0 always starts one)
                     const unsigned long long starts = __ballot(run_start);
                     const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-#if DR_BWD_DTF_ROWS
-                    // a pass of many short runs adds every sample from the transposed lanes; few long runs keep their sums
-                    if (DTF_CM && __popcll(starts) >= DR_BWD_DTF_DIRECT_MIN) {   // wave-uniform
-                        dtf_rows_add(L.dtf, P.R, lane, valid, sm.lo, sm.hi, sm.fr, ad.Lop * go.x, ad.Lop * go.y, ad.Lop * go.z, ad.a_bar);
-                    } else {
-#endif
                     const int rs = 63 - __clzll((long long)(starts & upto));
                     const float w0 = 1.0f - sm.fr, w1 = sm.fr;
                     float tv[4] = {w0 * ad.Lop, w1 * ad.Lop, w0 * ad.a_bar, w1 * ad.a_bar};
@@ -1295,27 +1223,23 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     const float vmax = ((fabsf(v8[0]) + fabsf(v8[1])) + (fabsf(v8[2]) + fabsf(v8[3]))) +
                                        ((fabsf(v8[4]) + fabsf(v8[5])) + (fabsf(v8[6]) + fabsf(v8[7])));
                     // d_tf accumulates in double; a NaN or an absurd run total takes the sanitising path
-                    const int qs = DTF_CM ? P.R : 1;   // elements between the components of a texel (dtf_slot)
                     if (__any(emit && !(vmax <= ACC_LIM))) {
                         if (emit) {
-                            unsigned long long *d0 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.lo, 0), *d1 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.hi, 0);
+                            unsigned long long *d0 = L.dtf + 4 * sm.lo, *d1 = L.dtf + 4 * sm.hi;
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                acc_add_f64(d0 + q * qs, acc_sanitise(v8[q]));
-                                acc_add_f64(d1 + q * qs, acc_sanitise(v8[4 + q]));
+                                acc_add_f64(d0 + q, acc_sanitise(v8[q]));
+                                acc_add_f64(d1 + q, acc_sanitise(v8[4 + q]));
                             }
                         }
                     } else if (emit) {
-                        unsigned long long *d0 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.lo, 0), *d1 = L.dtf + dtf_slot<DTF_CM>(P.R, sm.hi, 0);
+                        unsigned long long *d0 = L.dtf + 4 * sm.lo, *d1 = L.dtf + 4 * sm.hi;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            acc_add_f64(d0 + q * qs, v8[q]);
-                            acc_add_f64(d1 + q * qs, v8[4 + q]);
+                            acc_add_f64(d0 + q, v8[q]);
+                            acc_add_f64(d1 + q, v8[4 + q]);
                         }
                     }
-#if DR_BWD_DTF_ROWS
-                    }
-#endif
                 }
                 if (WANT_VOL) {
                     // d_volume: fixed-point adds into the LDS gradient box (dr_brick_common.h). A 32-bit addend
@@ -1417,7 +1341,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
     }
     if (WANT_TF) {   // (into the call's double table: dtf_commit_kernel hands the sums to the caller's tensor)
         for (int k = threadIdx.x; k < 4 * P.R; k += FNT) {
-            const unsigned long long raw = L.dtf[dtf_slot_of<DTF_CM>(P.R, k)];
+            const unsigned long long raw = L.dtf[k];
             if (raw != 0ull) dtf64_add(P.dtf64, view, k, raw);
         }
     }
@@ -1535,15 +1459,6 @@ int flat_bwd_vol_launch(const MarchArgs &a, BrickParams<VT> P, dim3 grid1, bool 
 }
 template int flat_bwd_vol_launch<float>(const MarchArgs &, BrickParams<float>, dim3, bool, hipStream_t);
 template int flat_bwd_vol_launch<__half>(const MarchArgs &, BrickParams<__half>, dim3, bool, hipStream_t);
-// Host view of B1's LDS d_tf table at resolution R (tests/test_bwd_dtf_table.py; not part of the public header): add_slot[4 k + q] =
-// the element the sample loop adds component q of texel k to, flush_slot[g] = the element the flush hands to entry g of the
-// caller's [texel][4] order; returns the number of elements the zeroing walks.
-extern "C" int dr_b1_dtf_table_map(int R, int *add_slot, int *flush_slot) {
-    for (int k = 0; k < R; ++k)
-        for (int q = 0; q < 4; ++q) add_slot[4 * k + q] = dtf_slot<DTF_CM_B1>(R, k, 0) + q * (DTF_CM_B1 ? R : 1);
-    for (int g = 0; g < 4 * R; ++g) flush_slot[g] = dtf_slot_of<DTF_CM_B1>(R, g);
-    return 4 * R;
-}
 #else
 
 template <typename VT>

@@ -12,7 +12,7 @@
 // Reference functions replaced: get_final_image[_nondiff] (VR.py:353-372) and the early-termination test of
 // raycast / raycast_nondiff (VR.py:267,318).
 #include "dr_brick_common.h"
-#include "dr_wave.h"
+#include "dr_dtf.h"
 #include "dr_tuning.h"
 
 namespace dr {
@@ -726,13 +726,7 @@ __global__ __launch_bounds__(EXACT_BWD_NT) void ray_exact_bwd_kernel(BrickParams
             }
             if (want_vol) {   // uniform
                 const int lane = (int)(threadIdx.x & 63);
-                const int prev = wave_up1(cell_key, cell_key);
-                const bool start = lane == 0 || cell_key != prev;
-                const unsigned long long starts = __ballot(start);
-                const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-                const int rs = 63 - __clzll((long long)(starts & upto));   // first lane of this lane's run of samples in one cell
-                seg_scan_sum<8>(acc, lane, rs);
-                const bool run_end = lane == 63 || ((starts >> ((lane + 1) & 63)) & 1ull);
+                const bool run_end = lane_run_sums<8>(cell_key, lane, 0, acc);   // runs of samples in one cell
                 if (cell_key >= 0 && run_end) {
                     unsafeAtomicAdd(cb00 + co0, acc[0]); unsafeAtomicAdd(cb10 + co0, acc[1]); unsafeAtomicAdd(cb01 + co0, acc[2]); unsafeAtomicAdd(cb11 + co0, acc[3]);
                     unsafeAtomicAdd(cb00 + co1, acc[4]); unsafeAtomicAdd(cb10 + co1, acc[5]); unsafeAtomicAdd(cb01 + co1, acc[6]); unsafeAtomicAdd(cb11 + co1, acc[7]);
@@ -741,13 +735,7 @@ __global__ __launch_bounds__(EXACT_BWD_NT) void ray_exact_bwd_kernel(BrickParams
             if (want_tf) {   // uniform
                 // lanes are consecutive samples: runs of them share a TF cell -- summed across the lanes (DPP), one set of LDS adds per run
                 const int lane = (int)(threadIdx.x & 63);
-                const int prev = wave_up1(key, key);
-                const bool start = lane == 0 || key != prev;
-                const unsigned long long starts = __ballot(start);
-                const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-                const int rs = 63 - __clzll((long long)(starts & upto));   // first lane of this lane's run
-                seg_scan_sum<8>(V8, lane, rs);
-                const bool run_end = lane == 63 || ((starts >> ((lane + 1) & 63)) & 1ull);
+                const bool run_end = lane_run_sums<8>(key, lane, 0, V8);
                 if (key >= 0 && run_end) {
                     unsigned long long *d0 = lds_dtf + 4 * key, *d1 = lds_dtf + 4 * key_hi;
 #pragma unroll

@@ -15,7 +15,7 @@
 // march_baseline.hip) serves them, as after every fast backward -- and all rays, if the workspace does not hold this call's tape.
 // Replaces, for d_tf: raycast.grad + get_final_image.grad (VR.py:460-461,470-471).
 #include "dr_brick_common.h"
-#include "dr_wave.h"
+#include "dr_dtf.h"
 #include "dr_tuning.h"
 
 namespace dr {
@@ -32,24 +32,6 @@ struct TapeRay {
     int R, tf_len;
     float inv_sr;
 };
-
-// adds a finished run's sums tq = (w0 L op T, w1 L op T, w0 a_bar, w1 a_bar) to the texels lo / hi
-__device__ __forceinline__ void tape_emit(const TapeRay &r, bool em, const float (&tq)[4], int lo, int hi) {
-    const float4 go = r.go;
-    const float v8[8] = {tq[0] * go.x, tq[0] * go.y, tq[0] * go.z, tq[2], tq[1] * go.x, tq[1] * go.y, tq[1] * go.z, tq[3]};
-    const float vmax = ((fabsf(v8[0]) + fabsf(v8[1])) + (fabsf(v8[2]) + fabsf(v8[3]))) +
-                       ((fabsf(v8[4]) + fabsf(v8[5])) + (fabsf(v8[6]) + fabsf(v8[7])));
-    unsigned long long *d0 = r.lds_dtf + 4 * lo, *d1 = r.lds_dtf + 4 * hi;
-    if (__any(em && !(vmax <= ACC_LIM))) {   // a NaN or an absurd run total: the sanitising path
-        if (em) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q, acc_sanitise(v8[q])); acc_add_f64(d1 + q, acc_sanitise(v8[4 + q])); }
-        }
-    } else if (em) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { acc_add_f64(d0 + q, v8[q]); acc_add_f64(d1 + q, v8[4 + q]); }
-    }
-}
 
 // One pass of a wave over 64 * K consecutive samples of its ray, K per lane, from sample `base`; `carry` is the composite of the
 // samples before the pass as (gC . C, A) and leaves as the composite including them. What is paid once per pass -- the scan of the
@@ -87,18 +69,14 @@ __device__ __forceinline__ void tape_pass(const TapeRay &r, const int base, cons
         el2 = (j == 0) ? ej : over2(el2, ej);   // over2(x, 0) == x exactly
     }
     // inclusive wave scan of the lanes' composites (one segment: the ray), then the carry from the passes before
-    Over2 inc2 = seg_scan_over2(el2, lane, 0), exc2;
-    exc2.w = wave_up1(inc2.w, 0.f); exc2.a = wave_up1(inc2.a, 0.f);
-    if (lane == 0) { exc2.w = 0.f; exc2.a = 0.f; }
-    inc2 = over2(carry, inc2); exc2 = over2(carry, exc2);
-    carry.w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc2.w), 63));
-    carry.a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc2.a), 63));
+    Over2 inc2;
+    const Over2 exc2 = scan_over2_carried(el2, lane, 0, true, 0, 0, carry, inc2);
     // Adjoints of the lane's samples, front to back (tape-free identity, as sample_adjoint of dr_device.h), gathered into RUNS of
     // consecutive samples between the same two texels: run sums are added to d_tf once. A lane's samples form up to K runs: the
     // first continues the run of the lane before (if that ended in the same TF cell), the last is carried on to the next lane
     // (summed across lanes by DPP below); a lane whose samples fall into different TF cells ("split") closes the incoming run
     // with its first group -- and a group strictly inside a lane (K = 4: three cells within four samples) is added where it ends.
-    // (the scheme of the brick-centric TF-only backward, march_flat.hip)
+    // (the scheme of the brick-centric TF-only backward, march_flat.hip; dr_dtf.h: dtf_split_runs)
     const bool v0 = s0 < r.live;
     int key_in = v0 ? klo[0] : -1 - lane, hi_in = khi[0];
     int key_out = key_in, hi_out = hi_in;
@@ -132,7 +110,7 @@ __device__ __forceinline__ void tape_pass(const TapeRay &r, const int base, cons
                         for (int q = 0; q < 4; ++q) Hd[q] = V[q];
                         split = true;
                     } else if (K > 2) {
-                        tape_emit(r, true, V, key_out, hi_out);   // (among the lanes that are here)
+                        dtf_run_add(r.lds_dtf, key_out, hi_out, true, V, go);   // (among the lanes that are here)
                     }
 #pragma unroll
                     for (int q = 0; q < 4; ++q) V[q] = t[q];
@@ -144,16 +122,9 @@ __device__ __forceinline__ void tape_pass(const TapeRay &r, const int base, cons
     const int prev_out = wave_up1(key_out, key_out);
     const bool contl = lane != 0 && key_in == prev_out;   // continues the run of the lane before
     const bool start = !contl || split;                   // the lane's outgoing value starts a run
-    const unsigned long long starts = __ballot(start);
-    const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-    const int rs = 63 - __clzll((long long)(starts & upto));   // first lane of this lane's outgoing run
-    seg_scan_sum<4>(V, lane, rs);
-    const unsigned long long contm = __ballot(contl);
-    const bool run_end = lane == 63 || !((contm >> ((lane + 1) & 63)) & 1ull);
-    tape_emit(r, v0 && run_end, V, key_out, hi_out);
-    if (__any(split)) {   // uniform
-        // (the DPP moves are pinned in front of the select: `contl ? dpp : 0` otherwise becomes an exec-masked region around
-        //  the v_mov_dpp, and a DPP move whose SOURCE lane is masked off writes nothing -- march_flat.hip, round 3)
+    const bool run_end = dtf_split_runs(lane, contl, start, V);
+    dtf_run_add(r.lds_dtf, key_out, hi_out, v0 && run_end, V, go);
+    if (__any(split)) {   // uniform; the DPP moves are pinned in front of the select (dr_dtf.h: dtf_split_runs)
         float Pv[4], H[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) Pv[q] = wave_up1(V[q], 0.f);   // inclusive sum of the previous lane's outgoing run
@@ -161,7 +132,7 @@ __device__ __forceinline__ void tape_pass(const TapeRay &r, const int base, cons
         for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(Pv[q]));
 #pragma unroll
         for (int q = 0; q < 4; ++q) H[q] = (contl ? Pv[q] : 0.0f) + Hd[q];
-        tape_emit(r, split, H, key_in, hi_in);
+        dtf_run_add(r.lds_dtf, key_in, hi_in, split, H, go);
     }
 }
 

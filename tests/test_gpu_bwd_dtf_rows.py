@@ -1,8 +1,8 @@
-"""The d_tf adds of the brick backward's main kernel (B1, csrc/march_flat.hip; DR_BWD_DTF_ROWS and DR_BWD_DTF_DIRECT_MIN,
-csrc/dr_tuning.h). As shipped (DR_BWD_DTF_ROWS = 0) every pass sums each run of samples between the same two texels across lanes
-and adds from the run's last lane into a [texel][4] LDS table. Built with DR_BWD_DTF_ROWS = 1 (measured slower,
-profiles/dtfrows_ab.txt; kept as a tuning switch) a 64-sample pass that holds at least DR_BWD_DTF_DIRECT_MIN runs moves each
-sample's d_tf inputs to lane 16 r + c <- 4 c + r and every lane adds its own eight products into a component-major table
+"""The d_tf adds of the brick backward's main kernel (B1, csrc/march_flat.hip). Every pass sums each run of samples between the
+same two texels across lanes and adds from the run's last lane into a [texel][4] LDS table. The other build these cases were
+written for is a closed experiment (DR_BWD_DTF_ROWS and DR_BWD_DTF_DIRECT_MIN of tools/patches/closed_experiments.patch; measured
+slower, profiles/dtfrows_ab.txt, tools/README.md): there a 64-sample pass that holds at least DR_BWD_DTF_DIRECT_MIN runs moves
+each sample's d_tf inputs to lane 16 r + c <- 4 c + r and every lane adds its own eight products into a component-major table
 (dtf_rows_add), a pass of fewer, longer runs keeps the run sums. The cases hold for either build, and passed with both. They
 are the smallest scenes that send passes down either way and through the edges of the exchange: runs of one sample, monotone
 runs of two, one texel from samples far apart, one run per segment, pass run counts right at the threshold, the smallest and
@@ -19,7 +19,7 @@ from test_gpu_bwd_row_scatter import BIG, Scene, T, check, randn_g, rule, Fn  # 
 
 pytestmark = pytest.mark.gpu
 
-DIRECT_MIN = 8   # DR_BWD_DTF_DIRECT_MIN (csrc/dr_tuning.h)
+DIRECT_MIN = 8   # DR_BWD_DTF_DIRECT_MIN of the patched build (tools/patches/closed_experiments.patch); the shipped kernel has no threshold
 BRK = 12         # cells per brick edge (csrc/dr_brick.h)
 R256 = 256
 
