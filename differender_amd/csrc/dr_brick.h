@@ -58,6 +58,10 @@ __device__ __forceinline__ void axis_coord(float pos, float sc, int &cell, float
     fr = __builtin_amdgcn_fractf(q);
     cell = (int)q;
 }
+// ... its fraction alone: what a +-delta tap needs where delta stays below half a voxel (dr_brick_common.h, "tap-cell flags")
+__device__ __forceinline__ float axis_frac(float pos, float sc) {
+    return __builtin_amdgcn_fractf(fminf(1.0f, fmaxf(0.0f, fmaf(0.5f, pos, 0.5f))) * sc);
+}
 
 // brick coordinate of the camera along one axis (unclamped linear map, may be negative or >= NB)
 __device__ __forceinline__ int cam_brick(float cam, float sc) {

@@ -5,6 +5,7 @@
 #include "dr_brick.h"
 #include "dr_kernels.h"
 #include "dr_tile.h"
+#include "dr_tuning.h"
 #include "../../include/differender_hip.h"
 #include <string.h>
 
@@ -482,9 +483,32 @@ __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t
 struct TapCoords {
     int lx, ly, lz;       // local (box) cell of the centre tap
     float fx, fy, fz;
-    int lxp, lxm, lyp, lym, lzp, lzm;  // local cells of the +-delta taps along each axis
+    int lxp, lxm, lyp, lym, lzp, lzm;  // local cells of the +-delta taps along each axis (wide taps only: the NARROW kernels do not form them)
     float fxp, fxm, fyp, fym, fzp, fzm;
 };
+
+// ---- Tap-cell flags from fractions (NARROW) -----------------------------------------------------------------------------------
+// All that the brick kernels ask of a +-delta tap's cell is whether it IS the centre's. Where delta' = delta * sc / 2 stays below
+// half a voxel (NARROW: every edge up to 991 voxels, taps_narrow in march_flat.hip) the fractions answer that, and the taps' cells
+// are never formed -- no float-to-int conversion, no subtraction of the brick's origin, nothing to keep alive or to pack for the
+// transposed scatter. axis_coord is monotone in its position and the fraction of a non-negative q is exact, so with
+// q- <= q <= q+ and q+ - q, q - q- < 1:
+//     cell(p + delta) == cell(p)  <=>  fr(p + delta) >= fr(p)      (a tap in the next cell has fr+ = fr + delta' - 1 < fr)
+//     cell(p - delta) == cell(p)  <=>  fr(p - delta) <= fr(p)      (equality: both positions clamp to the volume's face)
+// tools/tapflag_proof.c checks both, and |cell(p +- delta) - cell(p)| <= 1, on every float position in [-1 - 2 delta, 1 + 2 delta]
+// at the edges 2, 3, 13, 14, 25, 96, 256, 512, 990, 991: no counter-example (profiles/tapflags_proof.txt); they first fail at an
+// edge of 2001, where delta' reaches a whole voxel. The wide-tap kernels (edges 992 .. 2000) keep the integer cells, their
+// assembly unchanged. Measured (profiles/tapflags_ab.txt, same device, alternating runs): headline step 8.536 -> 8.347 ms
+// (-2.21 %), F1 2141.8 -> 2068.7 us, B1 6190.0 -> 5983.0 us; valu_lane_instr_per_voxel_step F1 433.4 -> 419.6, B1 1047.1 -> 1003.6;
+// B1's main kernels 126 -> 120 / 119 -> 113 VGPRs; the forward's K = 4 and tape kernels lose their 8 B of scratch.
+// Has the +delta / -delta tap of an axis LEFT the centre's cell? (l0, f0: the centre's cell and fraction; FRAC: the cells are not read)
+template <bool FRAC>
+__device__ __forceinline__ bool tap_left_up(int l0, int lp, float f0, float fp) { return FRAC ? !(fp >= f0) : (lp != l0); }
+template <bool FRAC>
+__device__ __forceinline__ bool tap_left_dn(int l0, int lm, float f0, float fm) { return FRAC ? !(fm <= f0) : (lm != l0); }
+// which instantiations take them there (DR_TAP_FRAC_FLAGS, dr_tuning.h: 0 rebuilds the integer cells everywhere, to re-measure)
+template <bool NARROW>
+struct TapFlags { static constexpr bool FRAC = NARROW && DR_TAP_FRAC_FLAGS != 0; };
 
 // Centre tap and the six normal taps from the LDS box, in two halves (the normal taps are skipped when no lane needs the
 // lighting term). Until round 4 these were seven independent tri_lds() calls -- 56 LDS words and 49 lerps per sample; the
@@ -518,13 +542,14 @@ __device__ __forceinline__ void sample_normal_taps_shared_lds(const float *box, 
                                                               float &dx, float &dy, float &dz) {
     // every address is the centre's plus a per-lane constant: the taps sit in the centre's cell or in the one next to it
     // (delta < 1 voxel), so a select + an add replaces the multiply-add chain per tap
+    constexpr bool FRAC = TapFlags<NARROW>::FRAC;
     const int base = t.lx * BOX_SX + t.ly * BOX_SY + t.lz;
     {   // x: two whole taps (their first lerp has its own fraction: nothing of the centre's is reusable but the voxels)
-        const int ip = base + ((t.lxp != t.lx) ? BOX_SX : 0), im = base - ((t.lxm != t.lx) ? BOX_SX : 0);
+        const int ip = base + (tap_left_up<FRAC>(t.lx, t.lxp, t.fx, t.fxp) ? BOX_SX : 0), im = base - (tap_left_dn<FRAC>(t.lx, t.lxm, t.fx, t.fxm) ? BOX_SX : 0);
         dx = tri_lds(box, ip, t.fxp, t.fy, t.fz) - tri_lds(box, im, t.fxm, t.fy, t.fz);
     }
     {   // y: the x-lerps of row ly+2 (for a +delta tap in the cell above) and of row ly-1 (a -delta tap in the cell below)
-        const bool up = t.lyp != t.ly, dn = t.lym != t.ly;
+        const bool up = tap_left_up<FRAC>(t.ly, t.lyp, t.fy, t.fyp), dn = tap_left_dn<FRAC>(t.ly, t.lym, t.fy, t.fym);
         const int ru = base + (NARROW ? (up ? 2 * BOX_SY : -BOX_SY) : 2 * BOX_SY);
         const float u0 = mixf(box[ru], box[ru + BOX_SX], t.fx);
         const float u1 = mixf(box[ru + 1], box[ru + BOX_SX + 1], t.fx);
@@ -539,7 +564,7 @@ __device__ __forceinline__ void sample_normal_taps_shared_lds(const float *box, 
         dy = p - m;
     }
     {   // z: the bilinear planes lz+2 and lz-1
-        const bool up = t.lzp != t.lz, dn = t.lzm != t.lz;
+        const bool up = tap_left_up<FRAC>(t.lz, t.lzp, t.fz, t.fzp), dn = tap_left_dn<FRAC>(t.lz, t.lzm, t.fz, t.fzm);
         const int pu = base + (NARROW ? (up ? 2 : -1) : 2);
         const float zu = mixf(mixf(box[pu], box[pu + BOX_SX], t.fx), mixf(box[pu + BOX_SY], box[pu + BOX_SX + BOX_SY], t.fx), t.fy);
         float zd = zu;
@@ -565,9 +590,16 @@ __device__ __forceinline__ bool sample_centre_coords_at(const VolView<VT> &vol, 
     // the brick's cells are box elements 1 .. BRK along each axis (element 0 is the voxel below the brick)
     return (unsigned)(t.lx - 1) < (unsigned)BRK && (unsigned)(t.ly - 1) < (unsigned)BRK && (unsigned)(t.lz - 1) < (unsigned)BRK;
 }
-template <typename VT>
+template <bool NARROW, typename VT>
 __device__ __forceinline__ void sample_normal_coords_at(const VolView<VT> &vol, const BrickCtx &c, const Sample &sm, TapCoords &t) {
     const float delta = 1e-3f;
+    if (TapFlags<NARROW>::FRAC) {   // fractions only: they carry the "same cell as the centre" flags (tap_left_up / tap_left_dn); the cells are not formed
+        t.fxp = axis_frac(sm.px + delta, vol.scx); t.fxm = axis_frac(sm.px - delta, vol.scx);
+        t.fyp = axis_frac(sm.py + delta, vol.scy); t.fym = axis_frac(sm.py - delta, vol.scy);
+        t.fzp = axis_frac(sm.pz + delta, vol.scz); t.fzm = axis_frac(sm.pz - delta, vol.scz);
+        t.lxp = t.lxm = t.lyp = t.lym = t.lzp = t.lzm = 0;   // (never read)
+        return;
+    }
     int k;
     axis_coord(sm.px + delta, vol.scx, k, t.fxp); t.lxp = k - c.ox;
     axis_coord(sm.px - delta, vol.scx, k, t.fxm); t.lxm = k - c.ox;
@@ -576,10 +608,10 @@ __device__ __forceinline__ void sample_normal_coords_at(const VolView<VT> &vol, 
     axis_coord(sm.pz + delta, vol.scz, k, t.fzp); t.lzp = k - c.oz;
     axis_coord(sm.pz - delta, vol.scz, k, t.fzm); t.lzm = k - c.oz;
 }
-template <typename VT>
+template <bool NARROW, typename VT>
 __device__ __forceinline__ bool sample_coords_at(const VolView<VT> &vol, const BrickCtx &c, Sample &sm, TapCoords &t) {
     if (!sample_centre_coords_at(vol, c, sm, t)) return false;
-    sample_normal_coords_at(vol, c, sm, t);
+    sample_normal_coords_at<NARROW>(vol, c, sm, t);
     return true;
 }
 

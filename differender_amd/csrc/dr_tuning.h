@@ -36,6 +36,14 @@
 #ifndef DR_BWD_ROW_SCATTER
 #define DR_BWD_ROW_SCATTER 1
 #endif
+// NARROW brick kernels (edges up to 991): whether a +-delta tap sits in the centre's cell is read from the FRACTIONS (fr+ >= fr,
+// fr- <= fr: dr_brick_common.h, "tap-cell flags"); the taps' cells are not formed, kept or packed for the transposed scatter.
+// 0: integer cells as in the wide-tap kernels. Headline step 8.536 -> 8.347 ms (-2.21 %, four alternating runs per build, 4.4 x the
+// larger spread), backward 6.253 -> 6.108 ms, forward 2.211 -> 2.168 ms; d_volume only -1.6 %, tf1 -1.0 %, CT-like -0.7 %, camera
+// inside -1.2 %, f16 + jitter -1.9 %, 8 views at 256^3 -2.3 % (profiles/tapflags_ab.txt)
+#ifndef DR_TAP_FRAC_FLAGS
+#define DR_TAP_FRAC_FLAGS 1
+#endif
 // brick-centric backward w.r.t. the TF only (no gradient box, 33 KB of LDS): FOUR-wave workgroups, four per CU -- 3.22 ms against
 // 3.80 with the 8-wave shape at 512^3 (profiles/r03_ab_experiments.txt); 96 VGPRs for a fifth workgroup spill 132 B per lane: 4.08 ms
 #ifndef DR_FNT_BWDTF

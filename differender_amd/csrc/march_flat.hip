@@ -471,8 +471,10 @@ __device__ __forceinline__ void scatter4(PT *dst, ST SA, ST SB, float c, const f
 // Adjoint of the two central-difference taps of one axis, reduced to coefficients along that axis over the box
 // planes l0-1 .. l0+2 (l0 = centre cell). The +delta tap sits in cell l0 or l0+1, the -delta tap in l0-1 or l0
 // (delta < 1 voxel, brick_path_supported); a tap in cell l spreads (1-f, f) over planes l, l+1. Times g.
-__device__ __forceinline__ void tap_line(int l0, int lp, int lm, float fp, float fm, float g, float (&cf)[4]) {
-    const bool in_p = lp == l0, in_m = lm == l0;
+// FRAC: whether a tap sits in the centre's cell is read from the fractions (f0: the centre's; dr_brick_common.h), not the cells.
+template <bool FRAC>
+__device__ __forceinline__ void tap_line(int l0, int lp, int lm, float f0, float fp, float fm, float g, float (&cf)[4]) {
+    const bool in_p = FRAC ? (fp >= f0) : (lp == l0), in_m = FRAC ? (fm <= f0) : (lm == l0);
     const float gp = 1.0f - fp, gm = 1.0f - fm;
     cf[0] = in_m ? 0.0f : -gm * g;
     cf[1] = ((in_p ? gp : 0.0f) - (in_m ? gm : fm)) * g;
@@ -486,8 +488,9 @@ __device__ __forceinline__ void tap_line(int l0, int lp, int lm, float fp, float
 // lands there is summed into the centre's 8 corners first (8 LDS adds); what remains per axis is one outside
 // plane of 4 voxels (l0+2 or l0-1; both only when delta >= 0.5 voxel, i.e. dim > 1000: rare uniform branch).
 // 8 + 3*4 = 20 LDS adds per sample instead of 8 per tap. NARROW (delta < 0.5 voxel: +delta past l0+1 AND -delta below l0 would
-// take 2 delta > 1) compiles the three "both planes" tests out.
-template <int ACC, bool NARROW, typename PT, typename ST>
+// take 2 delta > 1) compiles the three "both planes" tests out. FRAC: the taps' "in the centre's cell" flags come from the fractions
+// (the NARROW kernels, dr_brick_common.h: "tap-cell flags"), t's neighbour cells are not read.
+template <int ACC, bool NARROW, bool FRAC, typename PT, typename ST>
 __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, const TapCoords &t, bool valid,
                                                float I_bar, const float (&gq)[3], const FixScale &fs) {
     const float X[2] = {1.0f - t.fx, t.fx}, Y[2] = {1.0f - t.fy, t.fy}, Z[2] = {1.0f - t.fz, t.fz};
@@ -495,9 +498,9 @@ __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, con
     const float XZ[4] = {X[0] * Z[0], X[1] * Z[0], X[0] * Z[1], X[1] * Z[1]};  // offsets {0, SX, SZ, SX+SZ}
     const float XY[4] = {X[0] * Y[0], X[1] * Y[0], X[0] * Y[1], X[1] * Y[1]};  // offsets {0, SX, SY, SX+SY}
     float cx[4], cy[4], cz[4];
-    tap_line(t.lx, t.lxp, t.lxm, t.fxp, t.fxm, gq[0], cx);
-    tap_line(t.ly, t.lyp, t.lym, t.fyp, t.fym, gq[1], cy);
-    tap_line(t.lz, t.lzp, t.lzm, t.fzp, t.fzm, gq[2], cz);
+    tap_line<FRAC>(t.lx, t.lxp, t.lxm, t.fx, t.fxp, t.fxm, gq[0], cx);
+    tap_line<FRAC>(t.ly, t.lyp, t.lym, t.fy, t.fyp, t.fym, gq[1], cy);
+    tap_line<FRAC>(t.lz, t.lzp, t.lzm, t.fz, t.fzp, t.fzm, gq[2], cz);
     const float ax[2] = {fmaf(I_bar, X[0], cx[1]), fmaf(I_bar, X[1], cx[2])};
     float acc[8];
 #pragma unroll
@@ -527,19 +530,20 @@ __device__ __forceinline__ void scatter_sample(PT *dst, ST SX, ST SY, ST SZ, con
     if (valid) scatter8<ACC>(dst, SX, SY, SZ, acc, fs);
 }
 // the common destination: the brick's LDS gradient box, centre cell at element cbase_i
-template <int ACC, bool NARROW>
+template <int ACC, bool NARROW, bool FRAC>
 __device__ __forceinline__ void scatter_sample(unsigned long long *dbox, const TapCoords &t, bool valid, int cbase_i,
                                                float I_bar, const float (&gq)[3], const FixScale &fs) {
-    scatter_sample<ACC, NARROW>(dbox + cbase_i, (int)BOX_SX, (int)BOX_SY, 1, t, valid, I_bar, gq, fs);
+    scatter_sample<ACC, NARROW, FRAC>(dbox + cbase_i, (int)BOX_SX, (int)BOX_SY, 1, t, valid, I_bar, gq, fs);
 }
 // ... from the ROW-TRANSPOSED lane layout (DR_BWD_ROW_SCATTER, dr_tuning.h). The pass computes in lane order -- the tap reads keep
 // their broadcasts, the scans their neighbours -- and only here, in front of the scatter, lane 16 r + c takes over the sample of
 // lane 4 c + r: what scatter_sample consumes travels through the LDS crossbar in 14 ds_bpermute_b32 -- one word with the centre
-// cell, the six "tap stays in the centre's cell" flags and the validity, the nine fractions, the four adjoints. Integer adds
+// cell and the validity (for the wide taps also the six "tap left the centre's cell" flags; under FRAC the destination lane forms
+// them from the fractions it receives anyway: nothing to pack or unpack), the nine fractions, the four adjoints. Integer adds
 // commute (ACC_FIX: the box ends bit-identical; the pass's scale is wave-uniform) and ACC_F64 only changes the order of its
 // double adds. Must be called with all 64 lanes enabled (a lane without a sample, or past the end of the wave's samples,
 // passes valid = false and arrives as such).
-template <int ACC, bool NARROW>
+template <int ACC, bool NARROW, bool FRAC>
 __device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, const TapCoords &t, bool valid, int cbase_i, int lane,
                                                     float I_bar, const float (&gq)[3], const FixScale &fs) {
 #if DR_BWD_ROW_SCATTER
@@ -547,9 +551,10 @@ __device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, co
     // (the cell is formed again here, not taken from cbase_i: its select would only be undone, and the main kernels need one
     // register less this way; the validity rides in the word's sign bit: a select here and a compare there, against a 64-bit shift of the ballot
     // by the source lane)
-    const int w_own = (t.lx * BOX_SX + t.ly * BOX_SY + t.lz) | ((int)(t.lxp != t.lx) << 12) | ((int)(t.lxm != t.lx) << 13) |
+    const int w_own = FRAC ? ((t.lx * BOX_SX + t.ly * BOX_SY + t.lz) | (int)0x80000000u) :
+                      ((t.lx * BOX_SX + t.ly * BOX_SY + t.lz) | ((int)(t.lxp != t.lx) << 12) | ((int)(t.lxm != t.lx) << 13) |
                       ((int)(t.lyp != t.ly) << 14) | ((int)(t.lym != t.ly) << 15) | ((int)(t.lzp != t.lz) << 16) |
-                      ((int)(t.lzm != t.lz) << 17) | (int)0x80000000u;
+                      ((int)(t.lzm != t.lz) << 17) | (int)0x80000000u);
     // (the source lane's address is made here, per pass: hoisted out of the sample loops it would be one more register to
     // keep alive across shading and the adjoint, where the kernel has none to spare)
     int l = lane;
@@ -565,12 +570,12 @@ __device__ __forceinline__ void scatter_sample_rows(unsigned long long *dbox, co
     u.fzp = row_transpose(t.fzp, a); u.fzm = row_transpose(t.fzm, a);
     // tap_line only asks whether a tap's cell IS the centre's: cells relative to the centre's
     u.lx = u.ly = u.lz = 0;
-    u.lxp = (w >> 12) & 1; u.lxm = -((w >> 13) & 1);
-    u.lyp = (w >> 14) & 1; u.lym = -((w >> 15) & 1);
-    u.lzp = (w >> 16) & 1; u.lzm = -((w >> 17) & 1);
-    scatter_sample<ACC, NARROW>(dbox, u, w < 0, w & 0xfff, I2, g2, fs);
+    u.lxp = FRAC ? 0 : (w >> 12) & 1; u.lxm = FRAC ? 0 : -((w >> 13) & 1);
+    u.lyp = FRAC ? 0 : (w >> 14) & 1; u.lym = FRAC ? 0 : -((w >> 15) & 1);
+    u.lzp = FRAC ? 0 : (w >> 16) & 1; u.lzm = FRAC ? 0 : -((w >> 17) & 1);
+    scatter_sample<ACC, NARROW, FRAC>(dbox, u, w < 0, w & 0xfff, I2, g2, fs);
 #else
-    scatter_sample<ACC, NARROW>(dbox, t, valid, cbase_i, I_bar, gq, fs);
+    scatter_sample<ACC, NARROW, FRAC>(dbox, t, valid, cbase_i, I_bar, gq, fs);
 #endif
 }
 
@@ -635,6 +640,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
     // scatter_sample without its three "both outside planes" tests, where delta < 0.5 voxel rules them out. (The d_volume-only
     // main kernel keeps them: without, the register-minimising scheduler leaves it 118 VGPRs and 36 B of scratch per lane.)
     constexpr bool ONE_OUTSIDE = NARROW && WANT_TF;
+    constexpr bool FRAC_FLAGS = TapFlags<NARROW>::FRAC;   // the scatter's tap-cell flags come from the fractions (dr_brick_common.h)
     const int nbricks = P.g.NBx * P.g.NBy * P.g.NBz;
     int *live_flag = &const_cast<BrickCtxRec *>(P.ctx)[(size_t)view * nbricks + slot].live;   // "this brick holds live samples of the view"
     const bool count_stats = (slot & 63) == 0;   // diagnostics counters (ST_UNLIT_SKIPPED, ST_EMPTY_BRICKS) are SAMPLED: one workgroup in 64
@@ -953,7 +959,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     bool vj = false;
                     if (actj) {
                         sample_pos_rcp(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, cam.x, cam.y, cam.z, s + j, sm.px, sm.py, sm.pz);
-                        vj = sample_coords_at(vol, c, sm, t);
+                        vj = sample_coords_at<NARROW>(vol, c, sm, t);
                     }
                     Over2 ej = {0.f, 0.f};
                     n_eval += (unsigned int)__popcll(__ballot(vj));
@@ -1051,7 +1057,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
             if (KS == 1) {
                 if (act) {
                     sample_pos_rcp(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, cam.x, cam.y, cam.z, s, sm.px, sm.py, sm.pz);
-                    valid = BWD ? sample_coords_at(vol, c, sm, t) : sample_centre_coords_at(vol, c, sm, t);
+                    valid = BWD ? sample_coords_at<NARROW>(vol, c, sm, t) : sample_centre_coords_at(vol, c, sm, t);
                 }
                 if (valid) {
                     sm.I = sample_centre_lds_keep(L.box, t, cl);
@@ -1060,7 +1066,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                 const bool lit = !ALPHA && valid && (BWD || (MODE == DR_MODE_NONDIFF ? (sm.a > 1e-3f) : (sm.op != 0.0f)));
                 if (BWD || __any(lit)) {
                     if (lit) {
-                        if (!BWD) sample_normal_coords_at(vol, c, sm, t);
+                        if (!BWD) sample_normal_coords_at<NARROW>(vol, c, sm, t);
                         sample_normal_taps_shared_lds<NARROW>(L.box, t, cl, dx, dy, dz);
                         shade_from_grad<true>(dx, dy, dz, light, vd, MODE == DR_MODE_DIFF, sm);
                     }
@@ -1108,7 +1114,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                     if (__any(lit)) {
                         if (lit) {
                             if (MODE == DR_MODE_NONDIFF) sm.op = opacity_of_alpha(sm.a, P.inv_sr);  // (a power: only where lit)
-                            sample_normal_coords_at(vol, c, sm, t);  // (not before: transparent stretches never need them)
+                            sample_normal_coords_at<NARROW>(vol, c, sm, t);  // (not before: transparent stretches never need them)
                             sample_normal_taps_shared_lds<NARROW>(L.box, t, cl, dx, dy, dz);
                             shade_from_grad<true>(dx, dy, dz, light, vd, MODE == DR_MODE_DIFF, sm);
                             ej.c0 = sm.L * sm.r * sm.op; ej.c1 = sm.L * sm.g * sm.op; ej.c2 = sm.L * sm.b * sm.op; ej.a = sm.op;
@@ -1260,7 +1266,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                             I_bar = acc_sanitise(I_bar);
                             gq[0] = acc_sanitise(gq[0]); gq[1] = acc_sanitise(gq[1]); gq[2] = acc_sanitise(gq[2]);
                         }
-                        scatter_sample_rows<ACC_F64, ONE_OUTSIDE>(L.dbox, t, valid, cbase_i, lane, I_bar, gq, fs);
+                        scatter_sample_rows<ACC_F64, ONE_OUTSIDE, FRAC_FLAGS>(L.dbox, t, valid, cbase_i, lane, I_bar, gq, fs);
                     } else {
                         // Beyond the range of the fixed-point box (2^12 x the brick's largest upstream gradient: the
                         // normalisation of a nearly vanishing volume gradient amplifies by 1/|grad|, 1e7 and more where
@@ -1275,7 +1281,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                                 const GradView dv = P.dvol;
                                 float *gdst = dv.p + ((long long)view * P.dvol_vs + (long long)(c.ox + t.lx) * dv.sx +
                                                       (long long)(c.oy + t.ly) * dv.sy + (long long)(c.oz + t.lz) * dv.sz);
-                                scatter_sample<ACC_GLOBAL, ONE_OUTSIDE>(gdst, (long long)dv.sx, (long long)dv.sy, (long long)dv.sz, t, over, I_bar, gq, fs);
+                                scatter_sample<ACC_GLOBAL, ONE_OUTSIDE, FRAC_FLAGS>(gdst, (long long)dv.sx, (long long)dv.sy, (long long)dv.sz, t, over, I_bar, gq, fs);
                             }
                             in_box = valid && !over;
                             I_bar = fix_clamp(I_bar, fs);
@@ -1290,7 +1296,7 @@ __device__ __forceinline__ void brick_flat_body(const BrickParams<VT> &P, unsign
                             FixScale fw = fs;
                             const float mul = fix_wave_scale(wmax, fw);
                             const float gs[3] = {gq[0] * mul, gq[1] * mul, gq[2] * mul};
-                            scatter_sample_rows<ACC_FIX, ONE_OUTSIDE>(L.dbox, t, in_box, cbase_i, lane, I_bar * mul, gs, fw);
+                            scatter_sample_rows<ACC_FIX, ONE_OUTSIDE, FRAC_FLAGS>(L.dbox, t, in_box, cbase_i, lane, I_bar * mul, gs, fw);
                         }
                     }
                 }
