@@ -272,7 +272,7 @@ int dr_march_bwd_rows_pose(const void *vol, int vol_dtype, int VX, int VY, int V
                                                         : brick_workspace_bytes(n_views, W, H, VX, VY, VZ))) return DR_EINVAL;
         return launch_march_bwd_flat(a, (hipStream_t)stream);
     }
-    return launch_march_bwd_baseline(a, (hipStream_t)stream);
+    return launch_march_bwd_baseline(a, RayFilter{}, (hipStream_t)stream);
 }
 
 int dr_march_bwd_rows(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,

@@ -8,6 +8,7 @@
 #include "dr_tuning.h"
 #include "../../include/differender_hip.h"
 #include <string.h>
+#include <type_traits>
 
 namespace dr {
 
@@ -46,8 +47,16 @@ struct BrickParams {
                          //   committed to the caller's float tensor by dtf_commit_kernel, which leaves it zero again (the forward zeroes it too).
                          //   80 000 per-brick partials met in float atomics before: 1e-4 of d_tf's maximum where a texel collects 1e8
                          //   cancelling terms (the air's texels under a random upstream gradient: tools/diff_sweep.py, round 6)
+    // ---- What differs from launch to launch of one call. The host builds ONE BrickParams per call (make_brick_params) and its
+    // dispatch (flat_fwd_dispatch / flat_bwd_dispatch, march_flat.hip) advances these fields through the pass sequence; every other
+    // field is the same for all launches of the call. Who reads them:
+    //   tape         F1 with TAPE, tf_tape_bwd_kernel; brick_ctx_kernel (null or not: does the header announce a tape?)
+    //   tape_stride  those three, ray_compose_kernel (F2), ray_exact_bwd_kernel (B3), dtf_commit_kernel
+    //   lm_words     the brick passes of march_flat.hip (F1, its alpha flavour, B1), brick_ctx_kernel
+    //   use_live     F1, ray_compose_kernel
+    //   pp_*         the alpha flavour of F1, ray_alpha_kernel
     float2 *tape;        // DR_TAPE_TF: [view][NP][tape_stride] (intensity, lighting term) of every marched sample (forward -> tf_tape.hip)
-    int tape_stride;     //   samples reserved per ray (0: no tape)
+    int tape_stride;     //   samples reserved per ray (0: no tape); set once per call, see call_tape_stride
     unsigned long long *unlit;  // [view][lm_words][NP]: non-differentiable renders with an alpha pre-pass -- bit l of a ray's mask: the pre-pass
     int lm_words;               //   marched the ray's segment of layer l and found NO sample with alpha > 1e-3 (the colour march
                                 //   skips it: its count and its zero partial are already in place). 0: feature off (NL > 128).
@@ -60,9 +69,9 @@ struct BrickParams {
                          // the backward trusts records, live flags, ray flags and work items only if it finds it there
     int nondiff;         // forward: non-differentiable march (a sample composites only if alpha > 1e-3, VR.py:334; differentiable: if alpha != 0)
     int hint_noterm;     // forward: the caller said no ray can terminate early and the pre-pass was not launched; F2 checks
-    int use_live;        // forward: ws_steps holds each ray's exact live sample count (from the alpha pre-pass)
+    int use_live;        // forward, from the colour march on: ws_steps holds each ray's exact live sample count (the alpha pre-pass ran)
     int count_eval;      // DR_COUNT_EVALUATED: the brick kernels add their evaluated samples to stats[ST_EVAL_*] (measurement only)
-    int pp_l0, pp_l1, pp_first;  // alpha pre-pass phase: brick layers [pp_l0, pp_l1); later phases skip terminated rays
+    int pp_l0, pp_l1, pp_first;  // alpha pre-pass phase: brick layers [pp_l0, pp_l1); later phases (pp_first = 0) skip terminated rays
     const struct BrickCtxRec *ctx;  // [view][brick]: brick geometry + pixel rectangle, filled once per forward call
     BrickItem *items;               // overflow work items of heavy bricks
     unsigned int *n_items;          // ... and how many there are
@@ -774,10 +783,19 @@ static inline size_t ws_layout(void *base, int n_views, int NP, const BrickGrid 
     return o;
 }
 
+// Samples per ray of the DR_TAPE_TF tape of this call, 0: none -- THE rule for BrickParams::tape / tape_stride and for the layout of
+// the workspace. A forward leaves a tape iff DR_TAPE_TF is set and the march is the differentiable one; a backward call carries
+// the stride iff DR_TAPE_TF is set: it is then the TF-only backward over the tape (capi.hip refuses DR_TAPE_TF together with d_vol and
+// returns early when no gradient is wanted), whose kernels check the stride against what the forward announced (ST_TAPE_STRIDE).
+static inline int call_tape_stride(const MarchArgs &a, bool backward) {
+    const bool tape = (a.hints & DR_TAPE_TF) && (backward || a.mode == DR_MODE_DIFF);
+    return tape ? tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S) : 0;
+}
 
-
+// The one BrickParams of a call: g its brick grid, w = ws_layout(.., g, .., tape_stride) with the stride of call_tape_stride. The per-launch fields (see BrickParams)
+// start at "no masks, no live counts, no pre-pass phase".
 template <typename VT>
-static inline BrickParams<VT> make_brick_params(const MarchArgs &a, const Workspace &w) {
+static inline BrickParams<VT> make_brick_params(const MarchArgs &a, const BrickGrid &g, const Workspace &w, int tape_stride) {
     BrickParams<VT> P;
     P.vol = make_vol_view<VT>(a); P.vol_vs = a.vol_vs;
     P.tf = reinterpret_cast<const float4 *>(a.tf); P.tf_vs = a.tf_vs / 4; P.R = a.R; P.tf_len = (float)(a.R - 1);
@@ -787,15 +805,15 @@ static inline BrickParams<VT> make_brick_params(const MarchArgs &a, const Worksp
     const double near_h = 2.0 * tan(a.fov_rad) * a.near_plane;
     P.near_ = (float)a.near_plane; P.near_h = (float)near_h; P.near_w = (float)(near_h * ((double)P.imgW / (double)a.H));
     P.pose = a.pose; P.fov_v = a.fov_v; P.near_d = a.near_plane; P.aspect = (double)P.imgW / (double)a.H;
-    P.g = make_brick_grid(a.VX, a.VY, a.VZ);
+    P.g = g;
 
-    P.seg_rgba = w.seg_rgba; P.seg_cnt = w.seg_cnt; P.rayflag = w.rayflag; P.stats = w.stats; P.vflags = w.vflags; P.n_views = a.n_views; P.ws_steps = w.ws_steps; P.fin = w.fin; P.exact_list = w.exact_list; P.seg_tiny = w.seg_tiny; P.dtf64 = w.dtf64; P.tape = nullptr; P.tape_stride = 0; P.unlit = w.unlit; P.lm_words = 0;
+    P.seg_rgba = w.seg_rgba; P.seg_cnt = w.seg_cnt; P.rayflag = w.rayflag; P.stats = w.stats; P.vflags = w.vflags; P.n_views = a.n_views; P.ws_steps = w.ws_steps; P.fin = w.fin; P.exact_list = w.exact_list; P.seg_tiny = w.seg_tiny; P.dtf64 = w.dtf64; P.tape = w.tape; P.tape_stride = tape_stride; P.unlit = w.unlit; P.lm_words = 0;
     P.hint_noterm = (a.hints & DR_HINT_NO_EARLY_TERMINATION) ? 1 : 0;
     P.count_eval = (a.hints & DR_COUNT_EVALUATED) ? 1 : 0;
     P.nondiff = a.mode == DR_MODE_NONDIFF ? 1 : 0;
-    P.use_live = a.use_live; P.ctx = w.ctx; P.items = w.items; P.n_items = w.n_items;
+    P.use_live = 0; P.ctx = w.ctx; P.items = w.items; P.n_items = w.n_items;
     P.mark = ws_fingerprint(a);
-    P.pp_l0 = a.pp_l0; P.pp_l1 = a.pp_l1; P.pp_first = a.pp_first;
+    P.pp_l0 = 0; P.pp_l1 = 0; P.pp_first = 0;
     P.out = a.out; P.steps = a.steps;
     P.grad_out = a.grad_out; P.out_fwd = a.out_fwd;
     P.dvol.p = a.d_vol; P.dvol.sx = a.dsx; P.dvol.sy = a.dsy; P.dvol.sz = a.dsz; P.dvol_vs = a.dvol_vs;
@@ -811,5 +829,25 @@ static inline hipError_t allow_lds(K kernel, size_t bytes) {
     return allow_lds_impl(reinterpret_cast<const void *>(kernel), bytes);
 }
 
+// A run-time choice as a template argument: f is a generic lambda, called with a std::integral_constant -- `decltype(flag)::value`
+// inside it is a constant expression. Both calls must return the same type.
+template <typename F>
+static inline auto with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// ... the march's mode, from BrickParams::nondiff: DR_MODE_DIFF or DR_MODE_NONDIFF
+template <typename F>
+static inline auto with_mode(int nondiff, F &&f) {
+    return !nondiff ? f(std::integral_constant<int, DR_MODE_DIFF>{}) : f(std::integral_constant<int, DR_MODE_NONDIFF>{});
+}
+
+// The per-ray passes of a call (march_flat.hip's dispatch strings them together with its own per-brick passes). Each takes the
+// call's BrickParams as the dispatch has advanced it and returns a hipError_t or DR_E* code; instantiated for float and __half
+// where the kernels live.
+// alpha pre-pass (ray_passes.hip): the per-ray composition of one phase, or (cross) the exact termination sample of the crossing rays
+template <typename VT> int launch_ray_alpha(const BrickParams<VT> &P, bool cross, hipStream_t stream);
+template <typename VT> int launch_ray_compose(const BrickParams<VT> &P, hipStream_t stream);    // F2: the workspace must hold the F1 output of the same call
+template <typename VT> int launch_ray_exact(const BrickParams<VT> &P, hipStream_t stream);      // F3: the rays F2 listed, sample by sample
+template <typename VT> int launch_ray_exact_bwd(const BrickParams<VT> &P, hipStream_t stream);  // B3: the backward of the rays F3 recomputed
+template <typename VT> int launch_tf_tape_bwd(const BrickParams<VT> &P, hipStream_t stream);    // TF-only backward over the per-sample tape (tf_tape.hip)
+template <typename VT> int launch_dtf_commit(const BrickParams<VT> &P, hipStream_t stream);     // the backward's double d_tf table -> the caller's float tensor (tf_tape.hip)
 
 }  // namespace dr

@@ -6,7 +6,7 @@
 
 namespace dr {
 
-// Everything a march launch needs; filled by capi.cpp from the C-ABI arguments.
+// Everything a march launch needs; filled by capi.hip from the C-ABI arguments.
 struct MarchArgs {
     const void *vol; int vol_dtype; int VX, VY, VZ; int64_t sx, sy, sz, vol_vs;
     const float *tf; int R; int64_t tf_vs;
@@ -22,14 +22,7 @@ struct MarchArgs {
     // brick path
     double fov_rad, near_plane;
     void *workspace; size_t workspace_bytes;
-    const uint8_t *only_flagged;  // baseline backward: restrict to rays with a non-zero flag (may be null)
-    const unsigned int *ws_mark;  // ... unless *ws_mark != ws_mark_expect (the workspace is not this call's forward's: the
-    unsigned int ws_mark_expect;  //     flags are garbage, every ray is marched); may be null
-    const unsigned int *ws_aux;   // ... or *ws_aux != ws_aux_expect (the TF-only backward over the tape: the forward left no tape of
-    unsigned int ws_aux_expect;   //     this stride); may be null
     int hints;                    // DR_HINT_* bits of the forward call
-    int use_live;                 // forward: per-ray live sample counts are available (alpha pre-pass)
-    int pp_l0, pp_l1, pp_first;   // alpha pre-pass phase: brick layers [pp_l0, pp_l1); pp_first: no earlier phase
     // free camera; null: the fixed one (look at the origin, up = +y, the scalar fov_rad)
     const float *pose;            // [n_views][9] look_from, look_at, up; look_from equals cam
     const float *fov_v;           // [n_views] fov in radians, nullable: fov_rad for every view
@@ -42,7 +35,15 @@ hipError_t launch_ray_setup(const float *cam, const float *pose, const float *fo
 
 // Plain one-lane-per-ray kernels (DR_VARIANT_BASELINE): direct global gathers, global float atomics.
 int launch_march_fwd_baseline(const MarchArgs &a, hipStream_t stream);
-int launch_march_bwd_baseline(const MarchArgs &a, hipStream_t stream);
+// The brick path's second backward pass (B2) runs the plain backward over the rays its forward flagged only; an empty filter: every ray.
+struct RayFilter {
+    const uint8_t *only_flagged = nullptr;   // [view][W][H]: march the rays whose flag is 1 ...
+    const unsigned int *ws_mark = nullptr;   // ... unless *ws_mark != ws_mark_expect (the workspace is not this call's forward's: the
+    unsigned int ws_mark_expect = 0;         //     flags are garbage, every ray is marched); may be null
+    const unsigned int *ws_aux = nullptr;    // ... or *ws_aux != ws_aux_expect (the TF-only backward over the tape: the forward left no
+    unsigned int ws_aux_expect = 0;          //     tape of this stride); may be null
+};
+int launch_march_bwd_baseline(const MarchArgs &a, const RayFilter &f, hipStream_t stream);
 
 // Brick-centric kernels (DR_VARIANT_AUTO): LDS-staged bricks, per-(ray,layer) partial composites.
 bool brick_path_supported(int VX, int VY, int VZ, int R);
@@ -50,13 +51,6 @@ bool brick_image_supported(int W, int H, int VX, int VY, int VZ);  // [layer][pi
 size_t brick_workspace_bytes(int n_views, int W, int H, int VX, int VY, int VZ);
 int tape_stride_for(int VX, int VY, int VZ, float sr, int max_samples);   // samples per ray the DR_TAPE_TF tape reserves
 size_t brick_workspace_bytes_tape(int n_views, int W, int H, int VX, int VY, int VZ, int max_samples, float sr);
-int launch_tf_tape_bwd(const MarchArgs &a, hipStream_t stream);     // TF-only backward over the per-sample tape (tf_tape.hip)
-int launch_ray_compose(const MarchArgs &a, hipStream_t stream);      // F2
-int launch_ray_exact(const MarchArgs &a, hipStream_t stream);        // F3: the rays F2 listed, sample by sample
-int launch_ray_exact_bwd(const MarchArgs &a, hipStream_t stream);   // B3: the backward of the rays F3 recomputed
-int launch_dtf_commit(const MarchArgs &a, hipStream_t stream);      // the backward's double d_tf table -> the caller's float tensor
-int launch_ray_alpha(const MarchArgs &a, hipStream_t stream);        // alpha pre-pass: per-ray composition of one phase
-int launch_ray_cross(const MarchArgs &a, hipStream_t stream);        // alpha pre-pass: exact termination sample of crossing rays
 bool flat_strides_ok(int64_t sx, int64_t sy, int64_t sz);  // 32-bit in-box offsets
 // Word of the workspace header that says whose coarse tape the workspace holds (a fingerprint of the forward call that
 // filled it, see ws_fingerprint); a forward served by the baseline kernels clears it (flat_invalidate_workspace).

@@ -15,7 +15,7 @@ namespace dr {
 template <typename VT>
 struct MarchParams : RayParams<VT> {
     const uint8_t *only_flagged;
-    const unsigned int *ws_mark; unsigned int ws_mark_expect;  // see MarchArgs
+    const unsigned int *ws_mark; unsigned int ws_mark_expect;  // see RayFilter
     const unsigned int *ws_aux; unsigned int ws_aux_expect;
 };
 
@@ -124,11 +124,11 @@ __global__ __launch_bounds__(256) void march_bwd_baseline_kernel(MarchParams<VT>
 }
 
 template <typename VT>
-static MarchParams<VT> make_params(const MarchArgs &a) {
+static MarchParams<VT> make_params(const MarchArgs &a, const RayFilter &f = RayFilter{}) {
     MarchParams<VT> P{make_ray_params<VT>(a)};
-    P.only_flagged = a.only_flagged;
-    P.ws_mark = a.ws_mark; P.ws_mark_expect = a.ws_mark_expect;
-    P.ws_aux = a.ws_aux; P.ws_aux_expect = a.ws_aux_expect;
+    P.only_flagged = f.only_flagged;
+    P.ws_mark = f.ws_mark; P.ws_mark_expect = f.ws_mark_expect;
+    P.ws_aux = f.ws_aux; P.ws_aux_expect = f.ws_aux_expect;
     return P;
 }
 
@@ -149,16 +149,16 @@ int launch_march_fwd_baseline(const MarchArgs &a, hipStream_t stream) {
 }
 
 template <typename VT>
-static int bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
+static int bwd_dispatch(const MarchArgs &a, const RayFilter &f, hipStream_t stream) {
     // TF + its double-precision gradient table in LDS while they fit (R <= 3392), then the TF alone (R <= 10176), then nothing
     const TableTier t = table_tier(a.R, true);
-    const MarchParams<VT> P = make_params<VT>(a);
+    const MarchParams<VT> P = make_params<VT>(a, f);
     return launch_tiles(t.tables == 2 ? march_bwd_baseline_kernel<VT, 2> : (t.tables == 1 ? march_bwd_baseline_kernel<VT, 1> : march_bwd_baseline_kernel<VT, 0>),
                         a, t.lds, stream, P);
 }
 
-int launch_march_bwd_baseline(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? bwd_dispatch<__half>(a, stream) : bwd_dispatch<float>(a, stream);
+int launch_march_bwd_baseline(const MarchArgs &a, const RayFilter &f, hipStream_t stream) {
+    return a.vol_dtype == DR_F16 ? bwd_dispatch<__half>(a, f, stream) : bwd_dispatch<float>(a, f, stream);
 }
 
 }  // namespace dr

@@ -1429,42 +1429,47 @@ bool brick_path_supported(int VX, int VY, int VZ, int R) {
 
 #endif  // !DR_FLAT_TU_BWDVOL
 
-static inline bool taps_narrow(const MarchArgs &a) {
-    const int m = a.VX > a.VY ? (a.VX > a.VZ ? a.VX : a.VZ) : (a.VY > a.VZ ? a.VY : a.VZ);
+// NARROW (delta below half a voxel: every edge <= 991 voxels) selects the cheaper shared-lerp taps (dr_brick_common.h); the alpha
+// pre-pass takes no normal taps and exists in one flavour, NARROW = true
+template <typename VT>
+static inline bool taps_narrow(const BrickParams<VT> &P) {
+    const int m = P.vol.VX > P.vol.VY ? (P.vol.VX > P.vol.VZ ? P.vol.VX : P.vol.VZ) : (P.vol.VY > P.vol.VZ ? P.vol.VY : P.vol.VZ);
     return m - 1 <= 990;   // delta = 1e-3 world units = 1e-3 * (m - 1) / 2 voxels <= 0.495
 }
-// one pass over the bricks: the main launch (one workgroup per brick and view) + the overflow items of heavy bricks
-#define DR_LAUNCH_BOTH_N(MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NT_, NARROW_)                                                             \
-    {                                                                                                                                 \
-        if ((e = allow_lds(brick_flat_kernel<VT, MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NARROW_>, lds)) != hipSuccess) return (int)e;    \
-        if ((e = allow_lds(brick_flat_items_kernel<VT, MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NARROW_>, align16(lds) + ITEM_EXTRA_LDS)) != hipSuccess) return (int)e; \
-        hipLaunchKernelGGL((brick_flat_kernel<VT, MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NARROW_>), grid1, dim3(NT_), lds, stream, P);         \
-        hipLaunchKernelGGL((brick_flat_items_kernel<VT, MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NARROW_>), dim3(BWD_ ? (VOL_ ? ITEM_GRID_BWD : 2 * ITEM_GRID_BWD) : ITEM_GRID_FWD), dim3(NT_), align16(lds) + ITEM_EXTRA_LDS, stream, P); \
-    }
-// NARROW (delta below half a voxel: every edge <= 991 voxels) selects the cheaper shared-lerp taps (dr_brick_common.h); the alpha
-// pre-pass takes no normal taps and exists in one flavour
-#define DR_LAUNCH_BOTH(MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NT_)                                                                       \
-    {                                                                                                                                 \
-        if ((ALPHA_) || taps_narrow(a)) DR_LAUNCH_BOTH_N(MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NT_, true)                              \
-        else DR_LAUNCH_BOTH_N(MODE_, BWD_, VOL_, TF_, ALPHA_, K_, NT_, false)                                                         \
-    }
+// One pass over the bricks: the main launch (one workgroup per brick and view) + the overflow items of heavy bricks. Every kernel
+// flavour the library holds is one instantiation of this template, made where the pass is launched below -- a ladder that is generic
+// over a parameter adds a kernel per value.
+template <typename VT, int MODE, bool BWD, bool WANT_VOL, bool WANT_TF, int ALPHA, int KF, bool NARROW, bool TAPE>
+static hipError_t launch_brick_pass(const BrickParams<VT> &P, dim3 grid1, size_t lds, hipStream_t stream) {
+    const auto k_main = brick_flat_kernel<VT, MODE, BWD, WANT_VOL, WANT_TF, ALPHA, KF, NARROW, TAPE>;
+    const auto k_items = brick_flat_items_kernel<VT, MODE, BWD, WANT_VOL, WANT_TF, ALPHA, KF, NARROW, TAPE>;
+    const dim3 nt(FlatCfg<BWD, WANT_VOL, ALPHA>::FNT);
+    const size_t lds_items = align16(lds) + ITEM_EXTRA_LDS;
+    hipError_t e;
+    if ((e = allow_lds(k_main, lds)) != hipSuccess) return e;
+    if ((e = allow_lds(k_items, lds_items)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_main, grid1, nt, lds, stream, P);
+    hipLaunchKernelGGL(k_items, dim3(BWD ? (WANT_VOL ? ITEM_GRID_BWD : 2 * ITEM_GRID_BWD) : ITEM_GRID_FWD), nt, lds_items, stream, P);
+    return hipGetLastError();
+}
 
 // B1 (the backward with a gradient box), launched from its own translation unit
 template <typename VT>
-int flat_bwd_vol_launch(const MarchArgs &a, BrickParams<VT> P, dim3 grid1, bool want_tf, hipStream_t stream);
+int flat_bwd_vol_launch(const BrickParams<VT> &P, dim3 grid1, bool want_tf, hipStream_t stream);
 
 #ifdef DR_FLAT_TU_BWDVOL
 template <typename VT>
-int flat_bwd_vol_launch(const MarchArgs &a, BrickParams<VT> P, dim3 grid1, bool want_tf, hipStream_t stream) {
-    hipError_t e = hipSuccess;
+int flat_bwd_vol_launch(const BrickParams<VT> &P, dim3 grid1, bool want_tf, hipStream_t stream) {
     // (the LDS size is this translation unit's own: tuning / what-if switches may be given to it alone, tools/mkvariant.sh BWDVOL_EXTRA)
-    const size_t lds = flat_lds_bytes<true>(a.R, true, want_tf);
-    if (want_tf) DR_LAUNCH_BOTH(DR_MODE_DIFF, true, true, true, false, 1, (FlatCfg<true, true>::FNT))
-    else DR_LAUNCH_BOTH(DR_MODE_DIFF, true, true, false, false, 1, (FlatCfg<true, true>::FNT))
-    return (int)hipGetLastError();
+    const size_t lds = flat_lds_bytes<true>(P.R, true, want_tf);
+    return (int)with_flag(want_tf, [&](auto tf) {
+        return with_flag(taps_narrow(P), [&](auto narrow) {
+            return launch_brick_pass<VT, DR_MODE_DIFF, true, true, decltype(tf)::value, 0, 1, decltype(narrow)::value, false>(P, grid1, lds, stream);
+        });
+    });
 }
-template int flat_bwd_vol_launch<float>(const MarchArgs &, BrickParams<float>, dim3, bool, hipStream_t);
-template int flat_bwd_vol_launch<__half>(const MarchArgs &, BrickParams<__half>, dim3, bool, hipStream_t);
+template int flat_bwd_vol_launch<float>(const BrickParams<float> &, dim3, bool, hipStream_t);
+template int flat_bwd_vol_launch<__half>(const BrickParams<__half> &, dim3, bool, hipStream_t);
 #else
 
 template <typename VT>
@@ -1473,12 +1478,12 @@ static int flat_fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     const int NP = a.W * a.H;
     Workspace w;
     // DR_TAPE_TF: a per-sample tape of (intensity, lighting) for the TF-only backward (tf_tape.hip) behind the ordinary workspace
-    const bool tape = (a.hints & DR_TAPE_TF) && a.mode == DR_MODE_DIFF;
-    const int tstride = tape ? tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S) : 0;
+    const int tstride = call_tape_stride(a, false);
+    const bool tape = tstride > 0;
     const size_t need = ws_layout(a.workspace, a.n_views, NP, g, &w, tstride);
     if (!a.workspace || a.workspace_bytes < need) return DR_EINVAL;
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    P.tape = w.tape; P.tape_stride = tstride;
+    // the call's one BrickParams: advanced through the passes below (lm_words, pp_*, use_live) and handed to each of them
+    BrickParams<VT> P = make_brick_params<VT>(a, g, w, tstride);
     hipError_t e;
     // Non-differentiable render with an alpha pre-pass: the pre-pass tells the colour march which (ray, layer) segments hold no
     // sample with alpha > 1e-3 ("unlit" masks behind seg_cnt, BrickParams::unlit); such segments keep the pre-pass's count and
@@ -1510,7 +1515,6 @@ static int flat_fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     // Samples per lane: the cross-lane scan and the chunk bookkeeping are paid once per K*64 samples, but lanes K
     // samples apart share fewer LDS words (more read cycles, more bank conflicts). Measured at 512^3: K = 2 wins up
     // at sampling rate 1 (-3 %), K = 4 from 2 on (-13 % at 2, -16 % at 4 and 8 vs K = 1: samples are closer together); K = 8 loses.
-#define DR_LAUNCH_F1(MODE_, K_) DR_LAUNCH_BOTH(MODE_, false, false, false, false, K_, (FlatCfg<false, false>::FNT))
     const bool k_hi = a.sr >= 1.75f;
     if (prepass) {
         // The pre-pass runs front to back in G groups of brick layers; after each group the rays that have reached
@@ -1519,27 +1523,22 @@ static int flat_fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
         // 11.0 instead of 15.0 ms (8 views, 256^3). Each extra group costs the non-terminating case two empty
         // launches (~10 us: +0.7 % on the 512^3 headline at G = 2 for -2.5 % with tf1), so below sampling rate 3: G = 1.
         const int G = a.sr >= 3.0f ? DR_PP_GROUPS : ((a.hints & DR_HINT_EARLY_TERMINATION) ? DR_PP_GROUPS_LO : 1);
-        MarchArgs pa = a;
         const bool alpha_hi = a.sr >= 3.0f;   // six workgroups per CU (FlatCfg<.., 2>)
-        // (shadows the colour march's `lds` on purpose: the launch macros read that name)
-        const size_t lds = flat_lds_bytes<false>(a.R, false, false, alpha_hi ? 2 : 1);   // the pre-pass's own table size
+        const size_t lds_pp = flat_lds_bytes<false>(a.R, false, false, alpha_hi ? 2 : 1);   // the pre-pass's own table size
         for (int gi = 0; gi < G; ++gi) {
-            pa.pp_l0 = g.NL * gi / G; pa.pp_l1 = g.NL * (gi + 1) / G; pa.pp_first = gi == 0;
-            P.pp_l0 = pa.pp_l0; P.pp_l1 = pa.pp_l1; P.pp_first = pa.pp_first;
+            P.pp_l0 = g.NL * gi / G; P.pp_l1 = g.NL * (gi + 1) / G; P.pp_first = gi == 0;
             // (several bricks per workgroup would quarter the cost of this launch when it is gated off -- 27 us of workgroup
             // exits at 512^3 -- but the looped kernel needs 96 VGPRs instead of 66 and is 3-5 % slower when it runs)
-            if (a.mode == DR_MODE_DIFF) {
-                if (alpha_hi) DR_LAUNCH_BOTH(DR_MODE_DIFF, false, false, false, 2, DR_ALPHA_K, (FlatCfg<false, false, 2>::FNT))
-                else DR_LAUNCH_BOTH(DR_MODE_DIFF, false, false, false, 1, DR_ALPHA_K, (FlatCfg<false, false, 1>::FNT))
-            } else {
-                if (alpha_hi) DR_LAUNCH_BOTH(DR_MODE_NONDIFF, false, false, false, 2, DR_ALPHA_K, (FlatCfg<false, false, 2>::FNT))
-                else DR_LAUNCH_BOTH(DR_MODE_NONDIFF, false, false, false, 1, DR_ALPHA_K, (FlatCfg<false, false, 1>::FNT))
-            }
-            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-            const int rc = launch_ray_alpha(pa, stream);
+            e = with_mode(P.nondiff, [&](auto mode) {
+                return with_flag(alpha_hi, [&](auto hi) {
+                    return launch_brick_pass<VT, decltype(mode)::value, false, false, false, decltype(hi)::value ? 2 : 1, DR_ALPHA_K, true, false>(P, grid1, lds_pp, stream);
+                });
+            });
+            if (e != hipSuccess) return (int)e;
+            const int rc = launch_ray_alpha(P, false, stream);
             if (rc) return rc;
         }
-        const int rc2 = launch_ray_cross(a, stream);
+        const int rc2 = launch_ray_alpha(P, true, stream);
         if (rc2) return rc2;
         const size_t n16 = (w.cnt_bytes + 15) / 16;  // (seg_cnt is 16-byte aligned and padded)
         // With the unlit masks the counts stay: the colour march overwrites the count of every segment it marches; what it does
@@ -1549,29 +1548,21 @@ static int flat_fwd_dispatch(const MarchArgs &a, hipStream_t stream) {
         hipLaunchKernelGGL(clear_counts_if_prepass_kernel, dim3((unsigned)((n16 + 255) / 256 < 4096 ? (n16 + 255) / 256 : 4096)), dim3(256), 0,
                            stream, reinterpret_cast<uint4 *>(w.seg_cnt), n16, w.vflags, a.n_views);
     }
-    MarchArgs b = a;
-    b.use_live = prepass ? 1 : 0;
-    P.use_live = b.use_live;
-    if (tape) {
-        // the same march with TAPE = true: main launch + work items, both tap flavours
-#define DR_LAUNCH_F1_TAPE(K_, NARROW_)                                                                                                   \
-        {                                                                                                                                \
-            if ((e = allow_lds(brick_flat_kernel<VT, DR_MODE_DIFF, false, false, false, 0, K_, NARROW_, true>, lds)) != hipSuccess) return (int)e;   \
-            if ((e = allow_lds(brick_flat_items_kernel<VT, DR_MODE_DIFF, false, false, false, 0, K_, NARROW_, true>, align16(lds) + ITEM_EXTRA_LDS)) != hipSuccess) return (int)e; \
-            hipLaunchKernelGGL((brick_flat_kernel<VT, DR_MODE_DIFF, false, false, false, 0, K_, NARROW_, true>), grid1, dim3(FlatCfg<false, false>::FNT), lds, stream, P); \
-            hipLaunchKernelGGL((brick_flat_items_kernel<VT, DR_MODE_DIFF, false, false, false, 0, K_, NARROW_, true>), dim3(ITEM_GRID_FWD), dim3(FlatCfg<false, false>::FNT), align16(lds) + ITEM_EXTRA_LDS, stream, P); \
-        }
-        const bool narrow = taps_narrow(a);
-        if (k_hi) { if (narrow) DR_LAUNCH_F1_TAPE(DR_FWD_K_HI, true) else DR_LAUNCH_F1_TAPE(DR_FWD_K_HI, false) }
-        else { if (narrow) DR_LAUNCH_F1_TAPE(DR_FWD_K, true) else DR_LAUNCH_F1_TAPE(DR_FWD_K, false) }
-#undef DR_LAUNCH_F1_TAPE
-    } else if (a.mode == DR_MODE_DIFF) { if (k_hi) DR_LAUNCH_F1(DR_MODE_DIFF, DR_FWD_K_HI) else DR_LAUNCH_F1(DR_MODE_DIFF, DR_FWD_K) }
-    else { if (k_hi) DR_LAUNCH_F1(DR_MODE_NONDIFF, DR_FWD_K_HI) else DR_LAUNCH_F1(DR_MODE_NONDIFF, DR_FWD_K) }
-#undef DR_LAUNCH_F1
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const int rc3 = launch_ray_compose(b, stream);
+    P.use_live = prepass ? 1 : 0;
+    // F1, the colour march: both tap flavours and both K of the plain march in either mode, and of the march that leaves the tape
+    e = with_flag(taps_narrow(P), [&](auto narrow) {
+        return with_flag(k_hi, [&](auto hi) {
+            constexpr bool N = decltype(narrow)::value;
+            constexpr int K = decltype(hi)::value ? DR_FWD_K_HI : DR_FWD_K;
+            if (tape) return launch_brick_pass<VT, DR_MODE_DIFF, false, false, false, 0, K, N, true>(P, grid1, lds, stream);
+            if (P.nondiff) return launch_brick_pass<VT, DR_MODE_NONDIFF, false, false, false, 0, K, N, false>(P, grid1, lds, stream);
+            return launch_brick_pass<VT, DR_MODE_DIFF, false, false, false, 0, K, N, false>(P, grid1, lds, stream);
+        });
+    });
+    if (e != hipSuccess) return (int)e;
+    const int rc3 = launch_ray_compose(P, stream);
     if (rc3) return rc3;
-    return launch_ray_exact(b, stream);
+    return launch_ray_exact(P, stream);
 }
 
 hipError_t flat_invalidate_workspace(void *workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -1586,48 +1577,38 @@ int launch_march_fwd_flat(const MarchArgs &a, hipStream_t stream) {
 template <typename VT>
 static int flat_bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
     const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    const int NP = a.W * a.H;
     Workspace w;
     const bool wv = a.d_vol != nullptr, wt = a.d_tf != nullptr;
-    // DR_TAPE_TF: the TF-only backward as a per-ray pass over the forward's per-sample tape (tf_tape.hip), B2 for the flagged rays --
-    // or for all of them, should the workspace turn out not to hold this call's tape (checked on the device)
-    if ((a.hints & DR_TAPE_TF) && !wv && wt) {
-        const int tstride = tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S);
-        const size_t need_t = ws_layout(a.workspace, a.n_views, NP, g, &w, tstride);
-        if (!a.workspace || a.workspace_bytes < need_t) return DR_EINVAL;
-        const int rc = launch_tf_tape_bwd(a, stream);
-        if (rc) return rc;
-        MarchArgs b = a;
-        b.only_flagged = w.rayflag;
-        b.ws_mark = w.stats + ST_MARK; b.ws_mark_expect = ws_fingerprint(a);
-        b.ws_aux = w.stats + ST_TAPE_STRIDE; b.ws_aux_expect = (unsigned int)tstride;
-        const int rc2 = launch_march_bwd_baseline(b, stream);
-        if (rc2) return rc2;
-        const int rc3 = launch_ray_exact_bwd(a, stream);   // B3: the rays the forward recomputed sequentially
-        if (rc3) return rc3;
-        return launch_dtf_commit(a, stream);
-    }
-    const size_t need = ws_layout(a.workspace, a.n_views, NP, g, &w);
+    const int tstride = call_tape_stride(a, true);
+    const size_t need = ws_layout(a.workspace, a.n_views, a.W * a.H, g, &w, tstride);
     if (!a.workspace || a.workspace_bytes < need) return DR_EINVAL;
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    P.lm_words = (wv && !wt && DR_UNLIT_SKIP > 1) ? w.lm_words : 0;   // the d_volume-only backward may skip unlit segments (if the forward left masks)
-    const size_t lds = flat_lds_bytes<true>(a.R, wv, wt);
-    const dim3 grid1(g.NBx * g.NBy * g.NBz, a.n_views);
-    hipError_t e = hipSuccess;
+    BrickParams<VT> P = make_brick_params<VT>(a, g, w, tstride);
     // (the brick records, live flags and work items are the forward's: same inputs, same workspace)
-    if (wv) {   // B1: march_flat_bwdvol.o
-        const int rc = flat_bwd_vol_launch<VT>(a, P, grid1, wt, stream);
+    // B2, after the brick pass or the tape pass: the irregular rays through the baseline backward -- every ray, if the workspace turns
+    // out not to hold this call's forward (or, over the tape, no tape of this stride): checked on the device
+    RayFilter b2;
+    b2.only_flagged = w.rayflag;
+    b2.ws_mark = w.stats + ST_MARK; b2.ws_mark_expect = P.mark;
+    if (tstride > 0) {
+        // DR_TAPE_TF: the TF-only backward as a per-ray pass over the forward's per-sample tape (tf_tape.hip)
+        b2.ws_aux = w.stats + ST_TAPE_STRIDE; b2.ws_aux_expect = (unsigned int)tstride;
+        const int rc = launch_tf_tape_bwd(P, stream);
         if (rc) return rc;
-    } else DR_LAUNCH_BOTH(DR_MODE_DIFF, true, false, true, false, 1, (FlatCfg<true, false>::FNT))
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    MarchArgs b = a;
-    b.only_flagged = w.rayflag;  // B2: irregular rays through the baseline backward (every ray, if the workspace is not this call's)
-    b.ws_mark = w.stats + ST_MARK; b.ws_mark_expect = P.mark;
-    const int rc2 = launch_march_bwd_baseline(b, stream);
+    } else {
+        P.lm_words = (wv && !wt && DR_UNLIT_SKIP > 1) ? w.lm_words : 0;   // the d_volume-only backward may skip unlit segments (if the forward left masks)
+        const dim3 grid1(g.NBx * g.NBy * g.NBz, a.n_views);
+        int rc;
+        if (wv) rc = flat_bwd_vol_launch<VT>(P, grid1, wt, stream);   // B1: march_flat_bwdvol.o
+        else rc = (int)with_flag(taps_narrow(P), [&](auto narrow) {
+            return launch_brick_pass<VT, DR_MODE_DIFF, true, false, true, 0, 1, decltype(narrow)::value, false>(P, grid1, flat_lds_bytes<true>(a.R, false, true), stream);
+        });
+        if (rc) return rc;
+    }
+    const int rc2 = launch_march_bwd_baseline(a, b2, stream);
     if (rc2) return rc2;
-    const int rc3 = launch_ray_exact_bwd(a, stream);   // B3: the rays the forward recomputed sequentially
+    const int rc3 = launch_ray_exact_bwd(P, stream);   // B3: the rays the forward recomputed sequentially
     if (rc3 || !wt) return rc3;
-    return launch_dtf_commit(a, stream);
+    return launch_dtf_commit(P, stream);
 }
 
 int launch_march_bwd_flat(const MarchArgs &a, hipStream_t stream) {

@@ -770,101 +770,71 @@ size_t brick_workspace_bytes_tape(int n_views, int W, int H, int VX, int VY, int
 }
 
 // F2: the workspace must hold the F1 output of the same call.
+// (a forward that leaves a per-sample tape: F2 reads its stride, to keep rays longer than that off the tape path)
 template <typename VT>
-static int ray_compose_dispatch(const MarchArgs &a, hipStream_t stream) {
-    const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    const int NP = a.W * a.H;
-    Workspace w;
-    ws_layout(a.workspace, a.n_views, NP, g, &w);
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    // (a forward that leaves a per-sample tape: F2 needs its stride, to keep rays longer than that off the tape path)
-    if ((a.hints & DR_TAPE_TF) && a.mode == DR_MODE_DIFF) P.tape_stride = tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S);
-    const dim3 grid2((NP + 255) / 256, a.n_views);
-    const size_t lds2 = (size_t)a.R * 16;
-    if (a.mode == DR_MODE_DIFF)
-        hipLaunchKernelGGL((ray_compose_kernel<VT, DR_MODE_DIFF>), grid2, dim3(256), lds2, stream, P);
-    else
-        hipLaunchKernelGGL((ray_compose_kernel<VT, DR_MODE_NONDIFF>), grid2, dim3(256), lds2, stream, P);
+int launch_ray_compose(const BrickParams<VT> &P, hipStream_t stream) {
+    const dim3 grid2((P.W * P.H + 255) / 256, P.n_views);
+    const size_t lds2 = (size_t)P.R * 16;
+    with_mode(P.nondiff, [&](auto mode) {
+        hipLaunchKernelGGL((ray_compose_kernel<VT, decltype(mode)::value>), grid2, dim3(256), lds2, stream, P);
+    });
     return (int)hipGetLastError();
 }
 
-int launch_ray_compose(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? ray_compose_dispatch<__half>(a, stream) : ray_compose_dispatch<float>(a, stream);
-}
-
 // B3: after B1 / the tape pass and B2 (what every backward pays: one small launch)
+// (the TF-only backward over the tape: the stride P carries is checked against the header)
 template <typename VT>
-static int ray_exact_bwd_dispatch(const MarchArgs &a, hipStream_t stream) {
-    const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    Workspace w;
-    ws_layout(a.workspace, a.n_views, a.W * a.H, g, &w);
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    if ((a.hints & DR_TAPE_TF) && !a.d_vol) P.tape_stride = tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S);   // (checked against the header)
-    const size_t lds = (size_t)a.R * 32 + (size_t)EXACT_BWD_NT * 32;
+int launch_ray_exact_bwd(const BrickParams<VT> &P, hipStream_t stream) {
+    const size_t lds = (size_t)P.R * 32 + (size_t)EXACT_BWD_NT * 32;
     const hipError_t e = allow_lds(ray_exact_bwd_kernel<VT>, lds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((ray_exact_bwd_kernel<VT>), dim3(DR_EXACT_BWD_GRID), dim3(EXACT_BWD_NT), lds, stream, P);
     return (int)hipGetLastError();
 }
-int launch_ray_exact_bwd(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? ray_exact_bwd_dispatch<__half>(a, stream) : ray_exact_bwd_dispatch<float>(a, stream);
-}
 
 // F3: the rays F2 listed, if any -- a resident grid that reads the count from the workspace header and leaves at once when it is 0
 // (what every forward pays: one small launch)
 template <typename VT>
-static int ray_exact_dispatch(const MarchArgs &a, hipStream_t stream) {
-    const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    Workspace w;
-    ws_layout(a.workspace, a.n_views, a.W * a.H, g, &w);
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    if (a.mode == DR_MODE_DIFF) {
-        hipLaunchKernelGGL((ray_exact_kernel<VT, DR_MODE_DIFF, 1024>), dim3(EXACT_FEW), dim3(1024), 0, stream, P);
-        hipLaunchKernelGGL((ray_exact_kernel<VT, DR_MODE_DIFF, 256>), dim3(DR_EXACT_GRID), dim3(256), 0, stream, P);
-    } else {
-        hipLaunchKernelGGL((ray_exact_kernel<VT, DR_MODE_NONDIFF, 1024>), dim3(EXACT_FEW), dim3(1024), 0, stream, P);
-        hipLaunchKernelGGL((ray_exact_kernel<VT, DR_MODE_NONDIFF, 256>), dim3(DR_EXACT_GRID), dim3(256), 0, stream, P);
-    }
+int launch_ray_exact(const BrickParams<VT> &P, hipStream_t stream) {
+    with_mode(P.nondiff, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        hipLaunchKernelGGL((ray_exact_kernel<VT, MODE, 1024>), dim3(EXACT_FEW), dim3(1024), 0, stream, P);
+        hipLaunchKernelGGL((ray_exact_kernel<VT, MODE, 256>), dim3(DR_EXACT_GRID), dim3(256), 0, stream, P);
+    });
     return (int)hipGetLastError();
 }
-int launch_ray_exact(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? ray_exact_dispatch<__half>(a, stream) : ray_exact_dispatch<float>(a, stream);
-}
 
+// The alpha pre-pass's per-ray kernels: the composition of one phase (cross = false), or the exact termination sample of the crossing rays
 template <typename VT>
-static int ray_alpha_dispatch(const MarchArgs &a, hipStream_t stream, bool cross) {
-    const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    const int NP = a.W * a.H;
-    Workspace w;
-    ws_layout(a.workspace, a.n_views, NP, g, &w);
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
+int launch_ray_alpha(const BrickParams<VT> &P, bool cross, hipStream_t stream) {
+    const int NP = P.W * P.H;
     // The crossing search runs as ~8 192 workgroups over all views (32 768 waves: four rounds of what the chip holds), each staging
     // the TF once and striding over the rays -- not one workgroup per four rays: 131 072 of them for the demo's 8 x 256^2 rays,
     // each paying the TF load and a barrier first (demo loop 10.25 -> 10.20 ms; 2 048 workgroups: +0.1 ms, rays queue up behind
     // long ones). DR_CROSS_GRID = workgroups over all views.
-    const int cross_cap = (DR_CROSS_GRID + a.n_views - 1) / a.n_views < 64 ? 64 : (DR_CROSS_GRID + a.n_views - 1) / a.n_views;
-    const dim3 grid2((NP + 255) / 256, a.n_views), grid3((NP + 3) / 4 < cross_cap ? (NP + 3) / 4 : cross_cap, a.n_views);
-    const size_t lds3 = (size_t)a.R * 16;
+    const int cross_cap = (DR_CROSS_GRID + P.n_views - 1) / P.n_views < 64 ? 64 : (DR_CROSS_GRID + P.n_views - 1) / P.n_views;
+    const dim3 grid2((NP + 255) / 256, P.n_views), grid3((NP + 3) / 4 < cross_cap ? (NP + 3) / 4 : cross_cap, P.n_views);
+    const size_t lds3 = (size_t)P.R * 16;
     // below sampling rate 2 a crossing segment is short: four rays per wave (ray_cross_quad_kernel)
-    const bool quad = a.sr < DR_CROSS_QUAD_BELOW;
-    const dim3 grid3q((NP + 15) / 16 < cross_cap ? (NP + 15) / 16 : cross_cap, a.n_views);
-    if (a.mode == DR_MODE_DIFF) {
-        if (!cross) hipLaunchKernelGGL((ray_alpha_kernel<VT, DR_MODE_DIFF>), grid2, dim3(256), 0, stream, P);
-        else if (quad) hipLaunchKernelGGL((ray_cross_quad_kernel<VT, DR_MODE_DIFF>), grid3q, dim3(256), lds3, stream, P);
-        else hipLaunchKernelGGL((ray_cross_kernel<VT, DR_MODE_DIFF>), grid3, dim3(256), lds3, stream, P);
-    } else {
-        if (!cross) hipLaunchKernelGGL((ray_alpha_kernel<VT, DR_MODE_NONDIFF>), grid2, dim3(256), 0, stream, P);
-        else if (quad) hipLaunchKernelGGL((ray_cross_quad_kernel<VT, DR_MODE_NONDIFF>), grid3q, dim3(256), lds3, stream, P);
-        else hipLaunchKernelGGL((ray_cross_kernel<VT, DR_MODE_NONDIFF>), grid3, dim3(256), lds3, stream, P);
-    }
+    const bool quad = P.sr < DR_CROSS_QUAD_BELOW;
+    const dim3 grid3q((NP + 15) / 16 < cross_cap ? (NP + 15) / 16 : cross_cap, P.n_views);
+    with_mode(P.nondiff, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (!cross) hipLaunchKernelGGL((ray_alpha_kernel<VT, MODE>), grid2, dim3(256), 0, stream, P);
+        else if (quad) hipLaunchKernelGGL((ray_cross_quad_kernel<VT, MODE>), grid3q, dim3(256), lds3, stream, P);
+        else hipLaunchKernelGGL((ray_cross_kernel<VT, MODE>), grid3, dim3(256), lds3, stream, P);
+    });
     return (int)hipGetLastError();
 }
 
-int launch_ray_alpha(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? ray_alpha_dispatch<__half>(a, stream, false) : ray_alpha_dispatch<float>(a, stream, false);
-}
-int launch_ray_cross(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? ray_alpha_dispatch<__half>(a, stream, true) : ray_alpha_dispatch<float>(a, stream, true);
-}
+// (in the order the kernels have always been emitted: the device assembly of this file is compared against its history, tools/asm_same.sh)
+template int launch_ray_compose<__half>(const BrickParams<__half> &, hipStream_t);
+template int launch_ray_compose<float>(const BrickParams<float> &, hipStream_t);
+template int launch_ray_exact_bwd<__half>(const BrickParams<__half> &, hipStream_t);
+template int launch_ray_exact_bwd<float>(const BrickParams<float> &, hipStream_t);
+template int launch_ray_exact<__half>(const BrickParams<__half> &, hipStream_t);
+template int launch_ray_exact<float>(const BrickParams<float> &, hipStream_t);
+template int launch_ray_alpha<__half>(const BrickParams<__half> &, bool, hipStream_t);
+template int launch_ray_alpha<float>(const BrickParams<float> &, bool, hipStream_t);
 
 }  // namespace dr

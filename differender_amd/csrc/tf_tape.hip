@@ -193,40 +193,27 @@ __global__ __launch_bounds__(256) void dtf_commit_kernel(BrickParams<VT> P) {
     }
 }
 template <typename VT>
-static int dtf_commit_dispatch(const MarchArgs &a, hipStream_t stream) {
-    const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    Workspace w;
-    ws_layout(a.workspace, a.n_views, a.W * a.H, g, &w);
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    if ((a.hints & DR_TAPE_TF) && !a.d_vol) P.tape_stride = tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S);
-    hipLaunchKernelGGL((dtf_commit_kernel<VT>), dim3((4 * a.R + 255) / 256, a.n_views), dim3(256), 0, stream, P);
+int launch_dtf_commit(const BrickParams<VT> &P, hipStream_t stream) {
+    hipLaunchKernelGGL((dtf_commit_kernel<VT>), dim3((4 * P.R + 255) / 256, P.n_views), dim3(256), 0, stream, P);
     return (int)hipGetLastError();
-}
-int launch_dtf_commit(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? dtf_commit_dispatch<__half>(a, stream) : dtf_commit_dispatch<float>(a, stream);
 }
 
 template <typename VT>
-static int tf_tape_dispatch(const MarchArgs &a, hipStream_t stream) {
-    const BrickGrid g = make_brick_grid(a.VX, a.VY, a.VZ);
-    const int NP = a.W * a.H;
-    const int tstride = tape_stride_for(a.VX, a.VY, a.VZ, a.sr, a.S);
-    Workspace w;
-    ws_layout(a.workspace, a.n_views, NP, g, &w, tstride);
-    BrickParams<VT> P = make_brick_params<VT>(a, w);
-    P.tape = w.tape; P.tape_stride = tstride;
-    const size_t lds = (size_t)a.R * 48;
+int launch_tf_tape_bwd(const BrickParams<VT> &P, hipStream_t stream) {
+    const int NP = P.W * P.H;
+    const size_t lds = (size_t)P.R * 48;
     const hipError_t e = allow_lds(tf_tape_bwd_kernel<VT>, lds);
     if (e != hipSuccess) return (int)e;
-    int gx = (DR_TAPE_GRID + a.n_views - 1) / a.n_views;
+    int gx = (DR_TAPE_GRID + P.n_views - 1) / P.n_views;
     if (gx > (NP + 3) / 4) gx = (NP + 3) / 4;
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL((tf_tape_bwd_kernel<VT>), dim3(gx, a.n_views), dim3(256), lds, stream, P);
+    hipLaunchKernelGGL((tf_tape_bwd_kernel<VT>), dim3(gx, P.n_views), dim3(256), lds, stream, P);
     return (int)hipGetLastError();
 }
 
-int launch_tf_tape_bwd(const MarchArgs &a, hipStream_t stream) {
-    return a.vol_dtype == DR_F16 ? tf_tape_dispatch<__half>(a, stream) : tf_tape_dispatch<float>(a, stream);
-}
+template int launch_dtf_commit<__half>(const BrickParams<__half> &, hipStream_t);
+template int launch_dtf_commit<float>(const BrickParams<float> &, hipStream_t);
+template int launch_tf_tape_bwd<__half>(const BrickParams<__half> &, hipStream_t);
+template int launch_tf_tape_bwd<float>(const BrickParams<float> &, hipStream_t);
 
 }  // namespace dr
