@@ -86,7 +86,7 @@ def raycast(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate):
     ambient, diffuse_k, specular_k, shininess = 0.4, 0.8, 0.3, 32.0
     light_pos = cam + torch.tensor([0.0, 1.0, 0.0], dtype=F64)
     nf = n.to(F64)
-    for s in range(int(n.max())):
+    for s in range(int(n.max()) if P else 0):   # (no ray at all: a view that misses the box)
         active = ((s < n) & (tape[:, 3] < 0.99) & (s < max_samples)).detach()   # VR.py:267-269
         if not bool(active.any()):
             continue

@@ -35,11 +35,16 @@ def inputs(name, WH=None, **over):
 
 
 def refs(inp):
-    return PR.run_case(inp), PR.run_case(inp, dtype=torch.float32)
+    return K.with_kinks(inp, PR.run_case(inp), "look_from"), PR.run_case(inp, dtype=torch.float32)
 
 
 def keep(ref, ref32):
     return (ref32["steps"] == ref["steps"]) & (ref32["n"] == ref["n"])
+
+
+def well_conditioned(ref, ref32, keep_, what=None, key="dpose_ray", lit=True):
+    """camgrad_gpu.well_conditioned over the four pose tensors, each judged by its own scale: the mask of the second pass."""
+    return K.well_conditioned(ref, ref32, keep_, key, COLUMNS, what, lit)
 
 
 def pose_rows(inps):
@@ -79,6 +84,16 @@ def hip_per_ray(inp, ref, vol_dtype, keep_):
     ray, total, mask, _ = launch(dev(inp["vol"]).to(vol_dtype), dev(inp["tf"]), [inp], [ref], [keep_], int(inp["max_samples"]),
                                  float(inp["sr"]), int(inp["jitter_seed"]), int(inp["view"]))
     return ray[0], total[0], mask[0]
+
+
+def both_passes(inp, ref, ref32, vol_dtype, what, run=hip_per_ray):
+    """One view, one launch per pass: pose_rule over all compared rays, then over the well-conditioned ones alone.
+    run(inp, ref, vol_dtype, keep) -> (ray, total, mask, ...). -> the first pass's (ray, total, mask)."""
+    first = run(inp, ref, vol_dtype, keep(ref, ref32))[:3]
+    pose_rule(*first[:2], ref, ref32, first[2], what)
+    ray, total, mask = run(inp, ref, vol_dtype, well_conditioned(ref, ref32, keep(ref, ref32), what))[:3]
+    pose_rule(ray, total, ref, ref32, mask, (what, "conditioned"))
+    return first
 
 
 def _three(a, sl):

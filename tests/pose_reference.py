@@ -108,8 +108,13 @@ def run_case(inp, dtype=torch.float64, pixels=None):
                                  int(inp["max_samples"]), float(inp["sr"]))
     finally:
         G.F64 = old
-    (out_sel * T(inp["grad_out"]).reshape(P, 4)[sel]).sum().backward()
-    res = _result(W, H, e, x, r, n, (lf, la, up, fov))
+    leaves = (lf, la, up, fov)
+    if out_sel.requires_grad:
+        (out_sel * T(inp["grad_out"]).reshape(P, 4)[sel]).sum().backward()
+    for leaf in leaves:   # (no ray marched: a view that misses the box)
+        if leaf.grad is None:
+            leaf.grad = torch.zeros_like(leaf)
+    res = _result(W, H, e, x, r, n, leaves)
     steps = np.zeros(P, np.int32); steps[sel.numpy()] = cnt.numpy()
     out = np.zeros((P, 4)); out[sel.numpy()] = out_sel.detach().double().numpy()
     res.update(steps=steps.reshape(W, H), rgba=out.reshape(W, H, 4))

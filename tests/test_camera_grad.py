@@ -124,6 +124,55 @@ def test_autograd_matches_finite_differences_of_the_f64_oracle(oracle, path):
     assert (err <= 1e-5 * scale).mean() >= 0.99, (np.sort(err)[-5:] / scale, same.sum())
 
 
+# ---- the conditioned pass of the GPU tests (camgrad_gpu.well_conditioned): its conditions, and that it bites -------------------
+
+def _conditioned_cases():
+    """Everything test_gpu_camera_grad.py and test_gpu_camera_grad_edges.py feed to the conditioned pass: id -> a function that
+    returns [(ref, ref32, keep, row bands or None)]. The fixtures with the float32 volume and with its float16 rounding."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_camera_grad as TG
+    import test_gpu_camera_grad_edges as TE
+    cases = {}
+    for p in FIXTURES:
+        for f16 in (False, True):
+            cases["%s_%s" % (os.path.basename(p)[8:-4], "f16" if f16 else "f32")] = \
+                lambda p=p, f16=f16: [TG.fixture_case(p, f16)[1:] + (None,)]
+    cases.update(TE.CONDITIONED)
+    return cases
+
+
+CONDITIONED = _conditioned_cases()
+
+
+@pytest.mark.parametrize("case", sorted(CONDITIONED))
+def test_cases_keep_enough_well_conditioned_rays(case):
+    """The rays on which the float32 and the float64 reference agree to 1e-4 of the scale are at least 80 % of the n > 1 rays
+    (in every row band where the rule is applied band by band), and err32 over them is within 1e-4 of the scale: the second
+    pass of the GPU tests then bounds every ray by 4e-4 of it."""
+    import camgrad_gpu as K
+    K.check_conditions(CONDITIONED[case]())
+
+
+def test_grazing_cases_keep_their_grazing_rays_well_conditioned():
+    import test_gpu_camera_grad_edges as TE
+    for name in sorted(TE.GRAZING):
+        inp, ref, ref32 = TE._grazing_case(name)
+        assert (TE._grazing_rays(name, inp, ref) & TE._good(ref, ref32)).sum() >= 6, name
+
+
+def test_the_conditioned_rule_rejects_a_one_percent_error():
+    """a_orbit_sr1: one ray next to a lighting kink puts err32 at 3 % of the scale, and D8's rule over all rays accepts a
+    gradient that is 1 % off everywhere. Over the well-conditioned rays it does not."""
+    import camgrad_gpu as K
+    import test_gpu_camera_grad as TG
+    path = os.path.join(GOLDEN, "camgrad_a_orbit_sr1.npz")
+    for f16 in (False, True):
+        _, ref, ref32, keep = TG.fixture_case(path, f16)
+        good = K.well_conditioned(ref, ref32, keep)
+        assert good.sum() < (keep & (ref["n"] > 1)).sum()   # there are ill-conditioned rays to leave out
+        K.mutation_check(K.d8_rule, ref["dcam_ray"], ref32["dcam_ray"], ref, ref32, keep, good)
+
+
 def test_generator_reproduces_its_fixture():
     import make_camgrad_golden as CG
     name = "d_jitter"

@@ -42,7 +42,7 @@ def _inputs(name, WH=None, **over):
 
 
 def _refs(inp):
-    return CG.run_case(inp), CG.run_case(inp, dtype=torch.float32)
+    return K.with_kinks(inp, CG.run_case(inp)), CG.run_case(inp, dtype=torch.float32)
 
 
 def _keep(ref, ref32):
@@ -73,10 +73,26 @@ def _view_case(batched):
     return views
 
 
-def _launch_views(views, vol, tf, **kw):
+def _launch_views(views, vol, tf, keeps=None, **kw):
     inp0 = views[0][0]
+    keeps = [_keep(r, r32) for _, r, r32 in views] if keeps is None else keeps
     return K.launch(vol, tf, [i["cam"] for i, _, _ in views], [r for _, r, _ in views], [i["grad_out"] for i, _, _ in views],
-                    [_keep(r, r32) for _, r, r32 in views], int(inp0["max_samples"]), float(inp0["sr"]), VIEW_SEED, VIEW_BASE, **kw)
+                    keeps, int(inp0["max_samples"]), float(inp0["sr"]), VIEW_SEED, VIEW_BASE, **kw)
+
+
+def _good(ref, ref32, what=None):
+    """The keep mask of the second, conditioned pass (camgrad_gpu.well_conditioned)."""
+    return K.well_conditioned(ref, ref32, _keep(ref, ref32), what=what)
+
+
+def _both_passes(inp, ref, ref32, vol_dtype, what):
+    """One view, one launch per pass: D8's rule over all compared rays, then over the well-conditioned ones alone.
+    -> the first pass's (ray, total, mask)."""
+    first = K.hip_per_ray(inp, ref, vol_dtype, _keep(ref, ref32))
+    K.d8_rule(*first[:2], ref, ref32, first[2], what)
+    ray, total, mask = K.hip_per_ray(inp, ref, vol_dtype, _good(ref, ref32, what))
+    K.d8_rule(ray, total, ref, ref32, mask, (what, "conditioned"))
+    return first
 
 
 @pytest.mark.parametrize("kind", ["shared", "batched", "batched_permuted_f16"])
@@ -94,6 +110,9 @@ def test_views_of_one_launch_match_the_f64_reference(hiplib, kind):
     ray, total, masks, _ = _launch_views(views, vol, tf)
     for v, (inp, ref, ref32) in enumerate(views):
         K.d8_rule(ray[v], total[v], ref, ref32, masks[v], (kind, "view", v))
+    ray, total, masks, _ = _launch_views(views, vol, tf, keeps=[_good(r, r32, (kind, "view", v)) for v, (_, r, r32) in enumerate(views)])
+    for v, (inp, ref, ref32) in enumerate(views):
+        K.d8_rule(ray[v], total[v], ref, ref32, masks[v], (kind, "view", v, "conditioned"))
 
 
 def test_the_jitter_draw_depends_on_the_view_index(hiplib):
@@ -107,27 +126,38 @@ def test_the_jitter_draw_depends_on_the_view_index(hiplib):
     differ = (ray[0] != ray[1]).any(-1)[m]
     assert differ.mean() > 0.9, differ.mean()
     assert np.abs(ray[0] - ray[1])[m].max() > 1e-3 * np.abs(ray[0]).max()
+    ray, total, masks, _ = _launch_views(twice, _dev(inp["vol"]), _dev(inp["tf"]), keeps=[_good(ref, ref32, "same buffers")] * 2)
+    K.d8_rule(ray[0], total[0], ref, ref32, masks[0], "same buffers, view 0, conditioned")
 
 
 # ---- row bands: row0 != 0 against float64 ----------------------------------------------------------------------------------
 
+BANDS = ((0, 7), (7, 9), (16, 6))   # (row0, rows) of a 22-row image
+
+
+@functools.lru_cache(maxsize=None)
+def _band_case():
+    inp = _inputs("a_orbit_sr1", WH=(22, 14), jitter_seed=np.int64(6021), cam=np.array(CAMS[1]))
+    return (inp,) + _refs(inp)
+
+
 def test_row_bands_match_the_rows_of_the_f64_reference(hiplib):
-    Wimg, H = 22, 14
-    inp = _inputs("a_orbit_sr1", WH=(Wimg, H), jitter_seed=np.int64(6021), cam=np.array(CAMS[1]))
-    ref, ref32 = _refs(inp)
+    inp, ref, ref32 = _band_case()
+    Wimg = ref["n"].shape[0]
     vol, tf = _dev(inp["vol"]), _dev(inp["tf"])
-    keep = _keep(ref, ref32)
-    totals = []
-    for row0, Wb in ((0, 7), (7, 9), (16, 6)):
-        rows = slice(row0, row0 + Wb)
-        band = lambda r: {k: r[k][rows] for k in ("entry", "exit", "rays", "n", "steps", "dcam_ray")}
-        ray, total, masks, _ = K.launch(vol, tf, inp["cam"], [band(ref)], [inp["grad_out"][rows]], [keep[rows]],
-                                        int(inp["max_samples"]), float(inp["sr"]), int(inp["jitter_seed"]), int(inp["view"]),
-                                        rows=(row0, Wimg))
-        K.d8_rule(ray[0], total[0], band(ref), band(ref32), masks[0], ("band", row0, Wb))
-        totals.append((total[0], masks[0]))
-    mask = np.concatenate([m for _, m in totals], 0)
-    K.d8_total_rule(sum(t for t, _ in totals), ref["dcam_ray"], ref32["dcam_ray"], mask, "the bands' sum")
+    # the second pass: the well-conditioned rays of the whole image (one scale), band by band
+    for keep, tag in ((_keep(ref, ref32), ()), (_good(ref, ref32, "bands"), ("conditioned",))):
+        totals = []
+        for row0, Wb in BANDS:
+            rows = slice(row0, row0 + Wb)
+            band = lambda r: {k: r[k][rows] for k in ("entry", "exit", "rays", "n", "steps", "dcam_ray")}
+            ray, total, masks, _ = K.launch(vol, tf, inp["cam"], [band(ref)], [inp["grad_out"][rows]], [keep[rows]],
+                                            int(inp["max_samples"]), float(inp["sr"]), int(inp["jitter_seed"]), int(inp["view"]),
+                                            rows=(row0, Wimg))
+            K.d8_rule(ray[0], total[0], band(ref), band(ref32), masks[0], ("band", row0, Wb) + tag)
+            totals.append((total[0], masks[0]))
+        mask = np.concatenate([m for _, m in totals], 0)
+        K.d8_total_rule(sum(t for t, _ in totals), ref["dcam_ray"], ref32["dcam_ray"], mask, ("the bands' sum",) + tag)
 
 
 # ---- the TF in LDS (R <= 3072) and read where it lies (R > 3072) -----------------------------------------------------------------
@@ -159,19 +189,26 @@ def test_table_in_lds_and_in_memory_match_the_f64_reference(hiplib, R, vol_dtype
     limit = _lds_limit_bytes()
     assert 3072 * 16 <= limit < 3073 * 16   # 3072 is the last table staged in LDS, 3073 the first read where it lies
     inp, ref, ref32 = _table_case(R, vol_dtype == torch.float16)
-    ray, total, mask = K.hip_per_ray(inp, ref, vol_dtype, _keep(ref, ref32))
-    K.d8_rule(ray, total, ref, ref32, mask, ("R", R, "LDS" if R * 16 <= limit else "memory", str(vol_dtype)))
+    _both_passes(inp, ref, ref32, vol_dtype, ("R", R, "LDS" if R * 16 <= limit else "memory", str(vol_dtype)))
 
 
 # ---- images smaller than a tile, workgroups with idle lanes and idle waves -------------------------------------------------------
 
-@pytest.mark.parametrize("WH", [(1, 1), (3, 5), (8, 8), (9, 17), (33, 7)], ids=lambda wh: "%dx%d" % wh)
+SHAPES = [(1, 1), (3, 5), (8, 8), (9, 17), (33, 7)]
+
+
+@functools.lru_cache(maxsize=None)
+def _shape_case(WH):
+    # (1 x 1 from CAMS[2]: the one ray of CAMS[1] lies next to a kink, its float32 reference 2e-3 of its own gradient off)
+    inp = _inputs("a_orbit_sr1", WH=WH, jitter_seed=np.int64(77), cam=np.array(CAMS[2 if WH == (1, 1) else WH[0] % 3]))
+    return (inp,) + _refs(inp)
+
+
+@pytest.mark.parametrize("WH", SHAPES, ids=lambda wh: "%dx%d" % wh)
 def test_image_shapes_match_the_f64_reference_and_sum_up(hiplib, WH):
-    inp = _inputs("a_orbit_sr1", WH=WH, jitter_seed=np.int64(77), cam=np.array(CAMS[WH[0] % 3]))
-    ref, ref32 = _refs(inp)
+    inp, ref, ref32 = _shape_case(WH)
     assert (ref["n"] > 1).any()
-    ray, total, mask = K.hip_per_ray(inp, ref, torch.float32, _keep(ref, ref32))
-    K.d8_rule(ray, total, ref, ref32, mask, ("image", WH))
+    ray, total, mask = _both_passes(inp, ref, ref32, torch.float32, ("image", WH))
     # idle lanes and idle waves add nothing to the workgroup's sum (the rule above already holds it to 1e-5 of sum |ray|)
     assert np.abs(total - ray.sum((0, 1))).max() <= 1e-5 * np.abs(ray).sum()
     assert np.abs(total).max() > 0
@@ -188,18 +225,28 @@ GRAZING = {"x_lower": ((2.4, 0.1981, 0.0), 0, -1.0), "x_upper": ((-2.4, 0.1981, 
            "z_upper": ((-2.4, 0.0, 0.1994), 2, 1.0), "z_lower": ((2.4, 0.0, -0.1994), 2, -1.0)}
 
 
-@pytest.mark.parametrize("name", sorted(GRAZING))
-def test_rays_leaving_next_to_an_edge_match_the_f64_reference(hiplib, name):
-    cam, axis, sign = GRAZING[name]
-    inp = _inputs("o_edge_grazing", cam=np.array(cam))
-    ref, ref32 = _refs(inp)
+@functools.lru_cache(maxsize=None)
+def _grazing_case(name):
+    inp = _inputs("o_edge_grazing", cam=np.array(GRAZING[name][0]))
+    return (inp,) + _refs(inp)
+
+
+def _grazing_rays(name, inp, ref):
+    _, axis, sign = GRAZING[name]
     last = inp["cam"] + ref["exit"][..., None] * ref["rays"]
     gap = 1.0 - sign * last[..., axis]
-    grazing = (gap > 2e-4) & (gap < 8e-4) & ((1.0 - np.abs(last) < 1e-9).sum(-1) == 1) & (ref["n"] > 1)
+    return (gap > 2e-4) & (gap < 8e-4) & ((1.0 - np.abs(last) < 1e-9).sum(-1) == 1) & (ref["n"] > 1)
+
+
+@pytest.mark.parametrize("name", sorted(GRAZING))
+def test_rays_leaving_next_to_an_edge_match_the_f64_reference(hiplib, name):
+    inp, ref, ref32 = _grazing_case(name)
+    grazing = _grazing_rays(name, inp, ref)
     assert grazing.sum() >= 6, grazing.sum()
-    ray, total, mask = K.hip_per_ray(inp, ref, torch.float32, _keep(ref, ref32))
+    # (the conditioned pass keeps grazing rays too: tests/test_camera_grad.py holds the case to that)
+    assert (grazing & _good(ref, ref32)).sum() >= 6
+    ray, total, mask = _both_passes(inp, ref, ref32, torch.float32, ("grazing", name))
     assert mask[grazing].all()
-    K.d8_rule(ray, total, ref, ref32, mask, ("grazing", name))
 
 
 # ---- D5: non-finite upstream gradients ------------------------------------------------------------------------------------------
@@ -228,7 +275,8 @@ def test_nan_upstream_gradients_contribute_nothing(hiplib):
     # a NaN in one channel, in all four, and in between
     chan = _dev(np.random.RandomState(4).rand(1, W, H, 4) < 0.5, torch.bool)
     chan[..., 0] |= ~chan.any(-1)
-    ray_n, total_n, masks, g = _d5_launch(lambda g: torch.where(bad_t & chan, torch.full_like(g, float("nan")), g))
+    nans = lambda g: torch.where(bad_t & chan, torch.full_like(g, float("nan")), g)
+    ray_n, total_n, masks, g = _d5_launch(nans)
     assert bool(torch.isnan(g).any(-1)[0][_dev(bad, torch.bool)].all())
     ray_0, total_0, masks_0, _ = _d5_launch(None, keep_extra=~bad)
     assert (ray_n[0][bad] == 0).all() and np.isfinite(ray_n).all()
@@ -238,6 +286,10 @@ def test_nan_upstream_gradients_contribute_nothing(hiplib):
     assert np.isfinite(total_n).all()
     assert np.abs(total_n[0] - ray_n[0].sum((0, 1))).max() <= 1e-5 * np.abs(ray_n[0]).sum()
     K.d8_total_rule(total_n[0], ref["dcam_ray"], ref32["dcam_ray"], ok, "NaN upstream")
+    # the same total over the well-conditioned rays alone, the NaN pixels still in the upstream gradient
+    ray_c, total_c, masks_c, g = _d5_launch(nans, keep_extra=_good(ref, ref32, "NaN upstream"))
+    assert bool(torch.isnan(g).any(-1)[0][_dev(bad, torch.bool)].all()) and np.isfinite(total_c).all()
+    K.d8_total_rule(total_c[0], ref["dcam_ray"], ref32["dcam_ray"], masks_c[0] & ~bad, "NaN upstream, conditioned")
 
 
 def test_infinite_upstream_gradients_are_clamped(hiplib):
@@ -263,6 +315,27 @@ def test_infinite_upstream_gradients_are_clamped(hiplib):
     assert np.isfinite(ray_i).all() and np.abs(ray_i[0][hot]).max() <= 1e30
     assert np.array_equal(ray_i[0][~hot], ray_0[0][~hot]) and (ray_0[0][masks_0[0]] != 0).any(-1).all()
     assert np.isfinite(total_i).all()
+
+
+# ---- what the conditioned pass is fed, for tests/test_camera_grad.py to hold to its conditions without a GPU -------------------
+
+def _band_parts():
+    inp, ref, ref32 = _band_case()
+    return [(ref, ref32, _keep(ref, ref32), [slice(r0, r0 + wb) for r0, wb in BANDS])]
+
+
+# id -> a function that returns [(float64 reference, float32 reference, keep mask, row bands or None)], one entry per view
+CONDITIONED = {"bands": _band_parts, "d5_e_nonsquare": lambda: [_d5_case()[1:] + (_keep(*_d5_case()[1:]), None)]}
+for _b in (False, True):
+    CONDITIONED["views_%s" % ("batched" if _b else "shared")] = lambda b=_b: [(r, r32, _keep(r, r32), None) for _, r, r32 in _view_case(b)]
+for _R in (3072, 3073, 4096):
+    for _f16 in (False, True):
+        CONDITIONED["table_%d_%s" % (_R, "f16" if _f16 else "f32")] = \
+            lambda R=_R, f=_f16: [_table_case(R, f)[1:] + (_keep(*_table_case(R, f)[1:]), None)]
+for _wh in SHAPES:
+    CONDITIONED["image_%dx%d" % _wh] = lambda wh=_wh: [_shape_case(wh)[1:] + (_keep(*_shape_case(wh)[1:]), None)]
+for _n in sorted(GRAZING):
+    CONDITIONED["grazing_" + _n] = lambda n=_n: [_grazing_case(n)[1:] + (_keep(*_grazing_case(n)[1:]), None)]
 
 
 # ---- through Raycaster, with jitter ---------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """The free camera on the GPU: the pose ray setup, the brick-centric fast path under a pose, the pose gradient
 of the march and of the projections against the float64 autograd reference (tests/pose_reference.py), and the four renderers."""
+import functools
 import math
 import os
 import sys
@@ -161,15 +162,26 @@ def _check_fast(res, what, heavy=None):
         assert ok, (what, k, err)
 
 
-@pytest.mark.parametrize("name", ["panned", "rolled", "all"])
+# look_at, up, fov of the two views (degrees): the hard poses of the fast path. The share of n > 1 rays of the two cameras was
+# checked on the CPU (pose_reference.ray_setup): 0.68 / 0.80, 0.69 / 0.80, 1.0 / 1.0, 0.53 / 0.60.
+FAST_HARD_POSES = {"upside_down": (None, (0.0, -1.0, 0.0), None), "roll_90": (None, (1.0, 0.05, 0.0), None),
+                   "narrow": (None, None, (8.0, 6.0)), "half_off": ((0.9, 0.6, -0.4), None, None)}
+FAST_SIZE = (48, 40)
+
+
+@pytest.mark.parametrize("name", ["panned", "rolled", "all"] + sorted(FAST_HARD_POSES))
 def test_fast_path_serves_a_posed_camera(hiplib, oracle, name):
     """The test that fails if only the ray setup learns the pose: with the fixed camera's brick rectangles the rays of a panned
     or rolled camera fail the sample-count check (workspace_stats[0]) and are marched one by one."""
-    look_at, up, fov = POSES[name]
+    if name in FAST_HARD_POSES:
+        look_at, up, fovs = FAST_HARD_POSES[name]
+    else:
+        look_at, up, fov = POSES[name]
+        fovs = None if fov is None else (fov, fov - 8.0)
     vol, tf = _fast_scene(oracle)
     pose = _pose(CAMS[:2], look_at, up)
-    fov_v = None if fov is None else torch.deg2rad(torch.tensor([fov, fov - 8.0], device=DEV()))
-    res = _fast_and_baseline(vol, tf, pose, fov_v, (48, 40), seed=77 if name == "all" else 0)
+    fov_v = None if fovs is None else torch.deg2rad(torch.tensor(fovs, device=DEV()))
+    res = _fast_and_baseline(vol, tf, pose, fov_v, FAST_SIZE, seed=77 if name == "all" else 0)
     assert (res["n"] > 1).float().mean() > 0.25
     _check_fast(res, name)
 
@@ -208,11 +220,24 @@ GRAD_CASES = {
     "look_at_off_centre": ("a_orbit_sr1", dict(look_at=(0.25, -0.15, 0.2))),
     "roll": ("e_nonsquare", dict(up=(0.35, 1.0, -0.2))),
     "per_view_fov": ("a_orbit_sr1", dict(fov_rad=math.radians(23.0))),
-    "all_three": ("l_anisotropic", dict(look_at=(-0.2, 0.1, 0.15), up=(-0.3, 0.9, 0.25), fov_rad=math.radians(36.0))),
+    # (34 degrees: at 36 only 75 of the 92 n > 1 rays were well-conditioned, one ray from the cap, and 72 with the float32
+    # reference of another CPU; here 104 of 112, and one ray still puts err32 at 4 % of the scale)
+    "all_three": ("l_anisotropic", dict(look_at=(-0.2, 0.1, 0.15), up=(-0.3, 0.9, 0.25), fov_rad=math.radians(34.0))),
     "inside": ("j_inside", dict(look_at=(-0.3, 0.05, 0.4), up=(0.3, 1.0, 0.1), fov_rad=math.radians(34.0))),
     "jitter": ("d_jitter", dict(look_at=(0.1, 0.2, -0.15), up=(0.2, 1.0, 0.1))),
     "early_termination_sr2": ("b_sr2_ert", dict(look_at=(0.15, -0.1, 0.1), up=(-0.25, 1.0, 0.15), fov_rad=math.radians(27.0))),
     "max_samples_clip": ("c_clip", dict(look_at=(-0.1, 0.15, 0.1), up=(0.15, 1.0, -0.3))),
+    # hard poses: the camera upside down, rolled by a quarter and by three eighths of a turn (right and up' swap roles and
+    # signs in pose_ray_grad), a 5 degree zoom (near_h, and with it d fov, 1/7 of the default's), a wide angle on a 24 x 24
+    # image (the box fills a third of it), the box half off the image and in one corner of it (26 rays). Each keeps its share
+    # of well-conditioned rays (tests/test_pose.py).
+    "upside_down": ("e_nonsquare", dict(up=(0.0, -1.0, 0.0))),
+    "roll_90": ("e_nonsquare", dict(up=(1.0, 0.05, 0.0))),
+    "roll_135": ("a_orbit_sr1", dict(up=(0.7, -0.7, 0.1))),
+    "narrow_5deg": ("a_orbit_sr1", dict(fov_rad=math.radians(5.0))),
+    "wide_45deg": ("a_orbit_sr1", dict(fov_rad=math.radians(45.0), WH=(24, 24))),
+    "half_off": ("e_nonsquare", dict(look_at=(0.9, 0.6, -0.4))),
+    "corner_only": ("a_orbit_sr1", dict(look_at=(1.6, 1.2, 0.3), fov_rad=math.radians(25.0))),
 }
 
 
@@ -220,21 +245,26 @@ GRAD_CASES = {
 GRAD_RUNS = [(name, torch.float32) for name in sorted(GRAD_CASES)] + [("all_three", torch.float16), ("early_termination_sr2", torch.float16)]
 
 
-@pytest.mark.parametrize("name,vol_dtype", GRAD_RUNS, ids=lambda v: v if isinstance(v, str) else str(v)[6:])
-def test_march_bwd_pose_matches_the_f64_reference(hiplib, name, vol_dtype):
+@functools.lru_cache(maxsize=None)
+def grad_case(name, f16):
+    """(inputs, float64 reference, float32 reference) of a case, computed once and shared (read only)."""
     scene, over = GRAD_CASES[name]
     inp = PG.inputs(scene, **over)
-    if vol_dtype == torch.float16:   # the reference on the f16-rounded volume the kernel reads
+    if f16:   # the reference on the f16-rounded volume the kernel reads
         inp["vol"] = PG.F16(inp["vol"])
-    ref, ref32 = PG.refs(inp)
+    return (inp,) + PG.refs(inp)
+
+
+@pytest.mark.parametrize("name,vol_dtype", GRAD_RUNS, ids=lambda v: v if isinstance(v, str) else str(v)[6:])
+def test_march_bwd_pose_matches_the_f64_reference(hiplib, name, vol_dtype):
+    inp, ref, ref32 = grad_case(name, vol_dtype == torch.float16)
     if name == "early_termination_sr2":
         assert ((ref["steps"] < ref["n"]) & (ref["n"] > 1)).sum() > 20
     if name == "max_samples_clip":
         assert (ref["n"] > int(inp["max_samples"])).sum() > 20
     if name == "inside":
         assert (ref["entry"] < 0).all() and (ref["n"] > 1).all()
-    ray, total, mask = PG.hip_per_ray(inp, ref, vol_dtype, PG.keep(ref, ref32))
-    PG.pose_rule(ray, total, ref, ref32, mask, (name, str(vol_dtype)))
+    ray, total, mask = PG.both_passes(inp, ref, ref32, vol_dtype, (name, str(vol_dtype)))
     for _, sl in PG.COLUMNS:   # every tensor has a gradient in every case (d up and d fov are there under the default pose too)
         assert np.abs(ray[..., sl]).max() > 0
 

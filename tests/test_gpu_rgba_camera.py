@@ -70,10 +70,21 @@ def _launch(vol, inps, refs_, keeps, seed=0, view_base=0, upstream=None, entry="
     return d_ray.double().cpu().numpy(), d.double().cpu().numpy(), masks, g
 
 
-def _one(inp, ref, ref32, layout="planar", dtype=torch.float32, entry="pose", upstream=None):
-    ray, total, mask, g = _launch(_volume(inp["vol"], layout, dtype), [inp], [ref], [PG.keep(ref, ref32)], int(inp["jitter_seed"]),
+def _one(inp, ref, ref32, layout="planar", dtype=torch.float32, entry="pose", upstream=None, keep=None):
+    keep = PG.keep(ref, ref32) if keep is None else keep
+    ray, total, mask, g = _launch(_volume(inp["vol"], layout, dtype), [inp], [ref], [keep], int(inp["jitter_seed"]),
                                   int(inp["view"]), upstream, entry)
     return ray[0], total[0], mask[0], g
+
+
+def _good(ref, ref32, what=None):
+    """The keep mask of the second, conditioned pass (pose_gpu.well_conditioned: the rays on which the two references agree)."""
+    return PG.well_conditioned(ref, ref32, PG.keep(ref, ref32), what, lit=False)   # (D16: no lighting, no kinks)
+
+
+def _conditioned_pass(inp, ref, ref32, what, layout="planar", dtype=torch.float32):
+    ray, total, mask, _ = _one(inp, ref, ref32, layout, dtype, keep=_good(ref, ref32, what))
+    pose_rule(ray, total, ref, ref32, mask, (what, "conditioned"))
 
 
 # ---- the pose gradient against the float64 reference -----------------------------------------------------------------------------
@@ -96,6 +107,7 @@ def test_march_rgba_bwd_pose_matches_the_f64_reference(hiplib, name, layout, vol
     pose_rule(ray, total, ref, ref32, mask, (name, layout, str(vol_dtype)))
     for _, sl in COLUMNS:   # every tensor has a gradient in every case
         assert np.abs(ray[..., sl]).max() > 0
+    _conditioned_pass(inp, ref, ref32, (name, layout, str(vol_dtype)), layout, vol_dtype)
 
 
 @pytest.mark.parametrize("seed", [0, 4711])
@@ -109,6 +121,9 @@ def test_march_rgba_bwd_cam_matches_the_reference_and_the_pose_kernels_look_from
     assert cray.shape[-1] == 3
     cref, cref32 = ({"n": r["n"], "dcam_ray": r["dpose_ray"][..., :3]} for r in (ref, ref32))
     K.d8_rule(cray, ctotal, cref, cref32, cmask, ("rgba bwd_cam", seed))
+    good = K.well_conditioned(cref, cref32, PG.keep(ref, ref32), what=("rgba bwd_cam", seed), lit=False)
+    gray, gtotal, gmask, _ = _one(inp, ref, ref32, entry="cam", keep=good)
+    K.d8_rule(gray, gtotal, cref, cref32, gmask, ("rgba bwd_cam", seed, "conditioned"))
     ray, total, mask, _ = _one(inp, ref, ref32)
     assert np.array_equal(mask, cmask)
     scale = np.abs(cray).max()
@@ -134,13 +149,16 @@ def test_a_sub_tile_image(hiplib):
     ray, total, mask, _ = _one(inp, ref, ref32)
     pose_rule(ray, total, ref, ref32, mask, "3x5")
     assert np.abs(ray).max() > 0
+    _conditioned_pass(inp, ref, ref32, "3x5")
 
 
-@pytest.mark.parametrize("batched_vol", [False, True], ids=["shared_volume", "batched_volume"])
-def test_two_views_in_one_launch_are_their_own_single_view_launches(hiplib, batched_vol):
-    """view_base = 3 with jitter and a fov per view: view v draws the jitter of hash view 3 + v, reads its own pose row, fov and
-    (batched) volume, and adds to its own row of d_pose."""
-    seed, base = 77, 3
+TWO_VIEWS_SEED, TWO_VIEWS_BASE = 77, 3
+
+
+@functools.lru_cache(maxsize=None)
+def _two_views_case(batched_vol):
+    """(inputs, float64 references, float32 references, volumes) of the two views, computed once and shared (read only)."""
+    seed, base = TWO_VIEWS_SEED, TWO_VIEWS_BASE
     over = [dict(view=base, seed=seed), dict(view=base + 1, seed=seed, look_from=(-1.9, 1.2, 1.6), look_at=(0.1, 0.15, -0.1),
                                              up=(-0.2, 1.0, 0.1), fov_rad=math.radians(28.0))]
     cases = [_refs("posed_sr2_ert_jit", **o) for o in over]
@@ -150,6 +168,15 @@ def test_two_views_in_one_launch_are_their_own_single_view_launches(hiplib, batc
         inps = [inps[0], dict(inps[1], vol=vols[1])]
         refs_ = [refs_[0], RP.run_case(inps[1])]
         refs32 = [refs32[0], RP.run_case(inps[1], dtype=torch.float32)]
+    return inps, refs_, refs32, vols
+
+
+@pytest.mark.parametrize("batched_vol", [False, True], ids=["shared_volume", "batched_volume"])
+def test_two_views_in_one_launch_are_their_own_single_view_launches(hiplib, batched_vol):
+    """view_base = 3 with jitter and a fov per view: view v draws the jitter of hash view 3 + v, reads its own pose row, fov and
+    (batched) volume, and adds to its own row of d_pose."""
+    seed, base = TWO_VIEWS_SEED, TWO_VIEWS_BASE
+    inps, refs_, refs32, vols = _two_views_case(batched_vol)
     keeps = [PG.keep(a, b) for a, b in zip(refs_, refs32)]
     vol = dev(np.stack(vols)) if batched_vol else dev(vols[0])
     ray, total, masks, _ = _launch(vol, inps, refs_, keeps, seed, base)
@@ -158,6 +185,29 @@ def test_two_views_in_one_launch_are_their_own_single_view_launches(hiplib, batc
         r1, t1, m1, _ = _launch(dev(vols[v]), [inps[v]], [refs_[v]], [keeps[v]], seed, base + v)
         assert np.array_equal(m1[0], masks[v]) and np.array_equal(r1[0], ray[v]) and np.array_equal(t1[0], total[v])
     assert not np.array_equal(ray[0], ray[1])
+    goods = [_good(refs_[v], refs32[v], ("two views", v)) for v in range(2)]
+    ray, total, masks, _ = _launch(vol, inps, refs_, goods, seed, base)
+    for v in range(2):
+        pose_rule(ray[v], total[v], refs_[v], refs32[v], masks[v], ("two views", v, "conditioned"))
+
+
+# ---- what the conditioned pass is fed, for tests/test_rgba_camera.py to hold to its conditions without a GPU ----------------------
+
+def _entry(name, f16=False, **over):
+    _, ref, ref32 = _refs(name, f16, **over)
+    return [(ref, ref32, PG.keep(ref, ref32), None)]
+
+
+def _two_views_entries(batched_vol):
+    _, refs_, refs32, _ = _two_views_case(batched_vol)
+    return [(a, b, PG.keep(a, b), None) for a, b in zip(refs_, refs32)]
+
+
+# id -> a function that returns [(float64 reference, float32 reference, keep mask, None)], one entry per view
+CONDITIONED = {name: (lambda n=name: _entry(n)) for name in sorted(SC.CASES)}
+CONDITIONED.update({"posed_sr2_ert_jit_f16": lambda: _entry("posed_sr2_ert_jit", True), "default_sr1_seed_4711": lambda: _entry("default_sr1", seed=4711),
+                    "3x5": lambda: _entry("posed_sr2_ert_jit", WH=(3, 5)), "two_views_shared": lambda: _two_views_entries(False),
+                    "two_views_batched": lambda: _two_views_entries(True)})
 
 
 def test_a_camera_looking_away_from_the_box_gives_zeros(hiplib):

@@ -131,6 +131,77 @@ def test_projection_reference_default_pose_matches_the_fixed_camera(mode):
     assert np.abs(res["dpose_ray"][..., :3] - want).max() <= 1e-12 * np.abs(want).max()
 
 
+# ---- the conditioned pass of the GPU tests (pose_gpu.well_conditioned): its conditions, and that it bites -------------------------
+
+def _conditioned_cases():
+    """Everything test_gpu_pose.py and test_gpu_pose_edges.py feed to the conditioned pass: id -> a function that returns
+    [(ref, ref32, keep, row bands or None)]. The cases of GRAD_RUNS, the float16-rounded volumes among them."""
+    import pose_gpu as PG
+    import test_gpu_pose as TP
+    import test_gpu_pose_edges as TE
+
+    def grad(name, f16):
+        _, ref, ref32 = TP.grad_case(name, f16)
+        return [(ref, ref32, PG.keep(ref, ref32), None)]
+
+    cases = {"%s_%s" % (name, str(dt)[6:]): (lambda n=name, f=(dt == torch.float16): grad(n, f)) for name, dt in TP.GRAD_RUNS}
+    cases.update({"edges_" + k: v for k, v in TE.CONDITIONED.items()})
+    return cases
+
+
+CONDITIONED = _conditioned_cases()
+
+
+@pytest.mark.parametrize("case", sorted(CONDITIONED))
+def test_cases_keep_enough_well_conditioned_rays(case):
+    """The rays on which the float32 and the float64 reference agree to 1e-4 of each pose tensor's scale are at least 80 % of
+    the n > 1 rays (in every row band where the rule is applied band by band), and err32 over them is within 1e-4 of the scale:
+    the second pass of the GPU tests then bounds every ray by 4e-4 of it."""
+    import camgrad_gpu as K
+    import pose_gpu as PG
+    K.check_conditions(CONDITIONED[case](), "dpose_ray", PG.COLUMNS)
+
+
+def test_the_conditioned_rule_rejects_a_one_percent_error():
+    """all_three: one ray puts err32 at 4 % of the scale, and the rule over all rays accepts a pose gradient that is 1 % off
+    in every column of every ray. Over the well-conditioned rays it does not."""
+    import camgrad_gpu as K
+    import pose_gpu as PG
+    import test_gpu_pose as TP
+    for f16 in (False, True):
+        _, ref, ref32 = TP.grad_case("all_three", f16)
+        keep = PG.keep(ref, ref32)
+        good = PG.well_conditioned(ref, ref32, keep)
+        assert good.sum() < (keep & (ref["n"] > 1)).sum()   # there are ill-conditioned rays to leave out
+        K.mutation_check(PG.pose_rule, ref["dpose_ray"], ref32["dpose_ray"], ref, ref32, keep, good)
+
+
+def test_a_view_that_misses_the_box_has_a_zero_reference():
+    """look_at = 2 look_from: no ray meets the box, the reference marches nothing and every gradient is 0."""
+    inp = dict(_scene(), **PANNED)
+    inp["look_at"] = tuple(2.0 * np.asarray(PANNED["look_from"]))
+    for dtype in (torch.float64, torch.float32):
+        res = PR.run_case(inp, dtype=dtype)
+        assert (res["n"] == 0).all() and (res["steps"] == 0).all() and (res["rgba"] == 0).all()
+        assert (res["dpose_ray"] == 0).all() and (res["dpose"] == 0).all()
+
+
+def test_fast_path_hard_poses_see_enough_of_the_box():
+    """The premise of test_gpu_pose.py::test_fast_path_serves_a_posed_camera for its hard poses: more than a quarter of the
+    pixels of the two cameras have n > 1."""
+    import test_gpu_pose as TP
+    W, H = TP.FAST_SIZE
+    T = lambda a: torch.tensor(np.asarray(a, np.float32).astype(np.float64))
+    for name, (look_at, up, fovs) in sorted(TP.FAST_HARD_POSES.items()):
+        hit = []
+        for v in range(2):
+            fov = math.radians((fovs or (PR.FOV_DEG,) * 2)[v])
+            n = PR.ray_setup(T(TP.CAMS[v]), T(look_at or PR.ORIGIN), T(up or PR.UP_Y), fov, W, H, (40, 24, 36), 1.0)[3]
+            hit.append(float((n > 1).double().mean()))
+        print("fast path pose", name, "share of n > 1 rays %.2f / %.2f" % tuple(hit))
+        assert min(hit) > 0.25, (name, hit)
+
+
 def test_new_symbols_and_abi_version(hiplib):
     from differender_amd import _native as N
     assert N.ABI_VERSION == 9 and hiplib.dr_abi_version() == 9

@@ -89,6 +89,24 @@ def test_default_pose_columns_are_the_fixed_cameras():
     assert np.abs(res["dpose_ray"][..., :3]).max() > 0
 
 
+def _conditioned_cases():
+    import test_gpu_rgba_camera as TG
+    return TG.CONDITIONED
+
+
+CONDITIONED = _conditioned_cases()
+
+
+@pytest.mark.parametrize("case", sorted(CONDITIONED))
+def test_cases_keep_enough_well_conditioned_rays(case):
+    """What test_gpu_rgba_camera.py feeds to the conditioned pass (pose_gpu.well_conditioned), held to its conditions without a
+    GPU: the rays on which the float32 and the float64 reference agree to 1e-4 of each pose tensor's scale are at least 80 %
+    of the n > 1 rays, and err32 over them is within 1e-4 of the scale."""
+    import camgrad_gpu as K
+    import pose_gpu as PG
+    K.check_conditions(CONDITIONED[case](), "dpose_ray", PG.COLUMNS, lit=False)   # (D16: no lighting, no kinks)
+
+
 # --- 2. the C ABI -----------------------------------------------------------------------------------------------------------
 
 def test_header_library_and_signatures_agree(hiplib):
