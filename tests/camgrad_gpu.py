@@ -47,38 +47,30 @@ LOOK_FROM = (("look_from", slice(0, 3)),)
 
 def _shading(vol, look_from, ref, dtype):
     """The lighting of every live sample of the reference's march, evaluated in `dtype` on that reference's own ray buffers
-    (the arithmetic of make_autograd_golden.raycast): per sample (S, P) the norm of the central differences, the unit normal
-    (S, P, 3), n.l, max(r.v, 0), L before min(1, .), and `lit`: live and not flat (D1)."""
+    (make_autograd_golden's sample positions, trilinear sample and lighting literals; the outputs are this diagnostic's own): per
+    sample (S, P) the norm of the central differences, the unit normal (S, P, 3), n.l, max(r.v, 0), L before min(1, .), and `lit`: live and not flat (D1)."""
     import make_autograd_golden as G
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dtype)
     v, cam = T(vol), T(look_from)
     e, x, r = T(ref["entry"]).reshape(-1), T(ref["exit"]).reshape(-1), T(ref["rays"]).reshape(-1, 3)
     n, steps = torch.from_numpy(ref["n"].reshape(-1)).long(), torch.from_numpy(ref["steps"].reshape(-1)).long()
-    nf = n.to(dtype)
-    t0 = e + 0.5 * (x - e) / nf.clamp(min=1.0)
-    light = cam + torch.tensor([0.0, 1.0, 0.0], dtype=dtype)
+    light = G.light_position(cam)
     out = {k: [] for k in ("lit", "norm", "nrm", "ndl", "rdv", "L")}
-    old = G.F64
-    G.F64 = dtype   # the transliteration reads its float type at call time
-    try:
-        for s in range(int(steps.max()) if len(steps) else 0):
-            live = (s < steps) & (n > 1)
-            pos = cam[None] + G.mix(t0, x, float(s) / (nf - 1.0).clamp(min=1.0))[:, None] * r
-            pos = torch.where(live[:, None], pos, torch.zeros_like(pos))
-            g = torch.stack([G.sample_volume_trilinear(v, pos + ax) - G.sample_volume_trilinear(v, pos - ax)
-                             for ax in 1e-3 * torch.eye(3, dtype=dtype)], 1)
-            norm = g.norm(dim=1)
-            lit = live & (norm > 0)
-            nrm = g / torch.where(lit, norm, torch.ones_like(norm))[:, None]
-            ld = pos - light[None]
-            ld = ld / ld.norm(dim=1, keepdim=True)
-            ndl = (nrm * ld).sum(1)
-            rdv = ((ld - 2.0 * ndl[:, None] * nrm) * (-r)).sum(1).clamp(min=0.0)
-            L = 0.8 * ndl.clamp(min=0.0) + 0.3 * rdv ** 32 + 0.4
-            for k, t in (("lit", lit), ("norm", norm), ("nrm", nrm), ("ndl", ndl), ("rdv", rdv), ("L", L)):
-                out[k].append(t if k == "lit" else t.double())
-    finally:
-        G.F64 = old
+    for s in range(int(steps.max()) if len(steps) else 0):
+        live = (s < steps) & (n > 1)
+        pos = G.sample_pos(cam, e, x, r, n, s, live)
+        g = torch.stack([G.sample_volume_trilinear(v, pos + ax) - G.sample_volume_trilinear(v, pos - ax)
+                         for ax in 1e-3 * torch.eye(3, dtype=dtype)], 1)
+        norm = g.norm(dim=1)
+        lit = live & (norm > 0)
+        nrm = g / torch.where(lit, norm, torch.ones_like(norm))[:, None]
+        ld = pos - light[None]
+        ld = ld / ld.norm(dim=1, keepdim=True)
+        ndl = (nrm * ld).sum(1)
+        rdv = ((ld - 2.0 * ndl[:, None] * nrm) * (-r)).sum(1).clamp(min=0.0)
+        L = G.DIFFUSE * ndl.clamp(min=0.0) + G.SPECULAR * rdv ** G.SHININESS + G.AMBIENT
+        for k, t in (("lit", lit), ("norm", norm), ("nrm", nrm), ("ndl", ndl), ("rdv", rdv), ("L", L)):
+            out[k].append(t if k == "lit" else t.double())
     return {k: torch.stack(t) for k, t in out.items()} if out["lit"] else None
 
 
@@ -96,6 +88,7 @@ def near_lighting_kink(vol, look_from, ref):
     2.5e-8 and its 99th percentile at 1.3e-7 ... 5.7e-7 over the cases here, around sqrt(3) 2 ulp = 2.1e-7.
     max(r.v, 0)^32 is no kink (31 continuous derivatives at 0); flat samples (D1) have no normal.
     vol: the volume the kernel reads; ref: entry, exit, rays, n, steps of the float64 reference. -> mask (W, H)."""
+    import make_autograd_golden as G
     W, H = ref["n"].shape
     a = _shading(vol, look_from, ref, torch.float64)
     if a is None:
@@ -103,7 +96,8 @@ def near_lighting_kink(vol, look_from, ref):
     top = np.float32(max(1.0, float(np.abs(vol).max())))
     ulp = float(top - np.nextafter(top, np.float32(0.0)))
     dn = math.sqrt(3.0) * 2.0 * ulp / torch.where(a["lit"], a["norm"], torch.ones_like(a["norm"]))
-    near = a["lit"] & ((a["ndl"].abs() <= dn) | ((a["L"] - 1.0).abs() <= (0.8 + 38.4 * a["rdv"] ** 31) * dn))
+    slope = G.DIFFUSE + G.SPECULAR * G.SHININESS * 4.0 * a["rdv"] ** (G.SHININESS - 1.0)
+    near = a["lit"] & ((a["ndl"].abs() <= dn) | ((a["L"] - 1.0).abs() <= slope * dn))
     return near.any(0).numpy().reshape(W, H)
 
 

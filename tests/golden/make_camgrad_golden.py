@@ -3,7 +3,8 @@
 
 A float64 PyTorch transliteration of the reference's ray setup -- compute_entry_exit + get_ray_direction +
 get_entry_exit_points (differender/volume_raycaster.py:221-259, 127-151, 28-53) -- feeding `raycast` of
-make_autograd_golden.py (imported, not copied). torch.autograd differentiates the whole program w.r.t. the camera; nothing
+make_autograd_golden.py under that file's driver `render_view` (imported, not copied), which takes one camera row per ray as
+it takes one camera. torch.autograd differentiates the whole program w.r.t. the camera; nothing
 is derived by hand. Frozen, as in any reverse-mode AD of a program with branches: the sample count n (a floor), the jitter
 draw u (recomputed from the counter hash the oracle and the kernels share), the slab faces max/min pick, and everything
 make_autograd_golden.py freezes.
@@ -85,22 +86,6 @@ def ray_setup(cam, W, H, vol_shape, sr, fov_deg=30.0, near=0.1, jitter_seed=0, v
     return entry, tmax, vd, n.long()
 
 
-class _PerRayCam:
-    """`raycast` takes one camera; this hands it one row per ray: cam[None, :] and the light position both stay (P, 3)."""
-
-    def __init__(self, c):
-        self.c = c
-
-    def __getitem__(self, idx):
-        return self.c
-
-    def __add__(self, o):
-        return _PerRayCam(self.c + o)
-
-    def __rsub__(self, o):
-        return o - self.c
-
-
 CASES = {
     # name: (volume shape, image, R, sampling rate, max_samples, TF kind, camera, jitter seed[, volume kind])
     "a_orbit_sr1": ((16, 16, 16), (16, 16), 8, 1.0, 4096, "thin", ("orbit", 0.8), 0),
@@ -178,24 +163,19 @@ def run_case(inp, dtype=torch.float64, pixels=None):
     cam_pp = T(inp["cam"]).expand(P, 3).clone().requires_grad_(True)
     vshape = inp["vol"].shape
     e, x, r, n = ray_setup(cam_pp, W, H, vshape, float(inp["sr"]), jitter_seed=int(inp["jitter_seed"]), view=int(inp["view"]))
-    live = n > 1
-    if pixels is not None:
-        live &= torch.zeros_like(live).index_fill_(0, torch.as_tensor(pixels), True)
-    sel = torch.nonzero(live)[:, 0]
-    old = G.F64
-    G.F64 = dtype   # the transliteration reads its float type at call time
-    try:
-        out_sel, cnt = G.raycast(T(inp["vol"]), T(inp["tf"]), _PerRayCam(cam_pp[sel]), e[sel], x[sel], r[sel], n[sel],
-                                 int(inp["max_samples"]), float(inp["sr"]))
-    finally:
-        G.F64 = old
-    (out_sel * T(inp["grad_out"]).reshape(P, 4)[sel]).sum().backward()
-    out = np.zeros((P, 4)); out[sel.numpy()] = out_sel.detach().double().numpy()
-    steps = np.zeros(P, np.int32); steps[sel.numpy()] = cnt.numpy()
-    d_ray = cam_pp.grad.double().numpy()
-    return dict(entry=e.detach().double().numpy().reshape(W, H), exit=x.detach().double().numpy().reshape(W, H),
+
+    def march_rays(sel):
+        out, cnt = G.raycast(T(inp["vol"]), T(inp["tf"]), cam_pp[sel], e[sel], x[sel], r[sel], n[sel], int(inp["max_samples"]),
+                             float(inp["sr"]))
+        return out, dict(steps=cnt.int())
+
+    loss, res = G.render_view((W, H), n, pixels, T(inp["grad_out"]).reshape(P, 4), march_rays)
+    if torch.is_tensor(loss):
+        loss.backward()
+    d_ray = G.grad_or_zero(cam_pp)
+    return dict(res, entry=e.detach().double().numpy().reshape(W, H), exit=x.detach().double().numpy().reshape(W, H),
                 rays=r.detach().double().numpy().reshape(W, H, 3), n=n.numpy().astype(np.int32).reshape(W, H),
-                rgba=out.reshape(W, H, 4), steps=steps.reshape(W, H), dcam_ray=d_ray.reshape(W, H, 3), dcam=d_ray.sum(0))
+                dcam_ray=d_ray.reshape(W, H, 3), dcam=d_ray.sum(0))
 
 
 def sample_stats(inp, res):
@@ -206,13 +186,10 @@ def sample_stats(inp, res):
     vol, cam = T(inp["vol"]), T(inp["cam"])
     e, x, r = T(res["entry"]).reshape(-1), T(res["exit"]).reshape(-1), T(res["rays"]).reshape(-1, 3)
     n, steps = torch.from_numpy(res["n"].reshape(-1)).long(), torch.from_numpy(res["steps"].reshape(-1)).long()
-    nf = n.double()
     flat, outside = torch.zeros_like(n), torch.zeros_like(n)
     for s in range(int(steps.max())):
         live = (s < steps) & (n > 1)
-        t0 = e + 0.5 * (x - e) / nf.clamp(min=1.0)
-        pos = cam[None] + G.mix(t0, x, s / (nf - 1.0).clamp(min=1.0))[:, None] * r
-        pos = torch.where(live[:, None], pos, torch.zeros_like(pos))
+        pos = G.sample_pos(cam, e, x, r, n, s, live)
         I = G.sample_volume_trilinear(vol, pos)
         flat += live & G.get_volume_normal(vol, pos)[1]
         outside += live & ((I < 0) | (I > 1))

@@ -2,8 +2,9 @@
 
 A PyTorch transliteration of the program dr_march_lit_fwd specifies -- `raycast` of tests/golden/make_autograd_golden.py with
 its lighting literals (VR.py:91-95, 281-299) replaced by ten parameters per view: the light's world position p and colour lc,
-the ambient, diffuse and specular weights ka, kd, ks and the shininess sh. The trilinear sample, the normal and the TF lookup
-are imported from that file, not copied. The backward is torch.autograd's; nothing is derived by hand. Every ray gets its own
+the ambient, diffuse and specular weights ka, kd, ks and the shininess sh. The sample loop (`march`), the trilinear sample, the
+normal, the TF lookup and the per-view driver (`render_view`) are imported from that file, not copied; `_shade`, the lighting
+under test, is this file's own. The backward is torch.autograd's; nothing is derived by hand. Every ray gets its own
 leaf copy of its view's ten parameters, so one run holds each ray's contribution to d_light as well as the views' totals.
 
 Branch predicates are frozen as in make_autograd_golden.py: max(x, 0) passes the gradient iff 0 < x, min(1, L) iff not 1 < L.
@@ -43,7 +44,8 @@ def reference_light(cam):
     """The reference's lighting for the cameras cam (views, 3) as (views, 10) rows: a white light at look_from + (0, 1, 0),
     0.4, 0.8, 0.3, 32."""
     cam = np.asarray(cam, np.float64).reshape(-1, 3)
-    return np.concatenate([cam + np.array([0.0, 1.0, 0.0]), np.tile([1.0, 1.0, 1.0, 0.4, 0.8, 0.3, 32.0], (cam.shape[0], 1))], 1)
+    return np.concatenate([cam + np.array(G.LIGHT_OFFSET), np.tile([1.0, 1.0, 1.0, G.AMBIENT, G.DIFFUSE, G.SPECULAR, G.SHININESS],
+                                                                    (cam.shape[0], 1))], 1)
 
 
 def _shade(vol, tf, pos, rays, light, sampling_rate):
@@ -67,71 +69,39 @@ def _shade(vol, tf, pos, rays, light, sampling_rate):
     return color, opacity, kd * ndl + ks * spec_pow + ka, flat, m, q
 
 
-def _sample_pos(cam, entry, exit_, rays, n, nf, s, active):
-    tmin = entry + 0.5 * (exit_ - entry) / nf
-    frac = torch.where(n > 1, float(s) / torch.clamp(nf - 1.0, min=1.0), torch.zeros_like(nf))
-    pos = cam[None, :] + G.mix(tmin, exit_, frac)[:, None] * rays
-    return torch.where(active[:, None], pos, torch.zeros_like(pos))
+def _march_lit(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampling_rate, nondiff, clamp):
+    """G.march with _shade's sample. Its per-ray counts: "kink" and "over" (Lraw > 1) over the live samples, or with nondiff
+    "band" (alpha within SKIP_BAND of SKIP) over the live samples and "bright" (Lraw > 1) over the composited ones."""
+    lc = light[:, 3:6]
+
+    def sample(pos):
+        color, opacity, Lraw, flat, m, q = _shade(vol, tf, pos, rays, light, sampling_rate)
+        L = torch.where(Lraw > 1.0, torch.ones_like(Lraw), Lraw) if clamp else Lraw
+        shaded = torch.cat([(L * opacity)[:, None] * color[:, :3] * lc, opacity[:, None]], dim=1)
+        if nondiff:
+            return shaded, color[:, 3], dict(band=(color[:, 3] - SKIP).abs() < SKIP_BAND, bright=(color[:, 3] > SKIP) & (Lraw > 1.0))
+        kink = ((Lraw - 1.0).abs() < KINK) | (~flat & ((m.abs() < KINK) | (q.abs() < KINK)))
+        return shaded, color[:, 3], dict(kink=kink, over=Lraw > 1.0)
+
+    return G.march(cam, entry, exit_, rays, n, max_samples, nondiff, sample)
 
 
 def raycast_lit(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampling_rate, clamp=True):
     """The lit march for P rays of one view. light (P, 10): each ray's own copy of the parameters.
     Returns the (P, 4) pixels, the live-sample counts, the rays' `near` flags and their counts of samples with Lraw > 1."""
-    dt = entry.dtype
-    P = entry.shape[0]
-    tape = torch.zeros((P, 4), dtype=dt)
-    count = torch.zeros(P, dtype=torch.long)
-    near = torch.zeros(P, dtype=torch.bool)
-    clamped = torch.zeros(P, dtype=torch.long)
-    lc = light[:, 3:6]
-    nf = n.to(dt)
-    for s in range(int(n.max())):
-        active = ((s < n) & (tape[:, 3] < 0.99) & (s < max_samples)).detach()
-        if not bool(active.any()):
-            continue
-        pos = _sample_pos(cam, entry, exit_, rays, n, nf, s, active)
-        color, opacity, Lraw, flat, m, q = _shade(vol, tf, pos, rays, light, sampling_rate)
-        L = torch.where(Lraw > 1.0, torch.ones_like(Lraw), Lraw) if clamp else Lraw
-        shaded = torch.cat([(L * opacity)[:, None] * color[:, :3] * lc, opacity[:, None]], dim=1)
-        new = (1.0 - tape[:, 3:4]) * shaded + tape
-        tape = torch.where(active[:, None], new, tape)
-        count = count + active.long()
-        kink = ((Lraw - 1.0).abs() < KINK) | (~flat & ((m.abs() < KINK) | (q.abs() < KINK)))
-        near = near | (active & kink.detach())
-        clamped = clamped + (active & (Lraw > 1.0).detach()).long()
-    return tape, count, near, clamped
+    out, _, count, c = _march_lit(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampling_rate, False, clamp)
+    return out, count, c["kink"] > 0, c["over"]
 
 
 def raycast_lit_nondiff(vol, tf, cam, light, entry, exit_, rays, n, sampling_rate):
-    """The non-differentiable lit march for P rays of one view, forward only (VR.py:308-361 with light (P, 10) for its literals).
+    """The non-differentiable lit march for P rays of one view, forward only (VR.py:308-361 with light (P, 10) for its literals;
+    the lighting is not clamped, :345).
     Returns the (P, 4) pixels min(1, .), the pixels before that clamp, the live-sample counts (every active sample, composited or
     not), the rays' `near` flags (a live sample's alpha within SKIP_BAND of the skip threshold) and, for the tests of the scenes,
     the rays' counts of skipped samples and of composited samples with Lraw > 1."""
-    dt = entry.dtype
-    P = entry.shape[0]
-    tape = torch.zeros((P, 4), dtype=dt)
-    count = torch.zeros(P, dtype=torch.long)
-    near = torch.zeros(P, dtype=torch.bool)
-    skipped = torch.zeros(P, dtype=torch.long)
-    bright = torch.zeros(P, dtype=torch.long)
-    lc = light[:, 3:6]
-    nf = n.to(dt)
     with torch.no_grad():
-        for s in range(int(n.max())):
-            active = (s < n) & (tape[:, 3] < 0.99)                       # no max_samples clip (VR.py:317-318)
-            if not bool(active.any()):
-                continue
-            pos = _sample_pos(cam, entry, exit_, rays, n, nf, s, active)
-            color, opacity, Lraw, _, _, _ = _shade(vol, tf, pos, rays, light, sampling_rate)
-            shade = active & (color[:, 3] > SKIP)                        # VR.py:334
-            shaded = torch.cat([(Lraw * opacity)[:, None] * color[:, :3] * lc, opacity[:, None]], dim=1)   # not clamped (:345)
-            new = (1.0 - tape[:, 3:4]) * shaded + tape
-            tape = torch.where(shade[:, None], new, tape)
-            count = count + active.long()
-            near = near | (active & ((color[:, 3] - SKIP).abs() < SKIP_BAND))
-            skipped = skipped + (active & ~shade).long()
-            bright = bright + (shade & (Lraw > 1.0)).long()
-    return torch.clamp(tape, max=1.0), tape, count, near, skipped, bright
+        out, raw, count, c = _march_lit(vol, tf, cam, light, entry, exit_, rays, n, None, sampling_rate, True, False)
+    return out, raw, count, c["band"] > 0, c["skipped"], c["bright"]
 
 
 def run(inp, light, dtype=torch.float64, want_grad=True, pixels=None, mode="diff"):
@@ -149,47 +119,28 @@ def run(inp, light, dtype=torch.float64, want_grad=True, pixels=None, mode="diff
     V, W, H = np.asarray(inp["n"]).shape
     vol, tf = T(inp["vol"]).requires_grad_(want_grad), T(inp["tf"]).requires_grad_(want_grad)
     assert vol.ndim in (3, 4) and tf.ndim in (2, 3) and (vol.ndim == 3 or vol.shape[0] == V) and (tf.ndim == 2 or tf.shape[0] == V)
-    rgba = np.zeros((V, W * H, 4)); raw = np.zeros((V, W * H, 4))
-    ints = {k: np.zeros((V, W * H), np.int32) for k in (("steps", "skipped", "bright") if nondiff else ("steps", "clamped"))}
-    near = np.zeros((V, W * H), bool)
-    dray = np.zeros((V, W * H, 10))
-    old = G.F64
-    G.F64 = dtype   # the imported helpers read their float type at call time
-    try:
-        for v in range(V):
-            n = torch.from_numpy(np.asarray(inp["n"][v]).reshape(-1)).long()
-            live = n > 1
-            if pixels is not None:
-                live &= torch.from_numpy(np.asarray(pixels[v]).reshape(-1))
-            sel = torch.nonzero(live)[:, 0]
-            if sel.numel() == 0:
-                continue
-            leaf = T(light[v]).expand(sel.numel(), 10).clone().requires_grad_(want_grad)
-            args = (vol if vol.ndim == 3 else vol[v], tf if tf.ndim == 2 else tf[v], T(inp["cam"][v]), leaf,
-                    T(inp["entry"][v]).reshape(-1)[sel], T(inp["exit"][v]).reshape(-1)[sel], T(inp["rays"][v]).reshape(-1, 3)[sel],
-                    n[sel])
-            if nondiff:
-                out, pre, cnt, nr, sk, br = raycast_lit_nondiff(*args, float(inp["sr"]))
-                raw[v, sel.numpy()] = pre.double().numpy()
-                counts = dict(steps=cnt, skipped=sk, bright=br)
-            else:
-                out, cnt, nr, cl = raycast_lit(*args, int(inp["max_samples"]), float(inp["sr"]))
-                counts = dict(steps=cnt, clamped=cl)
-            rgba[v, sel.numpy()] = out.detach().double().numpy()
-            near[v, sel.numpy()] = nr.numpy()
-            for k, c in counts.items():
-                ints[k][v, sel.numpy()] = c.numpy()
-            if want_grad:
-                (out * T(inp["grad_out"][v]).reshape(-1, 4)[sel]).sum().backward()
-                dray[v, sel.numpy()] = leaf.grad.double().numpy()
-    finally:
-        G.F64 = old
-    res = dict(rgba=rgba.reshape(V, W, H, 4), near=near.reshape(V, W, H), **{k: a.reshape(V, W, H) for k, a in ints.items()})
-    if nondiff:
-        res["raw"] = raw.reshape(V, W, H, 4)
-    if want_grad:
-        zero = lambda t: np.zeros(tuple(t.shape)) if t.grad is None else t.grad.double().numpy()
-        res.update(dvol=zero(vol), dtf=zero(tf), dlight_ray=dray.reshape(V, W, H, 10),
-                   dlight=dray.sum(1))
-    return res
+    views = []
+    for v in range(V):
+        leaf = T(light[v]).expand(W * H, 10).clone().requires_grad_(want_grad)   # every ray its own copy
 
+        def march_rays(sel):
+            args = (vol if vol.ndim == 3 else vol[v], tf if tf.ndim == 2 else tf[v], T(inp["cam"][v]), leaf[sel],
+                    T(inp["entry"][v]).reshape(-1)[sel], T(inp["exit"][v]).reshape(-1)[sel], T(inp["rays"][v]).reshape(-1, 3)[sel],
+                    torch.from_numpy(np.asarray(inp["n"][v]).reshape(-1)).long()[sel])
+            if nondiff:
+                out, raw, cnt, nr, sk, br = raycast_lit_nondiff(*args, float(inp["sr"]))
+                return out, dict(raw=raw, steps=cnt.int(), near=nr, skipped=sk.int(), bright=br.int())
+            out, cnt, nr, cl = raycast_lit(*args, int(inp["max_samples"]), float(inp["sr"]))
+            return out, dict(steps=cnt.int(), near=nr, clamped=cl.int())
+
+        loss, res = G.render_view((W, H), np.asarray(inp["n"][v]), None if pixels is None else np.asarray(pixels[v]),
+                                  T(inp["grad_out"][v]).reshape(-1, 4) if want_grad else None, march_rays)
+        if torch.is_tensor(loss):
+            loss.backward()
+        if want_grad:
+            res["dlight_ray"] = G.grad_or_zero(leaf).reshape(W, H, 10)
+        views.append(res)
+    res = {k: np.stack([r[k] for r in views]) for k in views[0]}
+    if want_grad:
+        res.update(dvol=G.grad_or_zero(vol), dtf=G.grad_or_zero(tf), dlight=res["dlight_ray"].reshape(V, W * H, 10).sum(1))
+    return res

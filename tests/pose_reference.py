@@ -2,8 +2,9 @@
 
 A PyTorch transliteration of the pose ray setup -- view_dir = normalize(look_at - look_from), right = normalize(view_dir x up),
 up' = normalize(right x view_dir), near_h = 2 tan(fov) near, near_w = near_h img_W / H, then the slab clipping, sample count and
-jitter of tests/golden/make_camgrad_golden.ray_setup -- feeding `raycast` of make_autograd_golden.py and `project` of
-proj_reference.py (imported, not copied). torch.autograd differentiates the whole program w.r.t. the ten pose parameters;
+jitter of tests/golden/make_camgrad_golden.ray_setup -- feeding `raycast` of make_autograd_golden.py, under that file's driver
+`render_view`, and `project` of proj_reference.py (imported, not copied). run_march is the driver for any march of the posed
+rays; tests/rgba_pose_reference.py uses it too. torch.autograd differentiates the whole program w.r.t. the ten pose parameters;
 nothing is derived by hand. Each ray gets its own leaf copy of the pose, so a run holds every ray's contribution as well as the
 total. The fov leaf is in RADIANS, as the C ABI's fov_v and its d_pose column 9 are.
 """
@@ -83,42 +84,37 @@ def _leaves(inp, dtype, P):
 
 
 def _result(W, H, e, x, r, n, leaves):
-    d_ray = torch.cat([leaves[0].grad, leaves[1].grad, leaves[2].grad, leaves[3].grad[:, None]], 1).double().numpy()
+    d_ray = np.concatenate([G.grad_or_zero(leaf).reshape(W * H, -1) for leaf in leaves], 1)   # (zeros: a leaf no ray depends on)
     return dict(entry=e.detach().double().numpy().reshape(W, H), exit=x.detach().double().numpy().reshape(W, H),
                 rays=r.detach().double().numpy().reshape(W, H, 3), n=n.numpy().astype(np.int32).reshape(W, H),
                 dpose_ray=d_ray.reshape(W, H, 10), dpose=d_ray.sum(0))
 
 
-def run_case(inp, dtype=torch.float64, pixels=None):
-    """Per-ray and total d (look_from, look_at, up, fov_rad) of sum(raycast(...) * grad_out), the forward in `dtype`.
-    inp: vol, tf, look_from, grad_out (W,H,4), sr, max_samples, jitter_seed, view; optional look_at, up, fov_rad."""
+def run_march(inp, dtype, pixels, march):
+    """run_case for any march of the rays: march(T, cam, entry, exit, rays, n), with T the conversion to `dtype` and one camera
+    row per ray, returns their pixels (P, 4) and live-sample counts."""
     W, H = inp["grad_out"].shape[:2]
     P = W * H
     T, lf, la, up, fov = _leaves(inp, dtype, P)
-    e, x, r, n = ray_setup(lf, la, up, fov, W, H, inp["vol"].shape, float(inp["sr"]), jitter_seed=int(inp["jitter_seed"]),
+    e, x, r, n = ray_setup(lf, la, up, fov, W, H, inp["vol"].shape[-3:], float(inp["sr"]), jitter_seed=int(inp["jitter_seed"]),
                            view=int(inp["view"]))
-    live = n > 1
-    if pixels is not None:
-        live &= torch.zeros_like(live).index_fill_(0, torch.as_tensor(pixels), True)
-    sel = torch.nonzero(live)[:, 0]
-    old = G.F64
-    G.F64 = dtype   # the transliteration reads its float type at call time
-    try:
-        out_sel, cnt = G.raycast(T(inp["vol"]), T(inp["tf"]), CG._PerRayCam(lf[sel]), e[sel], x[sel], r[sel], n[sel],
-                                 int(inp["max_samples"]), float(inp["sr"]))
-    finally:
-        G.F64 = old
-    leaves = (lf, la, up, fov)
-    if out_sel.requires_grad:
-        (out_sel * T(inp["grad_out"]).reshape(P, 4)[sel]).sum().backward()
-    for leaf in leaves:   # (no ray marched: a view that misses the box)
-        if leaf.grad is None:
-            leaf.grad = torch.zeros_like(leaf)
-    res = _result(W, H, e, x, r, n, leaves)
-    steps = np.zeros(P, np.int32); steps[sel.numpy()] = cnt.numpy()
-    out = np.zeros((P, 4)); out[sel.numpy()] = out_sel.detach().double().numpy()
-    res.update(steps=steps.reshape(W, H), rgba=out.reshape(W, H, 4))
-    return res
+
+    def march_rays(sel):
+        out, cnt = march(T, lf[sel], e[sel], x[sel], r[sel], n[sel])
+        return out, dict(steps=cnt.int())
+
+    loss, res = G.render_view((W, H), n, pixels, T(inp["grad_out"]).reshape(P, 4), march_rays)
+    if torch.is_tensor(loss):   # (else no ray marched: a view that misses the box)
+        loss.backward()
+    return dict(res, **_result(W, H, e, x, r, n, (lf, la, up, fov)))
+
+
+def run_case(inp, dtype=torch.float64, pixels=None):
+    """Per-ray and total d (look_from, look_at, up, fov_rad) of sum(raycast(...) * grad_out), the forward in `dtype`.
+    inp: vol, tf, look_from, grad_out (W,H,4), sr, max_samples, jitter_seed, view; optional look_at, up, fov_rad.
+    pixels: flat indices of the rays to march (default all)."""
+    return run_march(inp, dtype, pixels, lambda T, cam, e, x, r, n: G.raycast(
+        T(inp["vol"]), T(inp["tf"]), cam, e, x, r, n, int(inp["max_samples"]), float(inp["sr"])))
 
 
 def run_projection(inp, mode, dtype=torch.float64, arg_max=None):

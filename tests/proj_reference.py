@@ -27,15 +27,6 @@ import make_autograd_golden as G  # noqa: E402
 import make_camgrad_golden as CG  # noqa: E402
 
 
-def trilinear(vol, pos):
-    old = G.F64
-    G.F64 = vol.dtype   # the helper reads its float type at call time
-    try:
-        return G.sample_volume_trilinear(vol, pos)
-    finally:
-        G.F64 = old
-
-
 def project(vol, cam, entry, exit_, rays, n, max_samples, mode):
     """vol (VX, VY, VZ); cam (3,) or (P, 3); entry, exit_ (P,), rays (P, 3), n (P,) integer. Returns out (P,) and, for "max",
     the argmax sample index (P,) int64 (-1: no sample); None for "sum"."""
@@ -55,7 +46,7 @@ def project(vol, cam, entry, exit_, rays, n, max_samples, mode):
         f = s / (nf[idx] - 1.0)
         t = G.mix(t0[idx], exit_[idx], f)
         pos = cam[idx] + t[:, None] * rays[idx]
-        mu = torch.zeros(P, dtype=dt).index_put((idx,), trilinear(vol, pos))
+        mu = torch.zeros(P, dtype=dt).index_put((idx,), G.sample_volume_trilinear(vol, pos))
         live = torch.zeros(P, dtype=torch.bool).index_fill_(0, idx, True)
         if mode == "sum":
             acc = acc + mu
@@ -89,7 +80,7 @@ def sample_at(vol, cam, entry, exit_, rays, n, s):
     f = s[idx].to(dt) / (nf - 1.0)
     t = G.mix(t0, exit_[idx], f)
     pos = cam[idx] + t[:, None] * rays[idx]
-    return torch.zeros(P, dtype=dt).index_put((idx,), trilinear(vol, pos))
+    return torch.zeros(P, dtype=dt).index_put((idx,), G.sample_volume_trilinear(vol, pos))
 
 
 # ---- which path the windowed SUM backward takes (a model of its decisions only, to choose test cases) ----------------------------

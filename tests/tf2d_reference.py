@@ -1,7 +1,8 @@
 """Float64 (or float32) PyTorch transliteration of the march with a 2-D (value, gradient-magnitude) transfer function, DESIGN.md D12.
 
-The 1-D program of tests/golden/make_autograd_golden.py -- the reference's `raycast` + `get_final_image`, whose helpers are
-imported here, not copied -- with one change, the classification:
+The 1-D program of tests/golden/make_autograd_golden.py -- the reference's `raycast` + `get_final_image`: its sample loop
+(`march`), its lighting (`fixed_lighting`), its helpers and its per-view driver (`render_view`) are imported here, not copied --
+with one change, the classification:
     I = trilinear(pos); (dx, dy, dz) = the six normal taps (delta 1e-3); u = |(dx, dy, dz)| * g_scale
     xv = I (RV - 1), xg = u (RG - 1); low_high_frac and the index clamp on each axis
     rgba = mix(mix(T[v0][g0], T[v1][g0], fv), mix(T[v0][g1], T[v1][g1], fv), fg)
@@ -20,15 +21,6 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_autograd_golden as G  # noqa: E402
 
 
-def _trilinear(vol, pos, dtype):
-    old = G.F64
-    G.F64 = dtype   # the helpers read their float type at call time
-    try:
-        return G.sample_volume_trilinear(vol, pos)
-    finally:
-        G.F64 = old
-
-
 def taps(vol, pos):
     """(dx, dy, dz) (P, 3) of the shading normal, get_volume_normal's central differences."""
     dt = vol.dtype
@@ -37,7 +29,7 @@ def taps(vol, pos):
     for axis in range(3):
         e = torch.zeros(3, dtype=dt)
         e[axis] = d
-        out.append(_trilinear(vol, pos + e, dt) - _trilinear(vol, pos - e, dt))
+        out.append(G.sample_volume_trilinear(vol, pos + e) - G.sample_volume_trilinear(vol, pos - e))
     return torch.stack(out, dim=1)
 
 
@@ -55,59 +47,29 @@ def classify_2d(tf2d, intensity, u):
 
 
 def raycast_tf2d(vol, tf2d, g_scale, cam, entry, exit_, rays, n, max_samples, sampling_rate, nondiff=False):
-    """G.raycast with the 2-D classification, for all pixels at once (one view). Returns (P, 4), the live-sample counts,
-    a mask of the rays with a live sample whose alpha lies within 1e-5 of 1e-3, and the per-ray count of live flat samples
-    (|grad| = 0 exactly).
+    """G.march with G.raycast's sample under the 2-D classification, for all pixels at once (one view). Returns (P, 4), the
+    live-sample counts, a mask of the rays with a live sample whose alpha lies within 1e-5 of 1e-3, and the per-ray count of
+    live flat samples (|grad| = 0 exactly).
     nondiff: the non-differentiable march (VR.py:308-361) -- no max_samples clip, samples with alpha <= 1e-3 are counted but
     not composited, unclamped lighting, the result clamped to <= 1."""
-    dt = vol.dtype
-    P = entry.shape[0]
-    tape = torch.zeros((P, 4), dtype=dt)
-    count = torch.zeros(P, dtype=torch.long)
-    near = torch.zeros(P, dtype=torch.bool)
-    nflat = torch.zeros(P, dtype=torch.long)
-    ambient, diffuse_k, specular_k, shininess = 0.4, 0.8, 0.3, 32.0
-    light_pos = cam + torch.tensor([0.0, 1.0, 0.0], dtype=dt)
-    nf = n.to(dt)
-    for s in range(int(n.max()) if P else 0):
-        active = ((s < n) & (tape[:, 3] < 0.99) & (nondiff or s < max_samples)).detach()
-        if not bool(active.any()):
-            continue
-        ray_len = exit_ - entry
-        tmin = entry + 0.5 * ray_len / nf
-        frac = torch.where(n > 1, float(s) / torch.clamp(nf - 1.0, min=1.0), torch.zeros_like(nf))
-        pos = cam[None, :] + G.mix(tmin, exit_, frac)[:, None] * rays
-        pos = torch.where(active[:, None], pos, torch.zeros_like(pos))
-        intensity = _trilinear(vol, pos, dt)
+    light_pos = G.light_position(cam)
+
+    def sample(pos):
+        intensity = G.sample_volume_trilinear(vol, pos)
         g = taps(vol, pos)
         n2 = (g * g).sum(1)
         flat = (n2 == 0).detach()
         gnorm = torch.where(flat, torch.zeros_like(n2), torch.sqrt(torch.where(flat, torch.ones_like(n2), n2)))
         normal = torch.where(flat[:, None], torch.zeros_like(g), g / torch.where(flat, torch.ones_like(gnorm), gnorm)[:, None])
-        u = gnorm * g_scale
-        sample_color = classify_2d(tf2d, intensity, u)
+        sample_color = classify_2d(tf2d, intensity, gnorm * g_scale)
         opacity = 1.0 - torch.pow(1.0 - sample_color[:, 3], 1.0 / sampling_rate)
-        ld = pos - light_pos[None, :]
-        light_dir = ld / ld.norm(dim=1, keepdim=True)
-        ndl_raw = (normal * light_dir).sum(1)
-        n_dot_l = torch.where(ndl_raw > 0, ndl_raw, torch.zeros_like(ndl_raw))
-        r = light_dir - 2.0 * (normal * light_dir).sum(1, keepdim=True) * normal
-        rdv_raw = (r * (-rays)).sum(1)
-        r_dot_v = torch.where(rdv_raw > 0, rdv_raw, torch.zeros_like(rdv_raw))
-        r_dot_v = torch.where(flat, torch.zeros_like(r_dot_v), r_dot_v)
-        specular = specular_k * torch.pow(r_dot_v, shininess)
-        Lraw = diffuse_k * n_dot_l + specular + ambient
+        Lraw = G.fixed_lighting(pos, normal, flat, rays, light_pos)
         L = Lraw if nondiff else torch.where(Lraw > 1.0, torch.ones_like(Lraw), Lraw)
         shaded = torch.cat([(L * opacity)[:, None] * sample_color[:, :3], opacity[:, None]], dim=1)
-        new = (1.0 - tape[:, 3:4]) * shaded + tape
-        near |= active & ((sample_color[:, 3] - 1e-3).abs() < 1e-5).detach()
-        lit = (active & (sample_color[:, 3] > 1e-3)) if nondiff else active
-        tape = torch.where(lit[:, None], new, tape)
-        count = count + active.long()
-        nflat = nflat + (active & flat).long()
-    if nondiff:
-        tape = torch.clamp(tape, max=1.0)
-    return tape, count, near, nflat
+        return shaded, sample_color[:, 3], dict(near=(sample_color[:, 3] - 1e-3).abs() < 1e-5, flat=flat)
+
+    out, _, count, counts = G.march(cam, entry, exit_, rays, n, max_samples, nondiff, sample)
+    return out, count, counts["near"] > 0, counts["flat"]
 
 
 def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, sampling_rate, dtype=torch.float64,
@@ -123,40 +85,25 @@ def run(vol, tf2d, g_scale, cam, entry, exit_, rays, n, grad_out, max_samples, s
     V, W, H = n.shape
     volt = T(vol).requires_grad_(want_grad and want_vol)
     tft = T(tf2d).requires_grad_(want_grad)
-    rgba = np.zeros((V, W, H, 4))
-    steps = np.zeros((V, W, H), np.int32)
-    near = np.zeros((V, W, H), bool)
-    nflat = np.zeros((V, W, H), np.int64)
-    total = 0.0
+    views, total = [], 0.0
     for v in range(V):
-        live = n[v].reshape(-1) > 1
-        if pixels is not None:
-            live &= pixels[v].reshape(-1)
-        sel = torch.from_numpy(np.nonzero(live)[0])
-        if sel.numel() == 0:
-            continue
-        out, cnt, nr, nf = raycast_tf2d(volt[v] if vol.ndim == 4 else volt, tft[v] if tf2d.ndim == 4 else tft, float(g_scale),
-                                T(cam[v]), T(entry[v]).reshape(-1)[sel], T(exit_[v]).reshape(-1)[sel],
-                                T(rays[v]).reshape(-1, 3)[sel], torch.from_numpy(n[v].astype(np.int64)).reshape(-1)[sel],
-                                int(max_samples), float(sampling_rate), nondiff)
-        flat = np.zeros((W * H, 4)); flat[sel.numpy()] = out.detach().double().numpy()
-        rgba[v] = flat.reshape(W, H, 4)
-        st = np.zeros(W * H, np.int32); st[sel.numpy()] = cnt.numpy()
-        steps[v] = st.reshape(W, H)
-        nm = np.zeros(W * H, bool); nm[sel.numpy()] = nr.numpy()
-        near[v] = nm.reshape(W, H)
-        fl = np.zeros(W * H, np.int64); fl[sel.numpy()] = nf.numpy()
-        nflat[v] = fl.reshape(W, H)
-        total = total + (out * T(grad_out[v]).reshape(-1, 4)[sel]).sum()
-    res = dict(rgba=rgba, steps=steps, near=near)
-    if count_flat:
-        res["flat"] = nflat
+        def march_rays(sel):
+            out, cnt, nr, nf = raycast_tf2d(volt[v] if vol.ndim == 4 else volt, tft[v] if tf2d.ndim == 4 else tft, float(g_scale),
+                                            T(cam[v]), T(entry[v]).reshape(-1)[sel], T(exit_[v]).reshape(-1)[sel],
+                                            T(rays[v]).reshape(-1, 3)[sel], torch.from_numpy(n[v].astype(np.int64)).reshape(-1)[sel],
+                                            int(max_samples), float(sampling_rate), nondiff)
+            return out, dict(steps=cnt.int(), near=nr, flat=nf)
+
+        loss, res = G.render_view((W, H), n[v], None if pixels is None else pixels[v], T(grad_out[v]).reshape(-1, 4), march_rays)
+        total = total + loss
+        views.append(res)
+    res = {k: np.stack([r[k] for r in views]) for k in ("rgba", "steps", "near") + (("flat",) if count_flat else ())}
     if want_grad:
         if torch.is_tensor(total):
             total.backward()
         if want_vol:
-            res["dvol"] = volt.grad.double().numpy() if volt.grad is not None else np.zeros(vol.shape)
-        res["dtf"] = tft.grad.double().numpy() if tft.grad is not None else np.zeros(tf2d.shape)
+            res["dvol"] = G.grad_or_zero(volt)
+        res["dtf"] = G.grad_or_zero(tft)
     return res
 
 
