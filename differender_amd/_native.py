@@ -88,6 +88,16 @@ SIGNATURES = {
                               _I, _I, _I, _I, _F, _P, _I, _P, _P, _P]),
     "dr_march_lit_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
                               _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _P, _P]),
+    # the depth moments: dr_march_fwd's volume, TF and ray arguments, then out, steps / the backward's
+    # gradients / the tails of dr_march_rgba_bwd_cam / _bwd_pose
+    "dr_march_depth_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                                _I, _I, _I, _I, _F, _P, _P, _P]),
+    "dr_march_depth_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                                _I, _I, _I, _I, _F, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P]),
+    "dr_march_depth_bwd_cam": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                                    _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P]),
+    "dr_march_depth_bwd_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
+                                     _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

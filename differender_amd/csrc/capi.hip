@@ -652,6 +652,93 @@ int dr_march_rgba_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int V
                                  grad_out, out_rgba, pose, fov_v, d_pose, d_pose_ray, stream);
 }
 
+// what the depth entries check before any HIP call: fill_rays with max_samples >= 1 and a finite rate, and the 1-D table
+static int fill_depth(MarchArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                      int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                      const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W, int H,
+                      int max_samples, float sampling_rate) {
+    const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                             W, H, max_samples, 1, sampling_rate, true);
+    if (rc) return rc;
+    if (!tf || R < 1 || tf_view_stride % 4 != 0) return DR_EINVAL;
+    a.tf = tf; a.R = R; a.tf_vs = tf_view_stride;
+    a.mode = DR_MODE_DIFF;
+    return 0;
+}
+
+int dr_march_depth_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                       int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                       const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W, int H,
+                       int max_samples, float sampling_rate, float *out_moments, int32_t *steps, void *stream) {
+    MarchArgs a;
+    const int rc = fill_depth(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
+                              rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!out_moments) return DR_EINVAL;
+    a.out = out_moments; a.steps = steps;
+    return launch_on(vol, launch_march_depth_fwd, a, (hipStream_t)stream);
+}
+
+int dr_march_depth_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                       int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                       const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W, int H,
+                       int max_samples, float sampling_rate, const float *grad_out, const float *out_moments, float *d_vol,
+                       int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride, float *d_tf, int64_t dtf_view_stride,
+                       void *stream) {
+    MarchArgs a;
+    int rc = fill_depth(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_, rays,
+                        nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    rc = fill_bwd(a, grad_out, out_moments, d_vol, dsx, dsy, dsz, dvol_view_stride, d_tf, dtf_view_stride);
+    if (rc) return rc;
+    if (!d_vol && !d_tf) return 0;  // nothing requested
+    return launch_on(vol, launch_march_depth_bwd, a, (hipStream_t)stream);
+}
+
+// dr_march_depth_bwd_cam (pose null: d_cam [n_views][3]) and dr_march_depth_bwd_pose (d_cam [n_views][10]): one implementation
+static int march_depth_bwd_camera(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                                  int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                                  const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views,
+                                  int W, int H, int max_samples, float sampling_rate, double fov_rad, double near_plane,
+                                  uint32_t jitter_seed, uint32_t view_base, const int32_t *steps, const float *grad_out,
+                                  const float *out_moments, const float *pose, const float *fov_v, double *d_cam,
+                                  float *d_cam_ray, void *stream) {
+    MarchArgs a;
+    const int rc = fill_depth(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
+                              rays, nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!steps || !grad_out || !out_moments || !d_cam || !pose_fits(pose, fov_v)) return DR_EINVAL;
+    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
+    a.pose = pose; a.fov_v = fov_v;
+    a.grad_out = grad_out; a.out_fwd = out_moments; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    CamArgs c;
+    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    return launch_on(vol, launch_march_depth_bwd_cam, a, c, (hipStream_t)stream);
+}
+
+int dr_march_depth_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                           int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                           const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                           int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed,
+                           uint32_t view_base, const int32_t *steps, const float *grad_out, const float *out_moments,
+                           double *d_cam, float *d_cam_ray, void *stream) {
+    return march_depth_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry,
+                                  exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, jitter_seed,
+                                  view_base, steps, grad_out, out_moments, nullptr, nullptr, d_cam, d_cam_ray, stream);
+}
+
+int dr_march_depth_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                            int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
+                            const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W,
+                            int H, int max_samples, float sampling_rate, double fov_rad, double near_plane, uint32_t jitter_seed,
+                            uint32_t view_base, const int32_t *steps, const float *grad_out, const float *out_moments,
+                            const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream) {
+    if (!pose) return DR_EINVAL;
+    return march_depth_bwd_camera(vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry,
+                                  exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate, fov_rad, near_plane, jitter_seed,
+                                  view_base, steps, grad_out, out_moments, pose, fov_v, d_pose, d_pose_ray, stream);
+}
+
 // what the three projection entries check: fill_rays at the projections' fixed rate of 1 with max_samples >= 1, the mode, and
 // arg_max for DR_PROJ_MAX
 static int fill_proj(MarchArgs &a, ProjArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,

@@ -184,6 +184,13 @@ struct LitArgs {
 __attribute__((weak)) int launch_march_lit_fwd(const MarchArgs &a, const LitArgs &q, hipStream_t stream);
 __attribute__((weak)) int launch_march_lit_bwd(const MarchArgs &a, const LitArgs &q, hipStream_t stream);
 
+// Ray-depth moments of the differentiable march (march_depth.hip): dr_march_depth_fwd / _bwd take the 1-D
+// march's MarchArgs (no workspace, variant, mode or bands); _bwd_cam / _bwd_pose CamArgs as launch_camera_grad.
+// weak, as launch_camera_grad: capi.o must load in a library linked without march_depth.o
+__attribute__((weak)) int launch_march_depth_fwd(const MarchArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_march_depth_bwd(const MarchArgs &a, hipStream_t stream);
+__attribute__((weak)) int launch_march_depth_bwd_cam(const MarchArgs &a, const CamArgs &c, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

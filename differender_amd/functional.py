@@ -14,7 +14,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd", "march_bwd_cam", "march_bwd_pose", "project_bwd_pose", "march_tf2d_fwd", "march_tf2d_bwd", "march_lit_fwd", "march_lit_bwd", "default_light", "march_rgba_fwd", "march_rgba_bwd", "project_fwd", "project_bwd",
+__all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd", "march_bwd_cam", "march_bwd_pose", "project_bwd_pose", "march_tf2d_fwd", "march_tf2d_bwd", "march_lit_fwd", "march_lit_bwd", "default_light", "march_rgba_fwd", "march_rgba_bwd", "march_depth_fwd", "march_depth_bwd", "march_depth_bwd_cam", "march_depth_bwd_pose", "project_fwd", "project_bwd",
            "project_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
@@ -734,6 +734,78 @@ def march_rgba_bwd_cam(vol4, cam, entry, exit_, rays, n, steps, max_samples, sam
                          int(jitter_seed) & 0xFFFFFFFF, int(view_base), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(),
                          *pargs[2:], d_cam.data_ptr(), _ptr(d_ray), _stream())
     N.check(rc, "dr_march_rgba_bwd_cam" if pose is None else "dr_march_rgba_bwd_pose")
+    return _cam_grad_result(d_cam, d_ray)
+
+
+def march_depth_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, want_steps=True):
+    """The ray-depth moments of the differentiable march (dr_march_depth_fwd): march_fwd's samples, classified by
+    the table's alpha alone (one tap, no shading), compositing the sample's distance t from look_from and its square. Returns
+    out (views,W,H,4) = (M1, M2, 0, A) -- A and steps the bits of march_fwd(variant=DR_VARIANT_BASELINE) -- and steps (views,W,H)
+    int32 (or None)."""
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    out, steps = _fwd_buffers(V, W, H, vol.device, want_steps)
+    vargs = _vol_args(vol, V)
+    targs = _tf_args(tf, V)
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_march_depth_fwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), out.data_ptr(),
+                                        _ptr(steps), _stream())
+    N.check(rc, "dr_march_depth_fwd")
+    return out, steps
+
+
+def march_depth_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, grad_out, out, want_vol=True, want_tf=True):
+    """Adjoint of march_depth_fwd w.r.t. vol and tf (dr_march_depth_bwd). Returns (d_vol, d_tf), either None when not wanted; a
+    shared (un-batched) vol / tf receives one gradient accumulated over all views. Only the alpha column of d_tf is non-zero.
+    Channel 2 of grad_out is not used. NaN propagates (the plain kernels' convention: the caller applies nan_to_num, as
+    depth.DepthRaycaster does)."""
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
+    vargs = _vol_args(vol, V)
+    targs = _tf_args(tf, V)
+    if not (want_vol or want_tf):
+        return None, None
+    d_vol, dv = _d_vol(vol, want_vol)
+    d_tf = None
+    dt = (None, 0)
+    if want_tf:
+        d_tf = torch.zeros_like(tf)
+        dt = (d_tf.data_ptr(), d_tf.stride(0) if tf.ndim == 3 else 0)
+    with torch.cuda.device(vol.device):
+        rc = N.lib().dr_march_depth_bwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
+                                        out.data_ptr(), *dv, *dt, _stream())
+    N.check(rc, "dr_march_depth_bwd")
+    return d_vol, d_tf
+
+
+def march_depth_bwd_pose(vol, tf, pose, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
+                         near=0.1, jitter_seed=0, view_base=0, per_ray=False, fov_v=None):
+    """d pose of sum(march_depth_fwd(...) * grad_out) (dr_march_depth_bwd_pose): march_depth_bwd_cam for the free
+    camera of ray_setup_pose, as march_bwd_pose is march_bwd_cam's. Returns d_pose (views, 10) float32 (the fov column per
+    radian) -- and, with per_ray=True, each ray's contribution (views, W, H, 10) as well."""
+    return march_depth_bwd_cam(vol, tf, pose[:, :3], entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out,
+                               fov_deg, near, jitter_seed, view_base, per_ray, pose=pose, fov_v=fov_v)
+
+
+def march_depth_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampling_rate, grad_out, out, fov_deg=30.0,
+                        near=0.1, jitter_seed=0, view_base=0, per_ray=False, pose=None, fov_v=None):
+    """d look_from of sum(march_depth_fwd(...) * grad_out) (dr_march_depth_bwd_cam): cam (views, 3), the ray
+    buffers, jitter_seed and view_base those of the forward's ray_setup, `steps` and `out` those of march_depth_fwd. Returns
+    d_cam (views, 3) float32 -- and, with per_ray=True, each ray's contribution (views, W, H, 3) as well."""
+    cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
+    grad_out, out = _bwd_images(grad_out, out)
+    steps = steps.to(torch.int32).contiguous()
+    vargs = _vol_args(vol, V)
+    targs = _tf_args(tf, V)
+    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray, 3 if pose is None else 10)
+    if pose is None:
+        entry_point, pargs = N.lib().dr_march_depth_bwd_cam, ()
+    else:   # (march_depth_bwd_pose)
+        entry_point, pargs = N.lib().dr_march_depth_bwd_pose, _pose_args(pose, fov_v, V)
+    with torch.cuda.device(vol.device):
+        rc = entry_point(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), float(np.radians(fov_deg)), float(near),
+                         int(jitter_seed) & 0xFFFFFFFF, int(view_base), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(),
+                         *pargs[2:], d_cam.data_ptr(), _ptr(d_ray), _stream())
+    N.check(rc, "dr_march_depth_bwd_cam" if pose is None else "dr_march_depth_bwd_pose")
     return _cam_grad_result(d_cam, d_ray)
 
 

@@ -520,6 +520,60 @@ int dr_march_lit_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                      float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
                      float *d_tf, int64_t dtf_view_stride, double *d_light, float *d_light_ray, void *stream);
 
+/* Ray-depth moments of the differentiable 1-D TF march: where along a ray the image comes from. The samples are
+ * exactly those of dr_march_fwd in DR_MODE_DIFF, from the buffers of dr_ray_setup[_pose_rows] (jitter included). For a ray with
+ * n > 1: m = min(n, max_samples) samples at t_s = mix(t0, exit, s/(n-1)), t0 = entry + 0.5 (exit - entry)/n -- the distance from
+ * look_from along the unit ray direction, in world units; per sample one trilinear tap, the TF lookup and
+ * op = 1 - (1 - a)^(1 / sampling_rate) (the specified power of dr_march_fwd, D6); no normal, no shading. While A < 0.99,
+ * sequentially in f32 with T = 1 - A:
+ *   M1 = fma(T, t op, M1),  M2 = fma(T, (t t) op, M2),  A = fma(T, op, A).
+ * out_moments [n_views][W][H][4] f32 = (M1, M2, 0, A); steps [n_views][W][H] int32 = the live samples, nullable. A ray with
+ * n <= 1 gives 0 with 0 steps (H6). A and steps are the bits of dr_march_fwd under DR_VARIANT_BASELINE on the same buffers.
+ * M1 / A is the expected depth, M2 / A - (M1 / A)^2 its variance. There is no non-differentiable mode.
+ * dr_march_depth_bwd is the reverse-mode derivative with dr_march_bwd's frozen branches (n, the live samples, every cell, the
+ * 0 < xtf predicate), tape-free. With g = grad_out (channel 2 is never used) and q_s = g.x t_s + g.y t_s^2 + g.w:
+ * op_bar = T_s q_s - suffix / (1 - op_s) (no suffix term for the last live sample), suffix = g . (final - composite after s).
+ * d_vol (f32, own element strides, dvol_view_stride 0 = one gradient summed over the views) and d_tf (f32, dtf_view_stride
+ * likewise) are ACCUMULATED (caller zeroes). Only the alpha column of d_tf receives anything: the colour columns are not
+ * written. NaN propagates as in the plain kernels. d_vol == NULL && d_tf == NULL returns 0 before any HIP call.
+ * dr_march_depth_bwd_cam / _bwd_pose: the camera gradient, dr_march_bwd_cam's chain (D8) without lighting and with the direct
+ * term of t_s in the integrand; the arguments after sampling_rate are those of dr_march_rgba_bwd_cam / _bwd_pose (`steps` of
+ * dr_march_depth_fwd; d_cam [n_views][3] / d_pose [n_views][10] f64 ACCUMULATED, d fov PER RADIAN; per-ray outputs f32,
+ * nullable, overwritten). A NaN ray contributes nothing and infinities are clamped to +-1e30 (D5). Whole images only.
+ * Invalid arguments (null required pointers, n_views, W or H <= 0, a volume extent < 2, R < 1, max_samples < 1, an unknown
+ * dtype, a non-finite or non-positive sampling rate; for the camera entries steps, d_cam, pose for _pose, fov_v without pose)
+ * return DR_EINVAL before any HIP call. */
+int dr_march_depth_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                       int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                       const float *tf, int R, int64_t tf_view_stride,
+                       const float *cam, const float *entry, const float *exit_, const float *rays,
+                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                       float *out_moments, int32_t *steps, void *stream);
+int dr_march_depth_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                       int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                       const float *tf, int R, int64_t tf_view_stride,
+                       const float *cam, const float *entry, const float *exit_, const float *rays,
+                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                       const float *grad_out, const float *out_moments,
+                       float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dvol_view_stride,
+                       float *d_tf, int64_t dtf_view_stride, void *stream);
+int dr_march_depth_bwd_cam(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                           int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                           const float *tf, int R, int64_t tf_view_stride,
+                           const float *cam, const float *entry, const float *exit_, const float *rays,
+                           const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                           double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                           const int32_t *steps, const float *grad_out, const float *out_moments,
+                           double *d_cam, float *d_cam_ray, void *stream);
+int dr_march_depth_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                            int64_t sx, int64_t sy, int64_t sz, int64_t vol_view_stride,
+                            const float *tf, int R, int64_t tf_view_stride,
+                            const float *cam, const float *entry, const float *exit_, const float *rays,
+                            const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                            double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                            const int32_t *steps, const float *grad_out, const float *out_moments,
+                            const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream);
+
 /* X-ray line-integral and maximum-intensity projections: the two standard projections of a scalar volume beside
  * compositing, differentiable w.r.t. the volume and the camera position. The samples are exactly those of the march, from the
  * ray buffers of dr_ray_setup (jitter included): s < m = min(n, max_samples), pos_s = look_from + mix(t0, exit, s/(n-1)) vd,
