@@ -144,13 +144,15 @@ static int fill_rays(MarchArgs &a, const void *vol, int vol_dtype, int VX, int V
     return 0;
 }
 
-// fill_rays and the 1-D table (the 2-D TF entries add their second axis in fill_tf2d)
+// fill_rays and the 1-D table (the 2-D TF entries add their second axis in fill_tf2d, the depth entries their stricter
+// min_samples and finite_rate in fill_depth)
 static int fill_common(MarchArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy,
                        int64_t sz, int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride,
                        const float *cam, const float *entry, const float *exit_, const float *rays,
-                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate) {
+                       const int32_t *nsamp, int n_views, int W, int H, int max_samples, float sampling_rate,
+                       int min_samples = 0, bool finite_rate = false) {
     const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
-                             W, H, max_samples, 0, sampling_rate, false);
+                             W, H, max_samples, min_samples, sampling_rate, finite_rate);
     if (rc) return rc;
     if (!tf || R < 1 || tf_view_stride % 4 != 0) return DR_EINVAL;
     a.tf = tf; a.R = R; a.tf_vs = tf_view_stride;
@@ -172,6 +174,19 @@ static int fill_bwd(MarchArgs &a, const float *grad_out, const float *out_rgba, 
 
 // a pose's look_from rows are the `cam` the march kernels read as the ray origin; fov_v only comes with a pose
 static bool pose_fits(const float *pose, const float *fov_v) { return pose || !fov_v; }
+
+// What the camera entries of the three marches (1-D TF, RGBA, depth; pose null: d_cam [n_views][3], else [n_views][10]) check
+// once their family's fill_* has passed, before any HIP call, and the MarchArgs and CamArgs fields they all set
+static int fill_camera(MarchArgs &a, CamArgs &c, double fov_rad, double near_plane, uint32_t jitter_seed, uint32_t view_base,
+                       const int32_t *steps, const float *grad_out, const float *out_fwd, const float *pose, const float *fov_v,
+                       double *d_cam, float *d_cam_ray) {
+    if (!steps || !grad_out || !out_fwd || !d_cam || !pose_fits(pose, fov_v)) return DR_EINVAL;
+    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
+    a.mode = DR_MODE_DIFF; a.pose = pose; a.fov_v = fov_v;
+    a.grad_out = grad_out; a.out_fwd = out_fwd; a.fov_rad = fov_rad; a.near_plane = near_plane;
+    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    return 0;
+}
 
 int dr_march_fwd_rows_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                  int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
@@ -310,16 +325,14 @@ static int march_bwd_camera(const void *vol, int vol_dtype, int VX, int VY, int 
                             const float *out_rgba, const float *pose, const float *fov_v, double *d_cam, float *d_cam_ray,
                             void *stream) {
     MarchArgs a;
+    CamArgs c;
     int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam,
                          entry, exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate);
     if (rc) return rc;
-    if (!steps || !grad_out || !out_rgba || !d_cam) return DR_EINVAL;
-    if (!band_fits(W, img_W, row0) || !pose_fits(pose, fov_v)) return DR_EINVAL;
-    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
-    a.img_W = img_W; a.row0 = row0; a.mode = DR_MODE_DIFF; a.pose = pose; a.fov_v = fov_v;
-    a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
-    CamArgs c;
-    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    rc = fill_camera(a, c, fov_rad, near_plane, jitter_seed, view_base, steps, grad_out, out_rgba, pose, fov_v, d_cam, d_cam_ray);
+    if (rc) return rc;
+    if (!band_fits(W, img_W, row0)) return DR_EINVAL;
+    a.img_W = img_W; a.row0 = row0;
     return launch_on(vol, launch_camera_grad, a, c, (hipStream_t)stream);
 }
 
@@ -618,15 +631,12 @@ static int march_rgba_bwd_camera(const void *vol, int vol_dtype, int VX, int VY,
                                  const float *fov_v, double *d_cam, float *d_cam_ray, void *stream) {
     MarchArgs a;
     RgbaArgs q;
-    const int rc = fill_rgba(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp,
-                             n_views, W, H, max_samples, sampling_rate);
-    if (rc) return rc;
-    if (!steps || !grad_out || !out_rgba || !d_cam || !pose_fits(pose, fov_v)) return DR_EINVAL;
-    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
-    a.mode = DR_MODE_DIFF; a.pose = pose; a.fov_v = fov_v;
-    a.grad_out = grad_out; a.out_fwd = out_rgba; a.fov_rad = fov_rad; a.near_plane = near_plane;
     CamArgs c;
-    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    int rc = fill_rgba(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
+                       W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    rc = fill_camera(a, c, fov_rad, near_plane, jitter_seed, view_base, steps, grad_out, out_rgba, pose, fov_v, d_cam, d_cam_ray);
+    if (rc) return rc;
     return launch_on(vol, launch_march_rgba_bwd_cam, a, q, c, (hipStream_t)stream);
 }
 
@@ -652,16 +662,14 @@ int dr_march_rgba_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int V
                                  grad_out, out_rgba, pose, fov_v, d_pose, d_pose_ray, stream);
 }
 
-// what the depth entries check before any HIP call: fill_rays with max_samples >= 1 and a finite rate, and the 1-D table
+// what the depth entries check before any HIP call: fill_common with max_samples >= 1 and a finite rate; always differentiable
 static int fill_depth(MarchArgs &a, const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
                       int64_t vol_view_stride, const float *tf, int R, int64_t tf_view_stride, const float *cam,
                       const float *entry, const float *exit_, const float *rays, const int32_t *nsamp, int n_views, int W, int H,
                       int max_samples, float sampling_rate) {
-    const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, cam, entry, exit_, rays, nsamp, n_views,
-                             W, H, max_samples, 1, sampling_rate, true);
+    const int rc = fill_common(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry,
+                               exit_, rays, nsamp, n_views, W, H, max_samples, sampling_rate, 1, true);
     if (rc) return rc;
-    if (!tf || R < 1 || tf_view_stride % 4 != 0) return DR_EINVAL;
-    a.tf = tf; a.R = R; a.tf_vs = tf_view_stride;
     a.mode = DR_MODE_DIFF;
     return 0;
 }
@@ -704,15 +712,13 @@ static int march_depth_bwd_camera(const void *vol, int vol_dtype, int VX, int VY
                                   const float *out_moments, const float *pose, const float *fov_v, double *d_cam,
                                   float *d_cam_ray, void *stream) {
     MarchArgs a;
-    const int rc = fill_depth(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_,
-                              rays, nsamp, n_views, W, H, max_samples, sampling_rate);
-    if (rc) return rc;
-    if (!steps || !grad_out || !out_moments || !d_cam || !pose_fits(pose, fov_v)) return DR_EINVAL;
-    if (!(near_plane > 0.0) || !(fov_rad > 0.0)) return DR_EINVAL;
-    a.pose = pose; a.fov_v = fov_v;
-    a.grad_out = grad_out; a.out_fwd = out_moments; a.fov_rad = fov_rad; a.near_plane = near_plane;
     CamArgs c;
-    c.jitter_seed = jitter_seed; c.view_base = view_base; c.steps = steps; c.d_cam = d_cam; c.d_cam_ray = d_cam_ray;
+    int rc = fill_depth(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, vol_view_stride, tf, R, tf_view_stride, cam, entry, exit_, rays,
+                        nsamp, n_views, W, H, max_samples, sampling_rate);
+    if (rc) return rc;
+    rc = fill_camera(a, c, fov_rad, near_plane, jitter_seed, view_base, steps, grad_out, out_moments, pose, fov_v, d_cam,
+                     d_cam_ray);
+    if (rc) return rc;
     return launch_on(vol, launch_march_depth_bwd_cam, a, c, (hipStream_t)stream);
 }
 

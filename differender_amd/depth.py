@@ -18,11 +18,12 @@ Jitter: every jittered forward draws its own seed (functional.new_jitter_seed), 
 render of the same training step sample their rays at DIFFERENT offsets. Render with jitter=False where the two must match
 sample for sample.
 """
+import functools
+
 import torch
 
 from . import _layout as L
 from . import functional as F
-from .pose import _pose_grads, _shapes
 
 __all__ = ["DepthRaycaster", "DepthRaycastFunction", "DepthCameraFunction", "expected_depth", "depth_variance"]
 
@@ -52,9 +53,23 @@ def depth_variance(m, eps=1e-6):
     return torch.where(hit, torch.clamp(m2 / safe - mean * mean, min=0.0), torch.zeros_like(a))
 
 
-def _sanitised(t):
-    # the plain kernels propagate NaN like the reference: nan_to_num, as RgbaRaycastFunction does
-    return None if t is None else torch.nan_to_num(t)
+def _forward(ctx, rc, volume, tf, look_from, sampling_rate, batched, jitter, pose, camera=None, needs=()):
+    tf = tf.float().contiguous()
+    march = lambda volume, cam, rays: F.march_depth_fwd(volume, tf, cam, *rays, rc.max_samples, sampling_rate)
+    return L.march_forward(ctx, rc, march, volume, (tf,), look_from, sampling_rate, batched, jitter, pose, camera, needs)
+
+
+def _backward(ctx, grad_output, need_camera=()):
+    """-> (d_vol, d_tf, [d look_from, d look_at, d up, d fov]): the volume / TF backward first, the camera backward (where
+    needed) behind it on the same stream."""
+    (volume, tf, e, x, r, n, out), cam, steps, pose9, fov_v = L.saved_rays(ctx)
+    g = grad_output if ctx.batched else grad_output[None]
+    dv, dt = F.march_depth_bwd(volume, tf, cam, e, x, r, n, ctx.rc.max_samples, ctx.sampling_rate, g, out,
+                               want_vol=ctx.needs_input_grad[1], want_tf=ctx.needs_input_grad[2])
+    march = (e, x, r, n, steps, ctx.rc.max_samples, ctx.sampling_rate, g, out)
+    camera = L.camera_grads(ctx, need_camera, functools.partial(F.march_depth_bwd_cam, volume, tf, cam, *march),
+                            functools.partial(F.march_depth_bwd_pose, volume, tf, pose9, *march, fov_v=fov_v))
+    return L.sanitised(dv), L.sanitised(dt), camera
 
 
 class DepthRaycastFunction(torch.autograd.Function):
@@ -65,22 +80,12 @@ class DepthRaycastFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, rc, volume, tf, look_from, sampling_rate, batched, jitter=True, pose=None):
-        volume, cam, _, rays = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near, pose)[:4]
-        tf = tf.float().contiguous()
-        out, steps = F.march_depth_fwd(volume, tf, cam, *rays, rc.max_samples, sampling_rate)
-        ctx.save_for_backward(volume, tf, cam, *rays, out)
-        ctx.rc, ctx.sampling_rate, ctx.batched = rc, sampling_rate, batched
-        rc._steps = L.unbatch(steps, batched)
-        return L.unbatch(out, batched)
+        return _forward(ctx, rc, volume, tf, look_from, sampling_rate, batched, jitter, pose)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, tf, cam, e, x, r, n, out = ctx.saved_tensors
-        g = grad_output if ctx.batched else grad_output[None]
-        dv, dt = F.march_depth_bwd(volume, tf, cam, e, x, r, n, ctx.rc.max_samples, ctx.sampling_rate, g, out,
-                                   want_vol=ctx.needs_input_grad[1], want_tf=ctx.needs_input_grad[2])
-        return None, _sanitised(dv), _sanitised(dt), None, None, None, None, None
+        return (None, *_backward(ctx, grad_output)[:2], None, None, None, None, None)
 
 
 class DepthCameraFunction(torch.autograd.Function):
@@ -92,41 +97,14 @@ class DepthCameraFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, rc, volume, tf, look_from, look_at, up, fov, sampling_rate, batched, jitter=True):
-        pose = (look_at, up, fov) if L.has_pose(look_at, up, fov) else None
-        volume, cam, seed, rays, *posed = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near,
-                                                      pose)
-        pose9, fov_v = posed if posed else (None, None)
-        tf = tf.float().contiguous()
-        out, steps = F.march_depth_fwd(volume, tf, cam, *rays, rc.max_samples, sampling_rate)
-        ctx.want_cam = any(ctx.needs_input_grad[3:7])
-        extra = [t for t in (steps if ctx.want_cam else None, pose9, fov_v) if t is not None]
-        ctx.save_for_backward(volume, tf, cam, *rays, out, *extra)
-        ctx.has_pose, ctx.has_fov = pose9 is not None, fov_v is not None
-        ctx.shapes = _shapes(look_from, look_at, up, fov)
-        ctx.rc, ctx.sampling_rate, ctx.batched, ctx.seed = rc, sampling_rate, batched, seed
-        rc._steps = L.unbatch(steps, batched)
-        return L.unbatch(out, batched)
+        return _forward(ctx, rc, volume, tf, look_from, sampling_rate, batched, jitter, L.pose_or_none(look_at, up, fov),
+                        (look_from, look_at, up, fov), ctx.needs_input_grad[3:7])
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, tf, cam, e, x, r, n, out, *extra = ctx.saved_tensors
-        rc = ctx.rc
-        g = grad_output if ctx.batched else grad_output[None]
-        dv, dt = F.march_depth_bwd(volume, tf, cam, e, x, r, n, rc.max_samples, ctx.sampling_rate, g, out,
-                                   want_vol=ctx.needs_input_grad[1], want_tf=ctx.needs_input_grad[2])
-        grads = [None] * 4
-        if ctx.want_cam:
-            steps = extra[0]
-            opts = dict(fov_deg=rc.fov, near=rc.near, jitter_seed=ctx.seed)
-            if ctx.has_pose:
-                d_pose = F.march_depth_bwd_pose(volume, tf, extra[1], e, x, r, n, steps, rc.max_samples, ctx.sampling_rate, g, out,
-                                                fov_v=extra[2] if ctx.has_fov else None, **opts)
-            else:   # the fixed camera: look_from's three columns, nothing else came in
-                d_cam = F.march_depth_bwd_cam(volume, tf, cam, e, x, r, n, steps, rc.max_samples, ctx.sampling_rate, g, out, **opts)
-                d_pose = torch.cat([d_cam, d_cam.new_zeros(d_cam.shape[0], 7)], 1)
-            grads = _pose_grads(d_pose, ctx.shapes, ctx.needs_input_grad[3:7])
-        return (None, _sanitised(dv), _sanitised(dt), *grads, None, None, None)
+        dv, dt, camera = _backward(ctx, grad_output, ctx.needs_input_grad[3:7])
+        return (None, dv, dt, *camera, None, None, None)
 
 
 class DepthRaycaster(L.RayModule):
@@ -139,30 +117,17 @@ class DepthRaycaster(L.RayModule):
 
     def __init__(self, volume_shape, output_shape, tf_shape, sampling_rate=1.0, jitter=True, max_samples=512, fov=30.0,
                  near=0.1, far=100.0, camera_grad=False):
-        if len(tuple(volume_shape)) != 3 or len(tuple(output_shape)) != 2:
-            raise ValueError("expected volume_shape (D, H, W) and output_shape (H, W)")
-        if int(tf_shape) < 1:
-            raise ValueError(f"tf_shape must be the TF resolution R >= 1, got {tf_shape}")
-        if int(max_samples) < 1:
-            raise ValueError(f"max_samples must be >= 1, got {max_samples}")
+        self._check_built(volume_shape, output_shape, tf_shape, max_samples)
         super().__init__(tuple(int(v) for v in volume_shape), output_shape, sampling_rate, jitter, max_samples, fov, near, far)
         self.tf_shape = int(tf_shape)
         self.camera_grad = bool(camera_grad)
 
-    def _determine_batch(self, volume, tf, look_from, pose=None):
-        """-> (batched, vol ([BS,] W, D, H) view, tf ([BS,] R, 4) view, look_from (views, 3)); un-batched inputs are shared by
-        all views. pose = (look_at, up, fov): they join the batch rule, and a fifth result holds them as rows per view."""
-        if volume.ndim not in (4, 5) or tf.ndim not in (2, 3) or look_from.ndim not in (1, 2):
-            raise ValueError("expected volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3)")
-        if volume.shape[-4] != 1 or tf.shape[-2] != 4 or look_from.shape[-1] != 3:
-            raise ValueError(f"expected volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3); got {tuple(volume.shape)}, "
-                             f"{tuple(tf.shape)}, {tuple(look_from.shape)}")
-        self._check_built_for(volume)
-        if tf.shape[-1] != self.tf_shape:
-            raise ValueError(f"tf has R = {tf.shape[-1]}, the module was built for {self.tf_shape}")
-        inputs = ((volume, 5), (tf, 3))
-        batched, _, lf, *posed = L.batch_rule(look_from, *inputs) if pose is None else L.pose_rule(look_from, pose, *inputs)
-        return (batched, L.field_view(volume), tf.transpose(-1, -2), lf, *posed)
+    def _batch(self, volume, tf, look_from, pose=None):
+        """-> (batched, vol ([BS,] W, D, H) view, tf ([BS,] R, 4) view, look_from (views, 3), pose); un-batched inputs are shared
+        by all views. pose = (look_at, up, fov): they join the batch rule and come back as rows per view; else None."""
+        self._check_tf_inputs(volume, tf, look_from)
+        batched, lf, pose = L.views(look_from, pose, (volume, 5), (tf, 3))
+        return batched, L.field_view(volume), tf.transpose(-1, -2), lf, pose
 
     @staticmethod
     def _moments_image(out, batched):
@@ -174,20 +139,15 @@ class DepthRaycaster(L.RayModule):
         """volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3) -> ([BS,]3,H,W) = (M1, M2, A).
         look_at, up ([BS,]3), fov ([BS,] degrees): the free camera. All None: the fixed camera. The four camera
         tensors may require grad in a module built with camera_grad=True only."""
-        posed = L.has_pose(look_at, up, fov)
+        pose = L.pose_or_none(look_at, up, fov)
         if self.camera_grad and L.wants_grad(look_from, look_at, up, fov):
-            if posed:
-                batched, vol, tf_in, lf, pose = self._determine_batch(volume, tf, look_from, (look_at, up, fov))
-            else:
-                (batched, vol, tf_in, lf), pose = self._determine_batch(volume, tf, look_from), (None, None, None)
-            res = DepthCameraFunction.apply(self, vol, tf_in, lf, *pose, self.sampling_rate, batched, self.jitter)
+            batched, vol, tf_in, lf, pose = self._batch(volume, tf, look_from, pose)
+            res = DepthCameraFunction.apply(self, vol, tf_in, lf, *(pose or (None, None, None)), self.sampling_rate, batched,
+                                            self.jitter)
             return self._moments_image(res, batched)
         hint = "construct DepthRaycaster(..., camera_grad=True) for camera gradients"
         L.refuse_pose_grad("DepthRaycaster", hint, look_from=look_from, look_at=look_at, up=up, fov=fov)
-        if posed:
-            batched, vol, tf_in, lf, pose = self._determine_batch(volume, tf, look_from, (look_at, up, fov))
-        else:
-            (batched, vol, tf_in, lf), pose = self._determine_batch(volume, tf, look_from), None
+        batched, vol, tf_in, lf, pose = self._batch(volume, tf, look_from, pose)
         res = DepthRaycastFunction.apply(self, vol, tf_in, lf, self.sampling_rate, batched, self.jitter, pose)
         return self._moments_image(res, batched)
 

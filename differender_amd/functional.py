@@ -24,6 +24,13 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _call(name, device, *args):
+    """The C entry `name` on `device`, on its current stream (the entry's last argument); an error names the entry."""
+    with torch.cuda.device(device):
+        rc = getattr(N.lib(), name)(*args, _stream())
+    N.check(rc, name)
+
+
 def _require_gpu(t, name):
     if not t.is_cuda:
         raise RuntimeError(f"differender_amd: `{name}` must live on a ROCm GPU (got {t.device}); "
@@ -468,6 +475,15 @@ def _d_vol(vol, want):
     return d_vol, (d_vol.data_ptr(), *d_vol.stride()[1:], d_vol.stride(0))
 
 
+def _d_tf(tf, want, batched_ndim):
+    """A plain backward's d_tf (zeros like the table, whose rank is batched_ndim when every view has its own) and its C-ABI
+    arguments (pointer, view stride); (None, (None, 0)) when not wanted."""
+    if not want:
+        return None, (None, 0)
+    d_tf = torch.zeros_like(tf)
+    return d_tf, (d_tf.data_ptr(), d_tf.stride(0) if tf.ndim == batched_ndim else 0)
+
+
 def march_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, grad_out, out, want_vol=True,
               want_tf=True, variant=N.DR_VARIANT_AUTO, fov_deg=30.0, near=0.1, workspace=None, rows=None, count_evaluated=False,
               tape=False, pose=None, fov_v=None):
@@ -521,19 +537,24 @@ def march_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples, sampl
     cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
     grad_out, out = _bwd_images(grad_out, out)
     steps = steps.to(torch.int32).contiguous()
-    vargs = _vol_args(vol, V)
-    targs = _tf_args(tf, V)
+    head = (*_vol_args(vol, V), *_tf_args(tf, V), *rargs, int(max_samples), float(sampling_rate))
+    return _camera_bwd("dr_march_bwd", vol, n, head, (fov_deg, near, jitter_seed, view_base),
+                       (steps.data_ptr(), grad_out.data_ptr(), out.data_ptr()), per_ray, pose, fov_v, rows)
+
+
+def _camera_bwd(name, vol, n, head_args, camera, image_args, per_ray, pose, fov_v, rows=False):
+    """The end of every camera backward: the entry `name`_cam (d look_from, k = 3 columns) or, with a pose, `name`_pose (d pose
+    and d fov, k = 10) -- the one place that chooses between them. The C-ABI arguments are the family's head_args, then camera =
+    (fov_deg, near, jitter_seed, view_base), the image band of `rows` (march_bwd_cam's; False: the entry takes none; checked
+    behind the pose, as it always was), the family's image_args, the pose pointers, d_cam (views, k) and the per-ray d_ray
+    (views, W, H, k). The caller keeps its temporaries until this returns. -> _cam_grad_result."""
+    V, W, H = n.shape
+    fov_deg, near, jitter_seed, view_base = camera
     d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray, 3 if pose is None else 10)
-    if pose is None:
-        entry_point, pargs = N.lib().dr_march_bwd_cam, ()
-    else:   # (march_bwd_pose)
-        entry_point, pargs = N.lib().dr_march_bwd_pose, _pose_args(pose, fov_v, V)
-    with torch.cuda.device(vol.device):
-        rc = entry_point(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate),
-                         float(np.radians(fov_deg)), float(near), int(jitter_seed) & 0xFFFFFFFF, int(view_base),
-                         *_rows(rows, W), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(), *pargs[2:], d_cam.data_ptr(),
-                         _ptr(d_ray), _stream())
-    N.check(rc, "dr_march_bwd_cam" if pose is None else "dr_march_bwd_pose")
+    pargs = () if pose is None else _pose_args(pose, fov_v, V)
+    _call(name + ("_cam" if pose is None else "_pose"), vol.device, *head_args, float(np.radians(fov_deg)), float(near),
+          int(jitter_seed) & 0xFFFFFFFF, int(view_base), *(() if rows is False else _rows(rows, W)), *image_args, *pargs[2:],
+          d_cam.data_ptr(), _ptr(d_ray))
     return _cam_grad_result(d_cam, d_ray)
 
 
@@ -564,10 +585,8 @@ def march_tf2d_fwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
     out, steps = _fwd_buffers(V, W, H, vol.device, want_steps)
     vargs = _vol_args(vol, V)
     targs = _tf2d_args(tf2d, V)
-    with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_tf2d_fwd(*vargs, *targs, _g_scale(g_scale), *rargs, int(max_samples), float(sampling_rate),
-                                       int(mode), out.data_ptr(), _ptr(steps), _stream())
-    N.check(rc, "dr_march_tf2d_fwd")
+    _call("dr_march_tf2d_fwd", vol.device, *vargs, *targs, _g_scale(g_scale), *rargs, int(max_samples), float(sampling_rate),
+          int(mode), out.data_ptr(), _ptr(steps))
     return out, steps
 
 
@@ -584,15 +603,9 @@ def march_tf2d_bwd(vol, tf2d, cam, entry, exit_, rays, n, max_samples, sampling_
     if not (want_vol or want_tf):
         return None, None
     d_vol, dv = _d_vol(vol, want_vol)
-    d_tf = None
-    dt = (None, 0)
-    if want_tf:
-        d_tf = torch.zeros_like(tf2d)
-        dt = (d_tf.data_ptr(), d_tf.stride(0) if tf2d.ndim == 4 else 0)
-    with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_tf2d_bwd(*vargs, *targs, g, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
-                                       out.data_ptr(), *dv, *dt, _stream())
-    N.check(rc, "dr_march_tf2d_bwd")
+    d_tf, dt = _d_tf(tf2d, want_tf, 4)
+    _call("dr_march_tf2d_bwd", vol.device, *vargs, *targs, g, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
+          out.data_ptr(), *dv, *dt)
     return d_vol, d_tf
 
 
@@ -625,10 +638,8 @@ def march_lit_fwd(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampl
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
     light = _light_arg(light, V, vol.device)
-    with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_lit_fwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), light.data_ptr(), int(mode),
-                                      out.data_ptr(), _ptr(steps), _stream())
-    N.check(rc, "dr_march_lit_fwd")
+    _call("dr_march_lit_fwd", vol.device, *vargs, *targs, *rargs, int(max_samples), float(sampling_rate), light.data_ptr(), int(mode),
+          out.data_ptr(), _ptr(steps))
     return out, steps
 
 
@@ -645,19 +656,12 @@ def march_lit_bwd(vol, tf, cam, light, entry, exit_, rays, n, max_samples, sampl
     targs = _tf_args(tf, V)
     light = _light_arg(light, V, vol.device)
     d_vol, dv = _d_vol(vol, want_vol)
-    d_tf = None
-    dt = (None, 0)
-    if want_tf:
-        d_tf = torch.zeros_like(tf)
-        dt = (d_tf.data_ptr(), d_tf.stride(0) if tf.ndim == 3 else 0)
+    d_tf, dt = _d_tf(tf, want_tf, 3)
     d_light = torch.zeros((V, 10), dtype=torch.float64, device=vol.device) if want_light else None
     d_ray = torch.empty((V, W, H, 10), dtype=torch.float32, device=vol.device) if per_ray else None
     if want_vol or want_tf or want_light or per_ray:
-        with torch.cuda.device(vol.device):
-            rc = N.lib().dr_march_lit_bwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), light.data_ptr(),
-                                          N.DR_MODE_DIFF, grad_out.data_ptr(), out.data_ptr(), *dv, *dt, _ptr(d_light),
-                                          _ptr(d_ray), _stream())
-        N.check(rc, "dr_march_lit_bwd")
+        _call("dr_march_lit_bwd", vol.device, *vargs, *targs, *rargs, int(max_samples), float(sampling_rate), light.data_ptr(),
+              N.DR_MODE_DIFF, grad_out.data_ptr(), out.data_ptr(), *dv, *dt, _ptr(d_light), _ptr(d_ray))
     if d_light is not None:
         d_light = torch.nan_to_num(d_light.float())   # D5: a sum beyond the float range saturates
     return (d_vol, d_tf, d_light, d_ray) if per_ray else (d_vol, d_tf, d_light)
@@ -683,10 +687,8 @@ def march_rgba_fwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate,
     cam, V, W, H, rargs = _ray_args(vol4, cam, entry, exit_, rays, n)
     vargs = _vol4_args(vol4, V)
     out, steps = _fwd_buffers(V, W, H, vol4.device, want_steps)
-    with torch.cuda.device(vol4.device):
-        rc = N.lib().dr_march_rgba_fwd(*vargs, *rargs, int(max_samples), float(sampling_rate), int(mode), out.data_ptr(),
-                                       _ptr(steps), _stream())
-    N.check(rc, "dr_march_rgba_fwd")
+    _call("dr_march_rgba_fwd", vol4.device, *vargs, *rargs, int(max_samples), float(sampling_rate), int(mode), out.data_ptr(),
+          _ptr(steps))
     return out, steps
 
 
@@ -699,10 +701,8 @@ def march_rgba_bwd(vol4, cam, entry, exit_, rays, n, max_samples, sampling_rate,
     vargs = _vol4_args(vol4, V)
     d_vol = torch.zeros_like(vol4, dtype=torch.float32, memory_format=torch.preserve_format)
     dc, dx, dy, dz = d_vol.stride()[-4:]
-    with torch.cuda.device(vol4.device):
-        rc = N.lib().dr_march_rgba_bwd(*vargs, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(), out.data_ptr(),
-                                       d_vol.data_ptr(), dx, dy, dz, dc, d_vol.stride(0) if d_vol.ndim == 5 else 0, _stream())
-    N.check(rc, "dr_march_rgba_bwd")
+    _call("dr_march_rgba_bwd", vol4.device, *vargs, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
+          out.data_ptr(), d_vol.data_ptr(), dx, dy, dz, dc, d_vol.stride(0) if d_vol.ndim == 5 else 0)
     return d_vol
 
 
@@ -723,18 +723,9 @@ def march_rgba_bwd_cam(vol4, cam, entry, exit_, rays, n, steps, max_samples, sam
     cam, V, W, H, rargs = _ray_args(vol4, cam, entry, exit_, rays, n)
     grad_out, out = _bwd_images(grad_out, out)
     steps = steps.to(torch.int32).contiguous()
-    vargs = _vol4_args(vol4, V)
-    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol4.device, per_ray, 3 if pose is None else 10)
-    if pose is None:
-        entry_point, pargs = N.lib().dr_march_rgba_bwd_cam, ()
-    else:   # (march_rgba_bwd_pose)
-        entry_point, pargs = N.lib().dr_march_rgba_bwd_pose, _pose_args(pose, fov_v, V)
-    with torch.cuda.device(vol4.device):
-        rc = entry_point(*vargs, *rargs, int(max_samples), float(sampling_rate), float(np.radians(fov_deg)), float(near),
-                         int(jitter_seed) & 0xFFFFFFFF, int(view_base), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(),
-                         *pargs[2:], d_cam.data_ptr(), _ptr(d_ray), _stream())
-    N.check(rc, "dr_march_rgba_bwd_cam" if pose is None else "dr_march_rgba_bwd_pose")
-    return _cam_grad_result(d_cam, d_ray)
+    head = (*_vol4_args(vol4, V), *rargs, int(max_samples), float(sampling_rate))
+    return _camera_bwd("dr_march_rgba_bwd", vol4, n, head, (fov_deg, near, jitter_seed, view_base),
+                       (steps.data_ptr(), grad_out.data_ptr(), out.data_ptr()), per_ray, pose, fov_v)
 
 
 def march_depth_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_rate, want_steps=True):
@@ -746,10 +737,8 @@ def march_depth_fwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_r
     out, steps = _fwd_buffers(V, W, H, vol.device, want_steps)
     vargs = _vol_args(vol, V)
     targs = _tf_args(tf, V)
-    with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_depth_fwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), out.data_ptr(),
-                                        _ptr(steps), _stream())
-    N.check(rc, "dr_march_depth_fwd")
+    _call("dr_march_depth_fwd", vol.device, *vargs, *targs, *rargs, int(max_samples), float(sampling_rate), out.data_ptr(),
+          _ptr(steps))
     return out, steps
 
 
@@ -765,15 +754,9 @@ def march_depth_bwd(vol, tf, cam, entry, exit_, rays, n, max_samples, sampling_r
     if not (want_vol or want_tf):
         return None, None
     d_vol, dv = _d_vol(vol, want_vol)
-    d_tf = None
-    dt = (None, 0)
-    if want_tf:
-        d_tf = torch.zeros_like(tf)
-        dt = (d_tf.data_ptr(), d_tf.stride(0) if tf.ndim == 3 else 0)
-    with torch.cuda.device(vol.device):
-        rc = N.lib().dr_march_depth_bwd(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
-                                        out.data_ptr(), *dv, *dt, _stream())
-    N.check(rc, "dr_march_depth_bwd")
+    d_tf, dt = _d_tf(tf, want_tf, 3)
+    _call("dr_march_depth_bwd", vol.device, *vargs, *targs, *rargs, int(max_samples), float(sampling_rate), grad_out.data_ptr(),
+          out.data_ptr(), *dv, *dt)
     return d_vol, d_tf
 
 
@@ -794,19 +777,9 @@ def march_depth_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples,
     cam, V, W, H, rargs = _ray_args(vol, cam, entry, exit_, rays, n)
     grad_out, out = _bwd_images(grad_out, out)
     steps = steps.to(torch.int32).contiguous()
-    vargs = _vol_args(vol, V)
-    targs = _tf_args(tf, V)
-    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray, 3 if pose is None else 10)
-    if pose is None:
-        entry_point, pargs = N.lib().dr_march_depth_bwd_cam, ()
-    else:   # (march_depth_bwd_pose)
-        entry_point, pargs = N.lib().dr_march_depth_bwd_pose, _pose_args(pose, fov_v, V)
-    with torch.cuda.device(vol.device):
-        rc = entry_point(*vargs, *targs, *rargs, int(max_samples), float(sampling_rate), float(np.radians(fov_deg)), float(near),
-                         int(jitter_seed) & 0xFFFFFFFF, int(view_base), steps.data_ptr(), grad_out.data_ptr(), out.data_ptr(),
-                         *pargs[2:], d_cam.data_ptr(), _ptr(d_ray), _stream())
-    N.check(rc, "dr_march_depth_bwd_cam" if pose is None else "dr_march_depth_bwd_pose")
-    return _cam_grad_result(d_cam, d_ray)
+    head = (*_vol_args(vol, V), *_tf_args(tf, V), *rargs, int(max_samples), float(sampling_rate))
+    return _camera_bwd("dr_march_depth_bwd", vol, n, head, (fov_deg, near, jitter_seed, view_base),
+                       (steps.data_ptr(), grad_out.data_ptr(), out.data_ptr()), per_ray, pose, fov_v)
 
 
 _PROJ_MODES = {"sum": N.DR_PROJ_SUM, "max": N.DR_PROJ_MAX}
@@ -845,9 +818,7 @@ def project_fwd(vol, cam, entry, exit_, rays, n, max_samples=None, mode="sum"):
     out = torch.empty((V, W, H), dtype=torch.float32, device=dev)
     arg = torch.empty((V, W, H), dtype=torch.int32, device=dev) if md == N.DR_PROJ_MAX else None
     vargs = _vol_args(vol, V)
-    with torch.cuda.device(dev):
-        rc = N.lib().dr_project_fwd(*vargs, *rargs, _max_samples(max_samples), md, out.data_ptr(), _ptr(arg), _stream())
-    N.check(rc, "dr_project_fwd")
+    _call("dr_project_fwd", dev, *vargs, *rargs, _max_samples(max_samples), md, out.data_ptr(), _ptr(arg))
     return out, arg
 
 
@@ -861,9 +832,7 @@ def project_bwd(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None, mod
     grad_out = grad_out.to(torch.float32).contiguous()
     vargs = _vol_args(vol, V)
     d_vol, dv = _d_vol(vol, True)
-    with torch.cuda.device(vol.device):
-        rc = N.lib().dr_project_bwd(*vargs, *rargs, *pargs, grad_out.data_ptr(), _ptr(arg), *dv, int(variant), _stream())
-    N.check(rc, "dr_project_bwd")
+    _call("dr_project_bwd", vol.device, *vargs, *rargs, *pargs, grad_out.data_ptr(), _ptr(arg), *dv, int(variant))
     return d_vol
 
 
@@ -885,17 +854,8 @@ def project_bwd_cam(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None,
     arg, pargs = _proj_bwd_args(max_samples, mode, arg_max)
     grad_out = grad_out.to(torch.float32).contiguous()
     vargs = _vol_args(vol, V)
-    d_cam, d_ray = _cam_grad_buffers(V, W, H, vol.device, per_ray, 3 if pose is None else 10)
-    if pose is None:
-        entry_point, qargs = N.lib().dr_project_bwd_cam, ()
-    else:   # (project_bwd_pose)
-        entry_point, qargs = N.lib().dr_project_bwd_pose, _pose_args(pose, fov_v, V)
-    with torch.cuda.device(vol.device):
-        rc = entry_point(*vargs, *rargs, *pargs, float(np.radians(fov_deg)), float(near),
-                         int(jitter_seed) & 0xFFFFFFFF, int(view_base), grad_out.data_ptr(), _ptr(arg), *qargs[2:],
-                         d_cam.data_ptr(), _ptr(d_ray), _stream())
-    N.check(rc, "dr_project_bwd_cam" if pose is None else "dr_project_bwd_pose")
-    return _cam_grad_result(d_cam, d_ray)
+    return _camera_bwd("dr_project_bwd", vol, n, (*vargs, *rargs, *pargs), (fov_deg, near, jitter_seed, view_base),
+                       (grad_out.data_ptr(), _ptr(arg)), per_ray, pose, fov_v)
 
 
 def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):

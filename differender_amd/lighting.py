@@ -81,27 +81,21 @@ class LitRaycastFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, rc, volume, tf, look_from, light, sampling_rate, batched, jitter=True, pose=None):
-        volume, cam, _, rays = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near, pose)[:4]
         tf = tf.float().contiguous()
         light = light.float().contiguous()
-        out, steps = F.march_lit_fwd(volume, tf, cam, light, *rays, rc.max_samples, sampling_rate, N.DR_MODE_DIFF)
-        ctx.save_for_backward(volume, tf, cam, light, *rays, out)
-        ctx.rc, ctx.sampling_rate, ctx.batched = rc, sampling_rate, batched
-        rc._steps = L.unbatch(steps, batched)
-        return L.unbatch(out, batched)
+        march = lambda volume, cam, rays: F.march_lit_fwd(volume, tf, cam, light, *rays, rc.max_samples, sampling_rate,
+                                                          N.DR_MODE_DIFF)
+        return L.march_forward(ctx, rc, march, volume, (tf, light), look_from, sampling_rate, batched, jitter, pose)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, tf, cam, light, e, x, r, n, out = ctx.saved_tensors
+        (volume, tf, light, e, x, r, n, out), cam, *_ = L.saved_rays(ctx)
         g = grad_output if ctx.batched else grad_output[None]
         dv, dt, dl = F.march_lit_bwd(volume, tf, cam, light, e, x, r, n, ctx.rc.max_samples, ctx.sampling_rate, g, out,
                                      want_vol=ctx.needs_input_grad[1], want_tf=ctx.needs_input_grad[2],
                                      want_light=ctx.needs_input_grad[4])
-        # the plain kernels propagate NaN like the reference: VR.py:463-464,474-475's nan_to_num, as RaycastFunction does
-        dv = None if dv is None else torch.nan_to_num(dv)
-        dt = None if dt is None else torch.nan_to_num(dt)
-        return None, dv, dt, None, dl, None, None, None, None
+        return None, L.sanitised(dv), L.sanitised(dt), None, dl, None, None, None, None   # (d_light: sanitised in functional)
 
 
 class RaycasterLit(L.RayModule):
@@ -114,38 +108,27 @@ class RaycasterLit(L.RayModule):
 
     def __init__(self, volume_shape, output_shape, tf_shape, sampling_rate=1.0, jitter=True, max_samples=512, fov=30.0,
                  near=0.1, far=100.0, headlight=True):
-        if len(tuple(volume_shape)) != 3 or len(tuple(output_shape)) != 2:
-            raise ValueError("expected volume_shape (D, H, W) and output_shape (H, W)")
-        if int(tf_shape) < 1:
-            raise ValueError(f"tf_shape must be the TF resolution R >= 1, got {tf_shape}")
+        self._check_built(volume_shape, output_shape, tf_shape)
         super().__init__(volume_shape, output_shape, sampling_rate, jitter, max_samples, fov, near, far)
         self.tf_shape = int(tf_shape)
         self.headlight = bool(headlight)
 
-    def _determine_batch(self, volume, tf, look_from, lighting, pose=None):
-        """-> (batched, vol ([BS,] W, D, H) view, tf ([BS,] R, 4) view, look_from (views, 3)); un-batched inputs are shared by
-        all views. A (BS, k) lighting tensor joins the batch rule like any other input, and so does pose = (look_at, up, fov),
-        which a fifth result then holds as rows per view."""
-        if volume.ndim not in (4, 5) or tf.ndim not in (2, 3) or look_from.ndim not in (1, 2):
-            raise ValueError("expected volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3)")
-        if volume.shape[-4] != 1 or tf.shape[-2] != 4 or look_from.shape[-1] != 3:
-            raise ValueError(f"expected volume ([BS,]1,D,H,W), tf ([BS,]4,R), look_from ([BS,]3); got {tuple(volume.shape)}, "
-                             f"{tuple(tf.shape)}, {tuple(look_from.shape)}")
-        self._check_built_for(volume)
-        if tf.shape[-1] != self.tf_shape:
-            raise ValueError(f"tf has R = {tf.shape[-1]}, the module was built for {self.tf_shape}")
+    def _batch(self, volume, tf, look_from, lighting, pose=None):
+        """-> (batched, vol ([BS,] W, D, H) view, tf ([BS,] R, 4) view, look_from (views, 3), pose); un-batched inputs are shared
+        by all views. A (BS, k) lighting tensor joins the batch rule like any other input, and so does pose = (look_at, up, fov),
+        which comes back as rows per view; else None."""
+        self._check_tf_inputs(volume, tf, look_from)
         inputs = ((volume, 5), (tf, 3), *((v, 2) for _, _, v in lighting if torch.is_tensor(v)))
-        batched, _, lf, *posed = L.batch_rule(look_from, *inputs) if pose is None else L.pose_rule(look_from, pose, *inputs)
-        return (batched, L.field_view(volume), tf.transpose(-1, -2), lf, *posed)
+        batched, lf, pose = L.views(look_from, pose, *inputs)
+        return batched, L.field_view(volume), tf.transpose(-1, -2), lf, pose
 
     def _prepare(self, volume, tf, look_from, lighting_values, look_at, up, fov):
         """Every check that needs no device, then the views' inputs -> (batched, vol, tf, lf, light rows (views, 10), pose)."""
         L.refuse_pose_grad("RaycasterLit", look_from=look_from, look_at=look_at, up=up, fov=fov)
         lighting = _check_lighting(lighting_values)
-        pose = (look_at, up, fov) if L.has_pose(look_at, up, fov) else None
-        batched, vol, tf_in, lf, *posed = self._determine_batch(volume, tf, look_from, lighting, pose)
+        batched, vol, tf_in, lf, pose = self._batch(volume, tf, look_from, lighting, L.pose_or_none(look_at, up, fov))
         light = _light_rows(lighting, lf.detach().to(torch.float32), self.headlight)
-        return batched, vol, tf_in, lf, light, (posed[0] if posed else None)
+        return batched, vol, tf_in, lf, light, pose
 
     def forward(self, volume, tf, look_from, light_pos=None, light_color=None, ambient=None, diffuse=None, specular=None,
                 shininess=None, look_at=None, up=None, fov=None):
@@ -167,10 +150,9 @@ class RaycasterLit(L.RayModule):
         with torch.no_grad():
             batched, vol, tf_in, lf, light, pose = self._prepare(volume, tf, look_from, (light_pos, light_color, ambient, diffuse,
                                                                                          specular, shininess), look_at, up, fov)
-        with self._nondiff_rays(vol, lf, sampling_rate, pose) as (sr, vol, cam, rays, *_):
-            out, steps = F.march_lit_fwd(vol, tf_in.float().contiguous(), cam, light, *rays, self.max_samples, sr, N.DR_MODE_NONDIFF)
-            self._steps = L.unbatch(steps, batched)
-            return L.image(L.unbatch(out, batched))
+        march = lambda vol, cam, rays, sr: F.march_lit_fwd(vol, tf_in.float().contiguous(), cam, light, *rays, self.max_samples, sr,
+                                                           N.DR_MODE_NONDIFF)
+        return self._raycast_nondiff(vol, lf, sampling_rate, pose, batched, march)
 
     def extra_repr(self):
         return (f"Volume ({self.volume_shape}), Output Render ({self.output_shape}), TF ({self.tf_shape}), "

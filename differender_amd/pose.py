@@ -13,29 +13,15 @@ sum of their gradients. The light stays at look_from + (0, 1, 0) in world space:
 viewing direction is degenerate (as the fixed camera on the y axis is), and a fov outside (0, 90) degrees is not checked: the
 values live on the device, and checking them would synchronise.
 """
-import math
-
 import torch
 
 from . import _layout as L
 from . import _native as N
 from . import functional as F
+from . import projection
+from ._layout import camera_shapes as _shapes, pose_grads as _pose_grads
 
 __all__ = ["PoseRaycastFunction", "PoseProjectFunction"]
-
-_RAD_PER_DEG = math.pi / 180.0
-
-
-def _shapes(*tensors):
-    """(shape, dtype) of each camera tensor as the caller handed it in (None for None): what its gradient goes back as."""
-    return [None if t is None else (t.shape, t.dtype) for t in tensors]
-
-
-def _pose_grads(d_pose, shapes, needs):
-    """d_pose (views, 10) of the kernels -> the gradients of look_from, look_at, up and fov in the shapes they came in (an
-    un-batched one gets the sum over the views); fov.grad is per degree."""
-    cols = (d_pose[:, 0:3], d_pose[:, 3:6], d_pose[:, 6:9], d_pose[:, 9] * _RAD_PER_DEG)
-    return [L.reduce_to(c, *sh) if need and sh is not None else None for c, sh, need in zip(cols, shapes, needs)]
 
 
 class PoseRaycastFunction(torch.autograd.Function):
@@ -98,21 +84,14 @@ class PoseProjectFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, pj, volume, look_from, look_at, up, fov, batched, jitter=True):
-        volume, cam, seed, rays, pose, fov_v = L.diff_rays(volume, look_from, jitter, pj.output_shape, pj.sampling_rate, pj.fov,
-                                                           pj.near, pose=(look_at, up, fov))
-        out, arg = F.project_fwd(volume, cam, *rays, pj.max_samples, pj.mode)
-        ctx.save_for_backward(volume, pose, *rays, *((arg,) if arg is not None else ()), *((fov_v,) if fov_v is not None else ()))
-        ctx.has_arg, ctx.has_fov = arg is not None, fov_v is not None
-        ctx.pj, ctx.batched, ctx.seed = pj, batched, seed
-        ctx.shapes = _shapes(look_from, look_at, up, fov)
-        return L.unbatch(out, batched)
+        return projection._forward(ctx, pj, volume, look_from, batched, jitter, (look_at, up, fov))
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, pose, e, x, r, n = ctx.saved_tensors[:6]
-        arg = ctx.saved_tensors[6] if ctx.has_arg else None
-        fov_v = ctx.saved_tensors[-1] if ctx.has_fov else None
+        volume, pose, e, x, r, n, *rest = ctx.saved_tensors
+        arg = rest[0] if ctx.has_arg else None
+        fov_v = rest[-1] if ctx.has_fov else None
         pj = ctx.pj
         g = grad_output if ctx.batched else grad_output[None]
         dv = None

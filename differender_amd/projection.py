@@ -22,6 +22,20 @@ __all__ = ["Projector", "ProjectFunction"]
 _MODES = ("sum", "max")
 
 
+def _forward(ctx, pj, volume, look_from, batched, jitter, pose=None):
+    """The forward of ProjectFunction and, with pose = (look_at, up, fov), of pose.PoseProjectFunction. Saved: the volume, cam
+    (views, 3) -- with a pose the pose (views, 9) in its place --, the ray buffers, arg_max for "max" only, fov_v where given."""
+    volume, cam, seed, rays, pose9, fov_v = L.diff_rays(volume, look_from, jitter, pj.output_shape, pj.sampling_rate, pj.fov,
+                                                        pj.near, pose)
+    out, arg = F.project_fwd(volume, cam, *rays, pj.max_samples, pj.mode)
+    ctx.save_for_backward(volume, cam if pose9 is None else pose9, *rays, *((arg,) if arg is not None else ()),
+                          *((fov_v,) if fov_v is not None else ()))
+    ctx.has_arg, ctx.has_fov = arg is not None, fov_v is not None
+    ctx.pj, ctx.batched, ctx.seed = pj, batched, seed
+    ctx.shapes = L.camera_shapes(look_from, *(pose or ()))
+    return L.unbatch(out, batched)
+
+
 class ProjectFunction(torch.autograd.Function):
     """Autograd boundary of the projections: `apply(pj, volume, look_from, batched, jitter)`. volume (W,D,H) or (BS,W,D,H),
     any strides; look_from (BS,3). Returns (W,H) or (BS,W,H)."""
@@ -29,27 +43,21 @@ class ProjectFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, pj, volume, look_from, batched, jitter=True):
-        volume, cam, seed, rays = L.diff_rays(volume, look_from, jitter, pj.output_shape, pj.sampling_rate, pj.fov, pj.near)
-        out, arg = F.project_fwd(volume, cam, *rays, pj.max_samples, pj.mode)
-        ctx.save_for_backward(volume, cam, *rays, *((arg,) if arg is not None else ()))
-        ctx.pj, ctx.batched, ctx.seed = pj, batched, seed
-        ctx.lf_shape, ctx.lf_dtype = look_from.shape, look_from.dtype
-        return L.unbatch(out, batched)
+        return _forward(ctx, pj, volume, look_from, batched, jitter)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, cam, e, x, r, n = ctx.saved_tensors[:6]
-        arg = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
-        pj = ctx.pj
+        volume, cam, e, x, r, n, *arg = ctx.saved_tensors
+        pj, arg = ctx.pj, arg[0] if arg else None
         g = grad_output if ctx.batched else grad_output[None]
         dv = d_cam = None
         if ctx.needs_input_grad[1]:
             dv = torch.nan_to_num(F.project_bwd(volume, cam, e, x, r, n, g, pj.max_samples, pj.mode, arg))
-        if ctx.needs_input_grad[2]:
+        if ctx.needs_input_grad[2]:   # after project_bwd, on the same stream
             d_cam = F.project_bwd_cam(volume, cam, e, x, r, n, g, pj.max_samples, pj.mode, arg, fov_deg=pj.fov, near=pj.near,
                                       jitter_seed=ctx.seed)
-            d_cam = d_cam.reshape(ctx.lf_shape).to(ctx.lf_dtype)
+            d_cam = L.reduce_to(d_cam, *ctx.shapes[0])
         return None, dv, d_cam, None, None
 
 
@@ -63,8 +71,7 @@ class Projector(L.RayModule):
 
     def __init__(self, volume_shape, output_shape, mode="sum", sampling_rate=1.0, jitter=True, max_samples=None, fov=30.0,
                  near=0.1, far=100.0):
-        if len(tuple(volume_shape)) != 3 or len(tuple(output_shape)) != 2:
-            raise ValueError("expected volume_shape (D, H, W) and output_shape (H, W)")
+        self._check_built(volume_shape, output_shape)
         if min(volume_shape) < 2 or min(output_shape) < 1:
             raise ValueError(f"volume_shape needs >= 2 voxels per axis and output_shape >= 1 pixel, got {tuple(volume_shape)}, "
                              f"{tuple(output_shape)}")
@@ -77,17 +84,13 @@ class Projector(L.RayModule):
         super().__init__(volume_shape, output_shape, float(sampling_rate), jitter, max_samples, fov, near, far)
         self.mode = mode
 
-    def _determine_batch(self, volume, look_from, pose=None):
-        """-> (batched, vol ([BS,] W, D, H) view, look_from (BS, 3)); an un-batched volume is shared by all views.
-        pose = (look_at, up, fov): they join the batch rule, and a fourth result holds them as rows per view."""
-        if volume.ndim not in (4, 5) or look_from.ndim not in (1, 2):
-            raise ValueError("expected volume ([BS,]1,D,H,W) and look_from ([BS,]3)")
-        if volume.shape[-4] != 1 or look_from.shape[-1] != 3:
-            raise ValueError(f"expected volume ([BS,]1,D,H,W) and look_from ([BS,]3); got {tuple(volume.shape)}, "
-                             f"{tuple(look_from.shape)}")
+    def _batch(self, volume, look_from, pose=None):
+        """-> (batched, vol ([BS,] W, D, H) view, look_from (BS, 3), pose); an un-batched volume is shared by all views.
+        pose = (look_at, up, fov): they join the batch rule and come back as rows per view; else None."""
+        L.check_inputs("volume ([BS,]1,D,H,W) and look_from ([BS,]3)", (volume, 5, -4, 1), (look_from, 2, -1, 3))
         self._check_built_for(volume)
-        batched, _, lf, *posed = L.batch_rule(look_from, (volume, 5)) if pose is None else L.pose_rule(look_from, pose, (volume, 5))
-        return (batched, L.field_view(volume), lf, *posed)
+        batched, lf, pose = L.views(look_from, pose, (volume, 5))
+        return batched, L.field_view(volume), lf, pose
 
     @staticmethod
     def _image(out, batched):
@@ -98,13 +101,11 @@ class Projector(L.RayModule):
         """volume ([BS,]1,D,H,W), look_from ([BS,]3) -> ([BS,]1,H,W).
         look_at, up ([BS,]3), fov ([BS,] degrees): the free camera (pose.py) and its gradients, as
         Raycaster.forward; all None: the fixed camera."""
-        if L.has_pose(look_at, up, fov):
-            from .pose import PoseProjectFunction
-            batched, vol, lf, pose = self._determine_batch(volume, look_from, (look_at, up, fov))
-            return self._image(PoseProjectFunction.apply(self, vol, lf, *pose, batched, self.jitter), batched)
-        batched, vol, lf = self._determine_batch(volume, look_from)
-        res = ProjectFunction.apply(self, vol, lf, batched, self.jitter)
-        return self._image(res, batched)
+        batched, vol, lf, pose = self._batch(volume, look_from, L.pose_or_none(look_at, up, fov))
+        if pose is None:
+            return self._image(ProjectFunction.apply(self, vol, lf, batched, self.jitter), batched)
+        from .pose import PoseProjectFunction
+        return self._image(PoseProjectFunction.apply(self, vol, lf, *pose, batched, self.jitter), batched)
 
     def extra_repr(self):
         return (f"Volume ({self.volume_shape}), Output ({self.output_shape}), mode = {self.mode}, "

@@ -61,25 +61,19 @@ class Tf2dRaycastFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, rc, volume, tf2d, look_from, sampling_rate, batched, jitter=True, pose=None):
-        volume, cam, _, rays = L.diff_rays(volume, look_from, jitter, rc.output_shape, sampling_rate, rc.fov, rc.near, pose)[:4]
         tf2d = tf2d.float().contiguous()
-        out, steps = F.march_tf2d_fwd(volume, tf2d, cam, *rays, rc.max_samples, sampling_rate, rc.g_scale, N.DR_MODE_DIFF)
-        ctx.save_for_backward(volume, tf2d, cam, *rays, out)
-        ctx.rc, ctx.sampling_rate, ctx.batched = rc, sampling_rate, batched
-        rc._steps = L.unbatch(steps, batched)
-        return L.unbatch(out, batched)
+        march = lambda volume, cam, rays: F.march_tf2d_fwd(volume, tf2d, cam, *rays, rc.max_samples, sampling_rate, rc.g_scale,
+                                                           N.DR_MODE_DIFF)
+        return L.march_forward(ctx, rc, march, volume, (tf2d,), look_from, sampling_rate, batched, jitter, pose)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
-        volume, tf2d, cam, e, x, r, n, out = ctx.saved_tensors
+        (volume, tf2d, e, x, r, n, out), cam, *_ = L.saved_rays(ctx)
         g = grad_output if ctx.batched else grad_output[None]
         dv, dt = F.march_tf2d_bwd(volume, tf2d, cam, e, x, r, n, ctx.rc.max_samples, ctx.sampling_rate, ctx.rc.g_scale, g, out,
                                   want_vol=ctx.needs_input_grad[1], want_tf=ctx.needs_input_grad[2])
-        # the plain kernels propagate NaN like the reference: VR.py:463-464,474-475's nan_to_num, as RaycastFunction does
-        dv = None if dv is None else torch.nan_to_num(dv)
-        dt = None if dt is None else torch.nan_to_num(dt)
-        return None, dv, dt, None, None, None, None, None
+        return None, L.sanitised(dv), L.sanitised(dt), None, None, None, None, None
 
 
 class Raycaster2D(L.RayModule):
@@ -101,19 +95,15 @@ class Raycaster2D(L.RayModule):
         self.tf_shape = tuple(int(v) for v in tf_shape)
         self.g_scale = g
 
-    def _determine_batch(self, volume, tf2d, look_from, pose=None):
-        """-> (batched, vol ([BS,] W, D, H) view, tf2d ([BS,] RV, RG, 4) view, look_from (BS, 3)); un-batched inputs are
-        shared by all views. pose = (look_at, up, fov): they join the batch rule, and a fifth result holds them as rows per view."""
-        if volume.ndim not in (4, 5) or tf2d.ndim not in (3, 4) or look_from.ndim not in (1, 2):
-            raise ValueError("expected volume ([BS,]1,D,H,W), tf2d ([BS,]4,RV,RG), look_from ([BS,]3)")
-        if volume.shape[-4] != 1 or tf2d.shape[-3] != 4 or look_from.shape[-1] != 3:
-            raise ValueError(f"expected volume ([BS,]1,D,H,W), tf2d ([BS,]4,RV,RG), look_from ([BS,]3); got "
-                             f"{tuple(volume.shape)}, {tuple(tf2d.shape)}, {tuple(look_from.shape)}")
+    def _batch(self, volume, tf2d, look_from, pose=None):
+        """-> (batched, vol ([BS,] W, D, H) view, tf2d ([BS,] RV, RG, 4) view, look_from (BS, 3), pose); un-batched inputs are
+        shared by all views. pose = (look_at, up, fov): they join the batch rule and come back as rows per view; else None."""
+        L.check_inputs("volume ([BS,]1,D,H,W), tf2d ([BS,]4,RV,RG), look_from ([BS,]3)", (volume, 5, -4, 1), (tf2d, 4, -3, 4),
+                       (look_from, 2, -1, 3))
         if tuple(tf2d.shape[-2:]) != self.tf_shape:
             raise ValueError(f"tf2d has (RV, RG) = {tuple(tf2d.shape[-2:])}, the module was built for {self.tf_shape}")
-        inputs = ((volume, 5), (tf2d, 4))
-        batched, _, lf, *posed = L.batch_rule(look_from, *inputs) if pose is None else L.pose_rule(look_from, pose, *inputs)
-        return (batched, L.field_view(volume), tf2d.movedim(-3, -1), lf, *posed)
+        batched, lf, pose = L.views(look_from, pose, (volume, 5), (tf2d, 4))
+        return batched, L.field_view(volume), tf2d.movedim(-3, -1), lf, pose
 
     def forward(self, volume, tf2d, look_from, look_at=None, up=None, fov=None):
         """volume ([BS,]1,D,H,W), tf2d ([BS,]4,RV,RG), look_from ([BS,]3) -> ([BS,]4,H,W).
@@ -122,26 +112,17 @@ class Raycaster2D(L.RayModule):
         if torch.is_grad_enabled() and look_from.requires_grad:
             raise ValueError("Raycaster2D has no gradient w.r.t. look_from: use volume_raycaster.Raycaster (1-D transfer "
                              "function) for camera gradients, or pass look_from.detach()")
-        if L.has_pose(look_at, up, fov):
-            L.refuse_pose_grad("Raycaster2D", look_at=look_at, up=up, fov=fov)
-            batched, vol, tf, lf, pose = self._determine_batch(volume, tf2d, look_from, (look_at, up, fov))
-            return self._image(Tf2dRaycastFunction.apply(self, vol, tf, lf, self.sampling_rate, batched, self.jitter, pose), batched)
-        batched, vol, tf, lf = self._determine_batch(volume, tf2d, look_from)
-        res = Tf2dRaycastFunction.apply(self, vol, tf, lf, self.sampling_rate, batched, self.jitter)
+        L.refuse_pose_grad("Raycaster2D", look_at=look_at, up=up, fov=fov)
+        batched, vol, tf, lf, pose = self._batch(volume, tf2d, look_from, L.pose_or_none(look_at, up, fov))
+        res = Tf2dRaycastFunction.apply(self, vol, tf, lf, self.sampling_rate, batched, self.jitter, pose)
         return self._image(res, batched)
 
     def raycast_nondiff(self, volume, tf2d, look_from, sampling_rate=None, look_at=None, up=None, fov=None):
         """Non-differentiable render (never jittered); default rate 4x the module's, as Raycaster.raycast_nondiff."""
-        pose = None
-        if L.has_pose(look_at, up, fov):
-            batched, vol, tf, lf, pose = self._determine_batch(volume, tf2d, look_from, (look_at, up, fov))
-        else:
-            batched, vol, tf, lf = self._determine_batch(volume, tf2d, look_from)
-        with self._nondiff_rays(vol, lf, sampling_rate, pose) as (sr, vol, cam, rays, *_):
-            out, steps = F.march_tf2d_fwd(vol, tf.float().contiguous(), cam, *rays, self.max_samples, sr, self.g_scale,
-                                          N.DR_MODE_NONDIFF)
-            self._steps = L.unbatch(steps, batched)
-            return L.image(L.unbatch(out, batched))
+        batched, vol, tf, lf, pose = self._batch(volume, tf2d, look_from, L.pose_or_none(look_at, up, fov))
+        march = lambda vol, cam, rays, sr: F.march_tf2d_fwd(vol, tf.float().contiguous(), cam, *rays, self.max_samples, sr,
+                                                            self.g_scale, N.DR_MODE_NONDIFF)
+        return self._raycast_nondiff(vol, lf, sampling_rate, pose, batched, march)
 
     def extra_repr(self):
         return (f"Volume ({self.volume_shape}), Output Render ({self.output_shape}), TF2D ({self.tf_shape}), "
