@@ -1,6 +1,7 @@
 """Depth moments, DESIGN.md D18, without a GPU: the C ABI and its argument checks, the float64 transliteration
-(tests/depth_reference.py) against central differences, the conditions every camera case of the GPU file owes the conditioned
-pass, the two torch helpers, and the module's argument checks."""
+(tests/depth_reference.py) against central differences, the conditions every camera case of the GPU files owes the conditioned
+pass, the premises of the edge scenes (test_gpu_depth_edges.py) and three mutations their rules must reject, the two torch
+helpers, and the module's argument checks."""
 import ctypes
 import math
 import os
@@ -176,10 +177,71 @@ CONDITIONED = DG.conditioned_entries()
 
 @pytest.mark.parametrize("case", sorted(CONDITIONED))
 def test_camera_cases_meet_the_conditions_of_the_conditioned_pass(case):
-    """Every camera case of test_gpu_depth.py keeps 80 % of its n > 1 rays in the conditioned pass, and the float32
+    """Every camera case of test_gpu_depth.py and (edge-...) of test_gpu_depth_edges.py keeps 80 % of its n > 1 rays in the conditioned pass, and the float32
     transliteration's error over them is within the rule's floor: from the references alone."""
     entries, key, columns = CONDITIONED[case]
     K.check_conditions(entries(), key, columns, lit=False)
+
+
+EDGE_FORWARD = DG.edge_forward_keys()
+
+
+@pytest.mark.parametrize("key", EDGE_FORWARD, ids=[DG.edge_id(k) for k in EDGE_FORWARD])
+def test_edge_scenes_keep_their_premises(key):
+    """Every forward scene of test_gpu_depth_edges.py on the references' own ray buffers: the two transliterations agree on
+    KEEP of the n > 1 rays (reference_state's mask), and the scene still exercises what it is there for (check_premise: the
+    clip and termination counts, zero and out-of-range samples, the sample counts). The planes' scenes have axial rays."""
+    inp, ref, ref32 = DG.edge_refs(key)
+    live = ref["n"] > 1
+    assert (DG.PG.keep(ref, ref32) & live).sum() >= DG.KEEP * live.sum() > 0
+    DG.check_premise(key, inp, ref["entry"], ref["exit"], ref["rays"], ref["n"], ref["steps"])
+    if key[1] in ("i_on_x_axis", "g_plane_y0"):
+        assert DG.axial_rays(ref).sum() > 0
+    if key[0] == "tiny":   # live rays and non-zero gradients in every one
+        assert np.abs(ref["dpose_ray"][..., :3]).max() > 0
+
+
+def test_edge_cases_stand_on_the_table_tiers_they_name():
+    DG.table_tiers()
+    for how in DG.BATCH_KINDS:   # a batched launch: three views, jitter on, view_base 5, tables or volumes of their own
+        inps = [DG.edge_inputs(k) for k in DG.batch_keys(how, True)]
+        assert [int(i["view"]) for i in inps] == [5, 6, 7] and all(int(i["jitter_seed"]) != 0 for i in inps)
+        own = "tf" if how == "tables" else "vol"
+        assert all(np.abs(inps[a][own] - inps[b][own]).max() > 0.01 for a in range(3) for b in range(a))
+        assert all(np.array_equal(inps[0][k], i[k]) for i in inps for k in ("vol", "tf") if k != own)
+
+
+def test_the_edge_rules_reject_plausible_mutations():
+    """Arrays in the kernel's place, as test_the_conditioned_rule_rejects_a_one_percent_error feeds them: the float32
+    transliteration passes each rule and a plausible mistake does not. A camera gradient 1 % too large under the max_samples
+    clip; d_tf shifted by one texel at R = 9793; view 1's pose gradient computed with view 0's table."""
+    from light_gpu import bound
+    for posed in (False, True):
+        _, ref, ref32 = DG.edge_refs(DG.variant("c_clip", posed))
+        key = "dpose_ray" if posed else "dcam_ray"
+        r64, r32 = (ref, ref32) if posed else (DG.look_from_columns(ref), DG.look_from_columns(ref32))
+        for mask in (DG.PG.keep(ref, ref32) & (ref["n"] > 1), DG.good_rays(ref, ref32, posed)):
+            m = mask[..., None]
+            DG.rule(r32[key] * m, (r32[key] * m).sum((0, 1)), ref, ref32, mask, posed)
+            wrong = 1.01 * r64[key] * m
+            with pytest.raises(AssertionError):
+                DG.rule(wrong, wrong.sum((0, 1)), ref, ref32, mask, posed)
+
+    inp, ref, _ = DG.edge_refs(DG.variant("d_jitter", table=("ramp", DG.CAM_TABLE_R[1])))
+    args = (inp["vol"], inp["tf"], inp["look_from"][None], *(ref[k][None] for k in ("entry", "exit", "rays", "n")),
+            inp["grad_out"][None], int(inp["max_samples"]), float(inp["sr"]))
+    d64, d32 = DR.run(*args)["dtf"][:, 3], DR.run(*args, dtype=torch.float32)["dtf"][:, 3]
+    bound(d32, d64, d32, "dtf alpha, the float32 transliteration")
+    with pytest.raises(AssertionError):
+        bound(np.roll(d64, 1), d64, d32, "dtf alpha, one texel on")
+
+    keys = DG.batch_keys("tables", True)
+    inp1, ref, ref32 = DG.edge_refs(keys[1])
+    wrong = DR.run_case(dict(inp1, tf=DG.edge_inputs(keys[0])["tf"]))["dpose_ray"]
+    for mask in (DG.PG.keep(ref, ref32) & (ref["n"] > 1), DG.good_rays(ref, ref32, True)):
+        m = mask[..., None]
+        with pytest.raises(AssertionError):
+            DG.rule(wrong * m, (wrong * m).sum((0, 1)), ref, ref32, mask, True)
 
 
 # --- 4. expected_depth and depth_variance -----------------------------------------------------------------------------------------

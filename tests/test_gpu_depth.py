@@ -96,26 +96,7 @@ def test_alpha_and_steps_are_the_plain_colour_marchs_bits(hiplib, name):
 
 # ---- 3. d_tf through the three table tiers ---------------------------------------------------------------------------------------
 
-def _small_scene(R=8, views=1, per_view=False, seed=0):
-    """A 10x9x11 volume under a 12x10 image: numpy inputs rounded to float32 (vol [V,]VX,VY,VZ, tf [V,]R,4, cams (V,3), g)."""
-    rng = np.random.RandomState(100 + seed)
-    lead = (views,) if per_view else ()
-    vol = PG.F32(np.clip(0.5 + 0.25 * rng.standard_normal(lead + (10, 9, 11)), 0.0, 1.0))
-    tf = rng.uniform(0.05, 0.95, lead + (R, 4))
-    tf[..., 3] = np.linspace(0.02, 0.3, R) * (1.0 + 0.3 * rng.uniform(-1.0, 1.0, lead + (R,)))
-    cams = PG.F32(np.array([(2.2, 1.1, 1.7), (-1.6, 1.3, 2.0), (0.4, -2.1, 1.9)][:views]))
-    return vol, PG.F32(tf), cams, PG.F32(rng.standard_normal((views, 12, 10, 4)))
-
-
-def _small_state(vol, tf, cams, g, S=512, sr=1.0, seed=0):
-    """forward_state for _small_scene: device tensors, the kernels' buffers and forward, reference_state on them."""
-    F = _F()
-    dvol, dtf, cam = dev(vol), dev(tf), dev(cams)
-    rays = F.ray_setup(cam, (12, 10), vol.shape[-3:], sr, jitter_seed=seed)
-    out, steps = F.march_depth_fwd(dvol, dtf, cam, *rays, S, sr)
-    e, x, r, n = rays
-    st = DG.reference_state(vol, tf, cams, C(e), C(x), C(r), n.cpu().numpy(), g, S, sr, steps.cpu().numpy())
-    return dict(vol=dvol, tf=dtf, cam=cam, rays=rays, out=out, steps=steps, st=st, S=S, sr=sr)
+_small_scene, _small_state, _raw_bwd = DG.small_scene, DG.small_state, DG.raw_bwd   # (shared with test_gpu_depth_edges.py)
 
 
 @pytest.mark.parametrize("R", [8, 3393, 10177])
@@ -134,18 +115,6 @@ def test_d_tf_through_the_three_table_tiers(hiplib, R):
 
 
 # ---- 4. accumulation and batching ------------------------------------------------------------------------------------------------
-
-def _raw_bwd(fs, go, d_vol, d_tf):
-    """dr_march_depth_bwd on the caller's own output buffers (functional.march_depth_bwd allocates zeroed ones); shared inputs."""
-    from differender_amd import _native as N
-    F = _F()
-    cam, V, W, H, rargs = F._ray_args(fs["vol"], fs["cam"], *fs["rays"])
-    rc = N.lib().dr_march_depth_bwd(*F._vol_args(fs["vol"], V), *F._tf_args(fs["tf"], V), *rargs, fs["S"], fs["sr"], go.data_ptr(),
-                                    fs["out"].data_ptr(), d_vol.data_ptr(), *d_vol.stride(), 0, d_tf.data_ptr(), 0,
-                                    torch.cuda.current_stream().cuda_stream)
-    assert rc == 0
-    torch.cuda.synchronize()
-
 
 def test_prefilled_gradients_come_back_as_prefill_plus_gradient(hiplib):
     fs = _small_state(*_small_scene())
