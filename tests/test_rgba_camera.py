@@ -91,7 +91,9 @@ def test_default_pose_columns_are_the_fixed_cameras():
 
 def _conditioned_cases():
     import test_gpu_rgba_camera as TG
-    return TG.CONDITIONED
+    import test_gpu_rgba_camera_edges as TE
+    assert not set(TG.CONDITIONED) & set(TE.CONDITIONED)
+    return dict(TG.CONDITIONED, **TE.CONDITIONED)
 
 
 CONDITIONED = _conditioned_cases()
@@ -99,12 +101,48 @@ CONDITIONED = _conditioned_cases()
 
 @pytest.mark.parametrize("case", sorted(CONDITIONED))
 def test_cases_keep_enough_well_conditioned_rays(case):
-    """What test_gpu_rgba_camera.py feeds to the conditioned pass (pose_gpu.well_conditioned), held to its conditions without a
-    GPU: the rays on which the float32 and the float64 reference agree to 1e-4 of each pose tensor's scale are at least 80 %
-    of the n > 1 rays, and err32 over them is within 1e-4 of the scale."""
+    """What test_gpu_rgba_camera.py and test_gpu_rgba_camera_edges.py feed to the conditioned pass (pose_gpu.well_conditioned),
+    held to its conditions without a GPU: the rays on which the float32 and the float64 reference agree to 1e-4 of each pose
+    tensor's scale are at least 80 % of the n > 1 rays, and err32 over them is within 1e-4 of the scale. (The scenes of the
+    look_from entry, under the default pose, are held to all four tensors' conditions: no fewer rays than its own three
+    columns would leave out.)"""
     import camgrad_gpu as K
     import pose_gpu as PG
     K.check_conditions(CONDITIONED[case](), "dpose_ray", PG.COLUMNS, lit=False)   # (D16: no lighting, no kinks)
+
+
+def test_the_conditioned_rule_rejects_a_one_percent_error_in_a_multi_workgroup_total():
+    """The 17 x 19 scene of test_gpu_rgba_camera_edges.py (three workgroups), with arrays in the kernel's place: eight rays put
+    err32 at 0.9 % (d look_at) and 2.4 % (d up) of the scale, and the rule over all kept rays accepts gradients of those two
+    tensors that are 1 % off in every column of every ray, with a total that is their sum; over the well-conditioned rays it
+    does not (camgrad_gpu.mutation_check, tensor by tensor as pose_rule judges them). d look_from and d fov have an err32 of
+    0.6 % and 0.2 % there: the first pass rejects their 1 % error already (the total's and the per-ray bound), and the
+    conditioned pass rejects it as well."""
+    import camgrad_gpu as K
+    import pose_gpu as PG
+    import test_gpu_rgba_camera_edges as TE
+    _, ref, ref32 = TE._edge("wg3_17x19")
+    assert ref["n"].shape == (17, 19)
+    keep = PG.keep(ref, ref32)
+    good = PG.well_conditioned(ref, ref32, keep, lit=False)
+    assert good.sum() < (keep & (ref["n"] > 1)).sum()   # there are ill-conditioned rays to leave out
+
+    def rule_of(sl):
+        three = lambda r: {"n": ref["n"], "dcam_ray": PG._three(r["dpose_ray"], sl)}
+        return lambda ray, total, ref, ref32, mask: K.d8_rule(PG._three(ray, sl), PG._three(total, sl), three(ref), three(ref32), mask)
+
+    for name, sl in PG.COLUMNS:
+        if name in ("look_at", "up"):
+            K.mutation_check(rule_of(sl), ref["dpose_ray"], ref32["dpose_ray"], ref, ref32, keep, good)
+        else:
+            wrong = 1.01 * ref["dpose_ray"] * good[..., None]
+            with pytest.raises(AssertionError):
+                rule_of(sl)(wrong, wrong.sum((0, 1)), ref, ref32, good)
+            right = ref32["dpose_ray"] * good[..., None]
+            rule_of(sl)(right, right.sum((0, 1)), ref, ref32, good)
+    with pytest.raises(AssertionError):   # and pose_rule as a whole, over the well-conditioned rays
+        wrong = 1.01 * ref["dpose_ray"] * good[..., None]
+        PG.pose_rule(wrong, wrong.sum((0, 1)), ref, ref32, good)
 
 
 # --- 2. the C ABI -----------------------------------------------------------------------------------------------------------
