@@ -466,7 +466,8 @@ static int fill_tv(TVArgs &a, const void *vol, int vol_dtype, int B, int D, int 
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return DR_EINVAL;
     if (vol_dtype != DR_F32 && vol_dtype != DR_F16) return DR_EINVAL;
     if (norm != DR_TV_L1 && norm != DR_TV_ISO && norm != DR_TV_SQ) return DR_EINVAL;
-    if (!std::isfinite(eps) || (norm == DR_TV_ISO && !(eps > 0.0))) return DR_EINVAL;
+    // the kernels add (float)(eps * eps): where that is 0, a flat voxel's ISO flux is 0 * inf
+    if (!std::isfinite(eps) || (norm == DR_TV_ISO && !(eps > 0.0 && (float)(eps * eps) > 0.0f))) return DR_EINVAL;
     a = TVArgs{};
     a.vol = vol; a.vol_dtype = vol_dtype; a.B = B; a.D = D; a.H = H; a.W = W;
     for (int i = 0; i < 4; ++i) a.strides[i] = strides4[i];

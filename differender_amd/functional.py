@@ -893,6 +893,17 @@ def _dense(t):
     return True
 
 
+def _disjoint(t):
+    """True if no two elements of t lie on one storage element, gaps allowed (a padded or sliced buffer): taken by |stride|,
+    every axis steps over all that the smaller ones span. Sufficient, not necessary: interleaved layouts are turned down."""
+    span = 1
+    for st, sz in sorted((abs(st), sz) for st, sz in zip(t.stride(), t.shape) if sz > 1):
+        if st < span:
+            return False
+        span += st * (sz - 1)
+    return True
+
+
 def _loss_inputs(out, reference):
     if out.ndim != 4 or reference.shape != out.shape:
         raise ValueError("the DSSIM + MSE loss expects two (N, C, H, W) tensors of the same shape")
@@ -1038,8 +1049,10 @@ def _tv_config(norm, eps):
     if norm not in _TV_NORMS:
         raise ValueError(f"norm must be one of {sorted(_TV_NORMS)}, got {norm!r}")
     eps = float(eps)
-    if not math.isfinite(eps) or (norm == "iso" and not eps > 0.0):
-        raise ValueError(f"eps must be finite (and > 0 for norm='iso'), got {eps}")
+    # the kernels add (float)(eps * eps): at or below 2^-150 (eps below about 2.6e-23) it rounds to 0, and a flat voxel's flux is
+    # 0 * inf
+    if not math.isfinite(eps) or (norm == "iso" and not (eps > 0.0 and eps * eps > 2.0 ** -150)):
+        raise ValueError(f"eps must be finite (and for norm='iso' > 0 with a square that float32 holds, eps >= 3e-23), got {eps}")
     return _TV_NORMS[norm], eps
 
 
@@ -1083,8 +1096,9 @@ def tv3d_fwd(vol, norm="l1", eps=1e-3):
 def tv3d_bwd(vol, upstream=None, scale=1.0, norm="l1", eps=1e-3, out=None, accumulate=False):
     """Gradient of tv3d_fwd's sum (dr_tv3d_bwd): out = (out if accumulate else 0) + upstream * scale * dTV/dvol, float32, shaped
     like vol. `upstream`: one float32 on the device (None = 1), read there (no host synchronisation). `out` may be any
-    float32 tensor of vol's shape whose elements do not overlap (e.g. the d_volume of the march); None allocates one in vol's
-    stride order. Bitwise deterministic."""
+    float32 tensor of vol's shape whose elements do not overlap (e.g. the d_volume of the march; a padded or sliced view keeps
+    what lies between its elements); None allocates one in vol's stride order. Bitwise deterministic. norm="iso" needs an eps
+    whose square float32 holds (eps >= 3e-23): a smaller one raises ValueError."""
     n, e = _tv_config(norm, eps)
     vol, tag, (b, d, h, w, strides) = _tv_volume(vol)
     if upstream is not None:
@@ -1100,7 +1114,7 @@ def tv3d_bwd(vol, upstream=None, scale=1.0, norm="l1", eps=1e-3, out=None, accum
     if out.shape != vol.shape or out.dtype != torch.float32 or out.device != vol.device:
         raise ValueError("out must be a float32 tensor of vol's shape on vol's device")
     gstrides = _tv_strides(out)
-    if gstrides is None or not _dense(out):
+    if gstrides is None or not _disjoint(out):
         raise ValueError("out must not have overlapping elements, and its leading axes must collapse into one stride")
     with torch.cuda.device(vol.device):
         rc = N.lib().dr_tv3d_bwd(vol.data_ptr(), tag, b, d, h, w, strides, n, e,

@@ -222,7 +222,8 @@ class _FusedTV3D(torch.autograd.Function):
 def fused_tv3d_loss(vol, norm="l1", eps=1e-3, reduction="mean"):
     """tv3d on the HIP kernels: a 0-d float32 tensor, differentiable w.r.t. vol (the gradient comes back in vol's dtype and
     shape). vol: (..., D, H, W) float32 or float16 on a ROCm GPU (there is no CPU path), any strides -- Raycaster's user
-    layouts (1, D, H, W) and (BS, 1, D, H, W) and its permuted views included."""
+    layouts (1, D, H, W) and (BS, 1, D, H, W) and its permuted views included. norm="iso" needs an eps whose square float32
+    holds (eps >= 3e-23; the kernels add eps^2 in float32): a smaller one raises ValueError where tv3d in float32 gives NaN."""
     if vol.ndim < 3:
         raise ValueError(f"fused_tv3d_loss expects a volume (..., D, H, W), got {vol.ndim} dimensions")
     if vol.dtype not in (torch.float32, torch.float16):

@@ -364,7 +364,9 @@ int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W
  * differences d_a along each of the three axes D, H, W of every volume with the last slice repeated (so d_a = 0 at the far edge
  * and an axis of extent 1 contributes nothing; no difference crosses from one volume of the batch into the next), per voxel
  *   DR_TV_L1   |dD| + |dH| + |dW|                       (anisotropic)
- *   DR_TV_ISO  sqrt(dD^2 + dH^2 + dW^2 + eps^2)         (isotropic, Charbonnier; eps > 0)
+ *   DR_TV_ISO  sqrt(dD^2 + dH^2 + dW^2 + eps^2)         (isotropic, Charbonnier; eps > 0 and (float)(eps * eps) > 0, that is
+ *                                                        eps >= 3e-23: eps^2 is added in f32, and with 0 a flat voxel's
+ *                                                        gradient would be 0 * inf)
  *   DR_TV_SQ   dD^2 + dH^2 + dW^2                       (quadratic, Tikhonov)
  * summed over the voxels of all B volumes. Arithmetic in f32, the sum in f64.
  *   vol       DR_F32 or DR_F16, logical (B, D, H, W) with the int64 element strides strides4[4] (a host array; any order:
@@ -374,8 +376,8 @@ int dr_msssim_mse_bwd(const float *x, const float *y, int N, int C, int H, int W
  *   grad      (bwd) f32, logical (B, D, H, W) with the strides grad_strides4[4], no two voxels on one element, not aliasing vol:
  *             grad = (accumulate ? grad : 0) + (*upstream) * scale * dTV/dvol, with sign(0) = 0 for DR_TV_L1. accumulate lets a
  *             caller add the regulariser straight into the d_vol of dr_march_bwd.
- * Invalid arguments (null pointers, extents <= 0, an unknown norm or dtype, a non-finite eps or scale, eps <= 0 with DR_TV_ISO)
- * return DR_EINVAL before any HIP call. One launch each (after a memset of sum in the forward), no allocation, no host
+ * Invalid arguments (null pointers, extents <= 0, an unknown norm or dtype, a non-finite eps or scale, eps <= 0 or
+ * (float)(eps * eps) == 0 with DR_TV_ISO) return DR_EINVAL before any HIP call. One launch each (after a memset of sum in the forward), no allocation, no host
  * synchronisation; the backward has no atomics and its gradient is bitwise deterministic. */
 enum { DR_TV_L1 = 0, DR_TV_ISO = 1, DR_TV_SQ = 2 };
 int dr_tv3d_fwd(const void *vol, int vol_dtype, int B, int D, int H, int W, const int64_t *strides4,

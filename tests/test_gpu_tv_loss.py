@@ -10,55 +10,15 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+import tv_gpu
 from differender_amd import functional as F
 from differender_amd.utils import fused_tv3d_loss, tv3d
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
-NORMS = [("l1", 1e-3), ("iso", 1e-3), ("iso", 1e-1), ("sq", 1e-3)]
-
-
-def _ref(vol, norm, eps, dtype, device="cpu", reduction="mean"):
-    v = vol.detach().to(device=device, dtype=dtype).requires_grad_(True)
-    loss = tv3d(v, norm, eps, reduction)
-    loss.backward()
-    return loss.detach().double(), v.grad.detach().double()
-
-
-def _check(vol, norm, eps, reduction="mean", device="cpu", loss=None, grad=None):
-    """The kernels' loss and gradient (through fused_tv3d_loss unless given) under the D8 rule."""
-    if loss is None:
-        v = vol.detach().clone().requires_grad_(True)
-        loss = fused_tv3d_loss(v, norm, eps, reduction)
-        loss.backward()
-        assert loss.dtype == torch.float32 and loss.ndim == 0
-        assert v.grad.dtype == vol.dtype and v.grad.shape == vol.shape
-        grad = v.grad
-    l64, g64 = _ref(vol, norm, eps, torch.float64, device, reduction)
-    l32, g32 = _ref(vol, norm, eps, torch.float32, device, reduction)
-    tol = max(3 * abs(float(l32 - l64)), 2e-6 * abs(float(l64)), 1e-7)
-    loss = float(loss.detach())
-    assert abs(loss - float(l64)) <= tol, (loss, float(l64), tol)
-    gmax = float(g64.abs().max())
-    gtol = max(3 * float((g32 - g64).abs().max()), 1e-5 * gmax, 1e-30)
-    grads = [(grad, gtol)]
-    if vol.dtype == torch.float16:
-        # the autograd gradient comes back in the volume's dtype: half an f16 ulp more (2^-25 where it is subnormal); the
-        # kernel's own float32 gradient is held to the rule itself
-        scale = 1.0 / vol.numel() if reduction == "mean" else 1.0
-        grads = [(grad, gtol + 2 ** -11 * gmax + 2 ** -25), (F.tv3d_bwd(vol, scale=scale, norm=norm, eps=eps), gtol)]
-    for g, t in grads:
-        err = float((g.detach().to(device).double() - g64).abs().max())
-        assert err <= t, (err, t)
-
-
-def _vol(shape, seed=0, dtype=torch.float32, flat=False):
-    g = torch.Generator().manual_seed(seed)
-    v = torch.rand(shape, generator=g)
-    if flat:
-        v = (v * 4).floor() / 4
-    return v.to(dtype).to(DEV)
+NORMS = tv_gpu.NORMS
+_check, _vol = tv_gpu.check, tv_gpu.volume   # (shared with test_gpu_tv_edges.py)
 
 
 SHAPES = [(1, 1, 1, 1), (1, 1, 2, 3), (2, 1, 5, 33, 65), (1, 37, 129, 70), (1, 1, 64, 64, 64), (3, 17, 1, 9), (1, 70, 18, 5)]

@@ -153,7 +153,7 @@ def _call(lib, bwd, **kw):
 
 BAD = [dict(vol=None), dict(strides=None), dict(B=0), dict(D=0), dict(H=-1), dict(W=0), dict(dtype=2), dict(dtype=-1),
        dict(norm=3), dict(norm=-1), dict(eps=float("nan")), dict(eps=float("inf")), dict(norm=1, eps=0.0),
-       dict(norm=1, eps=-1e-3)]
+       dict(norm=1, eps=-1e-3), dict(norm=1, eps=1e-30), dict(norm=1, eps=2.0 ** -75)]   # (the last two: eps^2 is 0 in float32)
 
 
 @pytest.mark.parametrize("bwd", [False, True])
@@ -170,6 +170,43 @@ def test_bad_forward_arguments(hiplib, bad):
 @pytest.mark.parametrize("bad", [dict(grad=None), dict(gstrides=None), dict(scale=float("nan")), dict(scale=float("inf"))])
 def test_bad_backward_arguments(hiplib, bad):
     assert _call(hiplib, True, **bad) == -1
+
+
+def test_iso_eps_whose_square_float32_drops_and_gradient_buffer_layouts():
+    """The argument rules that need no GPU: "iso" turns down an eps whose square is 0 in float32 (2^-75 squared is the tie that
+    rounds to 0) and takes one whose square is subnormal; `out` may have gaps but no two voxels on one element."""
+    from differender_amd import functional as F
+    v = torch.rand(1, 4, 5, 6)
+    for eps in (0.0, -1e-3, 1e-30, 2.0 ** -75):
+        with pytest.raises(ValueError):
+            F.tv3d_fwd(v, "iso", eps)
+        with pytest.raises(ValueError):
+            F.tv3d_bwd(v, norm="iso", eps=eps)
+    for norm, eps in (("iso", 1e-20), ("iso", 2.7e-23), ("l1", 0.0), ("sq", 1e-30)):
+        assert F._tv_config(norm, eps)[1] == eps
+    buf = torch.zeros(4, 5, 8)
+    for ok in (buf[..., :6], buf[:, ::2], buf.permute(2, 0, 1), buf[..., 1:7].permute(1, 2, 0)):
+        assert F._disjoint(ok)
+    for bad in (buf[:1].expand(3, 5, 8), buf.as_strided((4, 5, 6), (6, 1, 1)), buf.as_strided((4, 5, 6), (29, 6, 1))):
+        assert not F._disjoint(bad)
+
+
+def test_restated_plan_stands_on_the_kernels_constants():
+    """tests/tv_gpu.py restates tv_loss.hip's launch plan for test_gpu_tv_edges.py to assert its premises against: the constants
+    are read from the source here, so one that moves fails this test instead of leaving the edge cases on another path; and the
+    chunk cases' premises hold without a GPU."""
+    import test_gpu_tv_edges as E
+    import tv_gpu as T
+    src = open(os.path.join(ROOT, "differender_amd", "csrc", "tv_loss.hip")).read()
+    got = {k: int(v) for k, v in re.findall(r"\b(NT|VX|TX|TY|TARGET_BLOCKS|ZMIN) = (\d+)", src)}
+    assert got == dict(NT=T.NT, VX=T.VX, TX=T.TX, TY=T.TY, TARGET_BLOCKS=T.TARGET_BLOCKS, ZMIN=T.ZMIN)
+    for shape, want in E.CHUNKS.items():
+        p = T.plan_of(torch.empty(shape))
+        assert (p.tiles, p.want, p.zc, p.chunks) == want, shape
+    # the alignment rule: x of stride 1, the other strides multiples of 4 unless the axis has extent 1, the pointer on 4 elements
+    assert T.aligned4(16, 4, (0, 1, 72, 1296), (1, 61, 18, 20)) and not T.aligned4(16, 4, (0, 1, 70, 1260), (1, 68, 18, 20))
+    assert T.aligned4(8, 2, (0, 1, 72, 1296), (1, 61, 18, 20)) and not T.aligned4(4, 2, (0, 1, 72, 1296), (1, 61, 18, 20))
+    assert T.aligned4(16, 4, (0, 1, 70, -1296), (1, 3, 1, 20)) and not T.aligned4(16, 4, (0, -1, 72, 1296), (1, 61, 18, 20))
 
 
 def test_fused_loss_has_no_cpu_path():
