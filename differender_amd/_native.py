@@ -98,6 +98,13 @@ SIGNATURES = {
                                     _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P]),
     "dr_march_depth_bwd_pose": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _L, _P, _P, _P, _P, _P,
                                      _I, _I, _I, _I, _F, _D, _D, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the ray bundle: origins, dirs and N in the camera's and the image's place; one volume, one table
+    "dr_bundle_setup": (_I, [_P, _P, _L, _I, _I, _I, _F, _F, _U, _U, _P, _P, _P, _P]),
+    "dr_march_bundle_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P]),
+    "dr_march_bundle_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P,
+                                 _P, _L, _L, _L, _P, _P]),
+    "dr_march_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F,
+                                      _P, _F, _U, _U, _P, _P, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

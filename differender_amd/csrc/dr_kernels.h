@@ -191,6 +191,24 @@ __attribute__((weak)) int launch_march_depth_fwd(const MarchArgs &a, hipStream_t
 __attribute__((weak)) int launch_march_depth_bwd(const MarchArgs &a, hipStream_t stream);
 __attribute__((weak)) int launch_march_depth_bwd_cam(const MarchArgs &a, const CamArgs &c, hipStream_t stream);
 
+// The differentiable 1-D TF march over a bundle of rays (march_bundle.hip): what dr_bundle_setup and
+// dr_march_bundle_fwd / _bwd / _bwd_rays take beside their MarchArgs (the 1-D march's with n_views = 1, W = N, H = 1, cam the
+// origins and rays the directions; no workspace, variant, mode or bands)
+struct BundleArgs {
+    const float *origins;              // [N][3]
+    int N;
+    float t_near;                      // -INFINITY: off
+    uint32_t jitter_seed, ray_base;    // setup and ray gradient
+    const int32_t *steps;              // ray gradient: the forward's live samples per ray
+    float *d_origins, *d_dirs;         // ray gradient: [N][3] each, overwritten
+};
+// weak, as launch_camera_grad: capi.o must load in a library linked without march_bundle.o
+__attribute__((weak)) int launch_bundle_setup(const BundleArgs &b, const float *dirs, int VX, int VY, int VZ, float sr, float *entry,
+                                              float *exit_, int32_t *nsamp, hipStream_t stream);
+__attribute__((weak)) int launch_march_bundle_fwd(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
+__attribute__((weak)) int launch_march_bundle_bwd(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
+__attribute__((weak)) int launch_bundle_ray_grad(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -18,6 +18,7 @@ __all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd",
            "project_bwd_cam", "new_jitter_seed", "alloc_workspace", "workspace_stats", "evaluated_samples",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
+__all__ += ["bundle_setup", "march_bundle_fwd", "march_bundle_bwd", "march_bundle_bwd_rays"]
 
 
 def _stream():
@@ -780,6 +781,96 @@ def march_depth_bwd_cam(vol, tf, cam, entry, exit_, rays, n, steps, max_samples,
     head = (*_vol_args(vol, V), *_tf_args(tf, V), *rargs, int(max_samples), float(sampling_rate))
     return _camera_bwd("dr_march_depth_bwd", vol, n, head, (fov_deg, near, jitter_seed, view_base),
                        (steps.data_ptr(), grad_out.data_ptr(), out.data_ptr()), per_ray, pose, fov_v)
+
+
+def _t_near(t_near):
+    """t_near as the C ABI takes it: None = off (-inf)."""
+    return -math.inf if t_near is None else float(t_near)
+
+
+def _bundle_rays(origins, dirs):
+    """A bundle's origins and directions (N, 3) as the float32 contiguous tensors the kernels read -> (origins, dirs, N). The
+    caller keeps them until its call has been issued."""
+    _require_gpu(origins, "origins")
+    _require_gpu(dirs, "directions")
+    if origins.ndim != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape or origins.shape[0] < 1:
+        raise ValueError(f"origins and directions must both be (N, 3) with N >= 1, got {tuple(origins.shape)} and "
+                         f"{tuple(dirs.shape)}")
+    if origins.device != dirs.device:
+        raise ValueError(f"origins and directions live on different devices: {origins.device}, {dirs.device}")
+    return origins.to(torch.float32).contiguous(), dirs.to(torch.float32).contiguous(), int(origins.shape[0])
+
+
+def bundle_setup(origins, dirs, vol_shape, sampling_rate, t_near=None, jitter_seed=0, ray_base=0):
+    """ray_setup for a bundle of rays (dr_bundle_setup): origins, dirs (N, 3) in look_from's world coordinates,
+    the directions of unit length and used as given -> entry, exit (N,) float32 and n (N,) int32. For the origin and direction
+    of a ray_setup pixel these are that pixel's, bit for bit. t_near: None marches the reference's whole line through the box
+    (also behind an origin inside it); a number clamps the entry distance from below before the hit test and the sample count
+    (0: a ray). jitter_seed != 0 draws ray p's offset from (jitter_seed, ray_base, p)."""
+    origins, dirs, n_rays = _bundle_rays(origins, dirs)
+    dev = origins.device
+    entry = torch.empty((n_rays,), dtype=torch.float32, device=dev)
+    exit_ = torch.empty((n_rays,), dtype=torch.float32, device=dev)
+    n = torch.empty((n_rays,), dtype=torch.int32, device=dev)
+    VX, VY, VZ = (int(s) for s in vol_shape)
+    _call("dr_bundle_setup", dev, origins.data_ptr(), dirs.data_ptr(), n_rays, VX, VY, VZ, float(sampling_rate), _t_near(t_near),
+          int(jitter_seed) & 0xFFFFFFFF, int(ray_base) & 0xFFFFFFFF, entry.data_ptr(), exit_.data_ptr(), n.data_ptr())
+    return entry, exit_, n
+
+
+def _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate):
+    """What the three bundle marches start with -> (origins, dirs, N, their C-ABI arguments up to sampling_rate): one volume
+    (VX, VY, VZ) with any strides and one table (R, 4)."""
+    _require_gpu(vol, "volume")
+    origins, dirs, n_rays = _bundle_rays(origins, dirs)
+    if vol.ndim != 3 or tf.ndim != 2:
+        raise ValueError("a bundle is marched through one volume (VX,VY,VZ) and one table (R,4)")
+    for name, t in (("entry", entry), ("exit", exit_), ("n", n)):
+        if tuple(t.shape) != (n_rays,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be bundle_setup's contiguous ({n_rays},) buffer, got {tuple(t.shape)}")
+    vargs, targs = _vol_args(vol, 1), _tf_args(tf, 1)
+    return origins, dirs, n_rays, (*vargs[:8], *targs[:2], origins.data_ptr(), dirs.data_ptr(), entry.data_ptr(), exit_.data_ptr(),
+                                   n.data_ptr(), n_rays, int(max_samples), float(sampling_rate))
+
+
+def march_bundle_fwd(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate, want_steps=True):
+    """The differentiable march of a bundle's rays (dr_march_bundle_fwd): march_fwd's DR_MODE_DIFF samples with
+    the ray's origin in the camera's place and the light at origin + (0, 1, 0). Returns out (N, 4) and steps (N,) int32 (or
+    None): for a pinhole view's rays, the bits of march_fwd(variant=DR_VARIANT_BASELINE)."""
+    origins, dirs, n_rays, head = _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    out = torch.empty((n_rays, 4), dtype=torch.float32, device=vol.device)
+    steps = torch.empty((n_rays,), dtype=torch.int32, device=vol.device) if want_steps else None
+    _call("dr_march_bundle_fwd", vol.device, *head, out.data_ptr(), _ptr(steps))
+    return out, steps
+
+
+def march_bundle_bwd(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate, grad_out, out, want_vol=True,
+                     want_tf=True):
+    """Adjoint of march_bundle_fwd w.r.t. vol and tf (dr_march_bundle_bwd). Returns (d_vol, d_tf), either None when not wanted.
+    NaN propagates (the plain kernels' convention: the caller applies nan_to_num, as bundle.RayBundleRaycaster does)."""
+    origins, dirs, n_rays, head = _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    grad_out, out = _bwd_images(grad_out, out)
+    if not (want_vol or want_tf):
+        return None, None
+    d_vol, dv = _d_vol(vol, want_vol)
+    d_tf, dt = _d_tf(tf, want_tf, 3)
+    _call("dr_march_bundle_bwd", vol.device, *head, grad_out.data_ptr(), out.data_ptr(), *dv[:4], dt[0])
+    return d_vol, d_tf
+
+
+def march_bundle_bwd_rays(vol, tf, origins, dirs, entry, exit_, n, steps, max_samples, sampling_rate, grad_out, out, t_near=None,
+                          jitter_seed=0, ray_base=0):
+    """Gradient of march_bundle_fwd w.r.t. every ray's origin and direction (dr_march_bundle_bwd_rays): the
+    buffers, t_near, jitter_seed and ray_base those of bundle_setup, `steps` and `out` those of march_bundle_fwd. Returns
+    d_origins, d_dirs (N, 3) float32 -- d_dirs w.r.t. the direction as a free 3-vector. A NaN ray gets zeros (D5)."""
+    origins, dirs, n_rays, head = _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    grad_out, out = _bwd_images(grad_out, out)
+    steps = steps.to(torch.int32).contiguous()
+    d_origins = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
+    d_dirs = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
+    _call("dr_march_bundle_bwd_rays", vol.device, *head, steps.data_ptr(), _t_near(t_near), int(jitter_seed) & 0xFFFFFFFF,
+          int(ray_base) & 0xFFFFFFFF, grad_out.data_ptr(), out.data_ptr(), d_origins.data_ptr(), d_dirs.data_ptr())
+    return d_origins, d_dirs
 
 
 _PROJ_MODES = {"sum": N.DR_PROJ_SUM, "max": N.DR_PROJ_MAX}

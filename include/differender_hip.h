@@ -627,6 +627,49 @@ int dr_project_bwd_pose(const void *vol, int vol_dtype, int VX, int VY, int VZ,
                         const float *grad_out, const int32_t *arg_max,
                         const float *pose, const float *fov_v, double *d_pose, float *d_pose_ray, void *stream);
 
+/* The differentiable 1-D TF march over an arbitrary bundle of rays: dr_march_fwd's DR_MODE_DIFF march and its
+ * backwards with a ray as an input -- origins [N][3] and UNIT directions [N][3] f32, used as given, in look_from's world
+ * coordinates (the volume fills [-1, 1]^3) -- instead of a pinhole camera's pixel. One volume and one table per call; the light
+ * of ray p sits at origins[p] + (0, 1, 0). All per-ray buffers are [N] (out_rgba [N][4]); one lane per ray, so 64 consecutive
+ * rays share a wave and the memory coherence of a bundle is the caller's ray order.
+ * dr_bundle_setup: dr_ray_setup's slab test, sample count and jitter for the ray as given: for the origin and direction of a
+ * dr_ray_setup pixel it writes that pixel's entry, exit and nsamp bit for bit. t_near: -INFINITY = off (the reference's line,
+ * which also marches behind an origin inside the box); else tmin = max(tmin, t_near) before the hit test and the sample count
+ * (0: a ray). jitter_seed 0 = none; else the draw is that of (jitter_seed, ray_base, p), ray_base playing view_base's part.
+ * dr_march_bundle_fwd: out_rgba and steps (nullable) as dr_march_fwd with DR_VARIANT_BASELINE: the rays of a dr_ray_setup view
+ * with its camera repeated as the origins give that view's image and steps bit for bit.
+ * dr_march_bundle_bwd ACCUMULATES d_vol (element strides dsx, dsy, dsz) and d_tf [R][4] (caller zeroes); either may be NULL,
+ * both NULL returns 0 before any HIP call. NaN propagates as in the plain kernels.
+ * dr_march_bundle_bwd_rays writes d_origins and d_dirs [N][3] f32 (overwritten): the reverse-mode derivative w.r.t. the origin
+ * and w.r.t. the direction as a free 3-vector (normalising it is the caller's, whose chain rule it then is), with the frozen
+ * branches of dr_march_bwd_cam (n, `steps` of dr_march_bundle_fwd, the jitter draw, the slab faces, the t_near clamp, the cells,
+ * the lighting predicates). t_near, jitter_seed and ray_base must be those of the dr_bundle_setup call that made the buffers. A
+ * ray with n <= 1 gets zeros; a NaN ray gets zeros and infinities are clamped to +-1e30 (D5).
+ * Invalid arguments (null required pointers, N <= 0, N >= 2^31, a volume extent < 2, R < 1, max_samples < 1, a NaN t_near, an
+ * unknown dtype, a non-finite or non-positive sampling rate) return DR_EINVAL before any HIP call; a library linked without
+ * these kernels returns DR_EUNSUPPORTED. */
+int dr_bundle_setup(const float *origins, const float *dirs, int64_t N, int VX, int VY, int VZ,
+                    float sampling_rate, float t_near, uint32_t jitter_seed, uint32_t ray_base,
+                    float *entry, float *exit_, int32_t *nsamp, void *stream);
+int dr_march_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                        int64_t sx, int64_t sy, int64_t sz, const float *tf, int R,
+                        const float *origins, const float *dirs, const float *entry, const float *exit_,
+                        const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                        float *out_rgba, int32_t *steps, void *stream);
+int dr_march_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                        int64_t sx, int64_t sy, int64_t sz, const float *tf, int R,
+                        const float *origins, const float *dirs, const float *entry, const float *exit_,
+                        const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                        const float *grad_out, const float *out_rgba,
+                        float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, float *d_tf, void *stream);
+int dr_march_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                             int64_t sx, int64_t sy, int64_t sz, const float *tf, int R,
+                             const float *origins, const float *dirs, const float *entry, const float *exit_,
+                             const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                             const int32_t *steps, float t_near, uint32_t jitter_seed, uint32_t ray_base,
+                             const float *grad_out, const float *out_rgba,
+                             float *d_origins, float *d_dirs, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
