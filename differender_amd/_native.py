@@ -105,6 +105,12 @@ SIGNATURES = {
                                  _P, _L, _L, _L, _P, _P]),
     "dr_march_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F,
                                       _P, _F, _U, _U, _P, _P, _P, _P, _P]),
+    # the projections of a ray bundle: the bundle's arguments without the table, mode and arg_max
+    "dr_project_bundle_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
+    "dr_project_bundle_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P,
+                                   _P, _L, _L, _L, _I, _P]),
+    "dr_project_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _I, _F, _U, _U,
+                                        _P, _P, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

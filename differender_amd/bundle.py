@@ -12,6 +12,11 @@ parallel-beam geometry or a distorted lens is a few lines of torch in front of t
 
     o, d = pinhole_rays(look_from, look_at, up, fov, (H, W))             # Raycaster's own rays, (H, W, 3) each
     o, d = orthographic_rays(look_from, look_at, up, extent, (H, W))     # parallel rays from a plane through look_from
+    o, d = cone_beam_rays(source, det_center, det_u, det_v, (H, W))      # a point source and a flat detector
+
+The rays of an image are fastest in tiles, not rows (a wave is 64 consecutive rays): `perm = tile_order((H, W))`, march
+`o.reshape(-1, 3)[perm]`, and put the result back with `out[perm] = result`. projection.RayBundleProjector takes
+the same bundles for X-ray and maximum intensity projections.
 
 Gradients flow to the volume and the TF; a module built with ray_grad=True gives origins and directions theirs as well, and
 autograd carries them on into whatever made the rays (both helpers are plain differentiable torch).
@@ -24,7 +29,7 @@ from . import _layout as L
 from . import _native as N
 from . import functional as F
 
-__all__ = ["RayBundleRaycaster", "RayBundleFunction", "pinhole_rays", "orthographic_rays"]
+__all__ = ["RayBundleRaycaster", "RayBundleFunction", "pinhole_rays", "orthographic_rays", "cone_beam_rays", "tile_order"]
 
 
 def _unit(a):
@@ -75,6 +80,38 @@ def orthographic_rays(look_from, look_at, up, extent, output_shape):
     ext_h = torch.as_tensor(extent, dtype=look_from.dtype, device=look_from.device)
     origins = look_from + (u * (ext_h * (W / H))) * right + (v * ext_h) * upp
     return origins, view_dir.expand(H, W, 3)
+
+
+def cone_beam_rays(source, det_center, det_u, det_v, det_shape):
+    """The rays of a cone beam: a point source and a flat detector of det_shape = (H, W) pixels whose pixel (r, c) sits at
+    det_center + (c - (W-1)/2) det_u + (r - (H-1)/2) det_v -- det_u, det_v (3,) the steps to the next column and row, any pitch,
+    any offset of det_center from the source's axis -> origins (the source), directions (unit vectors to the pixels), (H, W, 3)
+    each; differentiable torch in all four, like pinhole_rays."""
+    H, W = int(det_shape[0]), int(det_shape[1])
+    like = dict(dtype=source.dtype, device=source.device)
+    det_center, det_u, det_v = (torch.as_tensor(a, **like) for a in (det_center, det_u, det_v))
+    c = (torch.arange(W, **like) - (W - 1) / 2)[None, :, None]
+    r = (torch.arange(H, **like) - (H - 1) / 2)[:, None, None]
+    pixels = det_center + c * det_u + r * det_v
+    return source.expand(H, W, 3), _unit(pixels - source)
+
+
+def tile_order(shape, tile=16):
+    """A permutation (int64, H*W) of the flattened (H, W) grid sorted by tile x tile tile, then by (tile/2) x (tile/2) sub-tile
+    within it, then row-major within the sub-tile: where H and W are multiples of 16, each run of 256 is one 16 x 16 tile (a
+    group of the bundle projections' windowed backward) and each run of 64 one 8 x 8 block (a wave of every bundle kernel).
+    Edge tiles are cut at the grid's border."""
+    H, W, tile = int(shape[0]), int(shape[1]), int(tile)
+    if H < 1 or W < 1 or tile < 2 or tile % 2:
+        raise ValueError(f"tile_order needs a grid of >= 1 x 1 and an even tile >= 2, got {(H, W)}, {tile}")
+    half = tile // 2
+    r = torch.arange(H)[:, None].expand(H, W).reshape(-1)
+    c = torch.arange(W)[None, :].expand(H, W).reshape(-1)
+    tiles_w, in_r, in_c = (W + tile - 1) // tile, r % tile, c % tile
+    key = (r // tile) * tiles_w + c // tile                      # the tile
+    key = key * 4 + (in_r // half) * 2 + in_c // half            # its sub-tile
+    key = key * (half * half) + (in_r % half) * half + in_c % half
+    return torch.argsort(key, stable=True)
 
 
 class RayBundleFunction(torch.autograd.Function):

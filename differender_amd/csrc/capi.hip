@@ -909,6 +909,76 @@ int dr_march_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int
     return launch_on(vol, launch_bundle_ray_grad, a, b, (hipStream_t)stream);
 }
 
+// the three bundle projections: fill_rays for one view of N x 1 rays whose camera rows are the origins, at the projections'
+// fixed rate of 1 with max_samples >= 1; the mode, and arg_max for DR_PROJ_MAX
+static int fill_proj_bundle(MarchArgs &a, BundleArgs &b, ProjArgs &q, const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                            int64_t sx, int64_t sy, int64_t sz, const float *origins, const float *dirs, const float *entry,
+                            const float *exit_, const int32_t *nsamp, int64_t N, int max_samples, int mode, const int32_t *arg_max,
+                            float t_near = 0.0f) {
+    if (!bundle_fits(N, t_near)) return DR_EINVAL;
+    const int rc = fill_rays(a, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, 0, origins, entry, exit_, dirs, nsamp, 1, (int)N, 1,
+                             max_samples, 1, 1.0f, false);
+    if (rc) return rc;
+    if (mode != DR_PROJ_SUM && mode != DR_PROJ_MAX) return DR_EINVAL;
+    if (mode == DR_PROJ_MAX && !arg_max) return DR_EINVAL;
+    a.mode = DR_MODE_DIFF;
+    b = BundleArgs{};
+    b.origins = origins; b.N = (int)N; b.t_near = t_near;
+    q = ProjArgs{};
+    q.mode = mode; q.variant = DR_VARIANT_AUTO; q.arg_max = const_cast<int32_t *>(arg_max);
+    return 0;
+}
+
+int dr_project_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                          const float *origins, const float *dirs, const float *entry, const float *exit_, const int32_t *nsamp,
+                          int64_t N, int max_samples, int mode, float *out, int32_t *arg_max, void *stream) {
+    MarchArgs a;
+    BundleArgs b;
+    ProjArgs q;
+    const int rc = fill_proj_bundle(a, b, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, origins, dirs, entry, exit_, nsamp, N,
+                                    max_samples, mode, arg_max);
+    if (rc) return rc;
+    if (!out) return DR_EINVAL;
+    a.out = out;
+    return launch_on(vol, launch_project_bundle_fwd, a, b, q, (hipStream_t)stream);
+}
+
+int dr_project_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                          const float *origins, const float *dirs, const float *entry, const float *exit_, const int32_t *nsamp,
+                          int64_t N, int max_samples, int mode, const float *grad_out, const int32_t *arg_max, float *d_vol,
+                          int64_t dsx, int64_t dsy, int64_t dsz, int variant, void *stream) {
+    MarchArgs a;
+    BundleArgs b;
+    ProjArgs q;
+    const int rc = fill_proj_bundle(a, b, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, origins, dirs, entry, exit_, nsamp, N,
+                                    max_samples, mode, arg_max);
+    if (rc) return rc;
+    if (!grad_out) return DR_EINVAL;
+    if (variant != DR_VARIANT_AUTO && variant != DR_VARIANT_BASELINE) return DR_EINVAL;
+    if (!d_vol) return 0;  // nothing requested
+    a.grad_out = grad_out;
+    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz;
+    q.variant = variant;
+    return launch_on(vol, launch_project_bundle_bwd, a, b, q, (hipStream_t)stream);
+}
+
+int dr_project_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                               const float *origins, const float *dirs, const float *entry, const float *exit_,
+                               const int32_t *nsamp, int64_t N, int max_samples, int mode, float t_near, uint32_t jitter_seed,
+                               uint32_t ray_base, const float *grad_out, const int32_t *arg_max, float *d_origins, float *d_dirs,
+                               void *stream) {
+    MarchArgs a;
+    BundleArgs b;
+    ProjArgs q;
+    const int rc = fill_proj_bundle(a, b, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, origins, dirs, entry, exit_, nsamp, N,
+                                    max_samples, mode, arg_max, t_near);
+    if (rc) return rc;
+    if (!grad_out || !d_origins || !d_dirs) return DR_EINVAL;
+    a.grad_out = grad_out;
+    b.jitter_seed = jitter_seed; b.ray_base = ray_base; b.d_origins = d_origins; b.d_dirs = d_dirs;
+    return launch_on(vol, launch_project_bundle_ray_grad, a, b, q, (hipStream_t)stream);
+}
+
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,
                         void *stream) {
     if (!tf || !d_tf || !momentum || n <= 0 || !(max_grad >= 0.0f)) return DR_EINVAL;

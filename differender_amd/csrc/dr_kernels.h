@@ -209,6 +209,14 @@ __attribute__((weak)) int launch_march_bundle_fwd(const MarchArgs &a, const Bund
 __attribute__((weak)) int launch_march_bundle_bwd(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
 __attribute__((weak)) int launch_bundle_ray_grad(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
 
+// The projections over a bundle of rays (projection_bundle.hip): dr_project_bundle_fwd / _bwd / _bwd_rays take the
+// bundle's MarchArgs without a table (n_views = 1, W = N, H = 1, cam the origins, rays the directions), its BundleArgs (no
+// steps) and the projections' ProjArgs (mode, variant, arg_max [N]; grad_out is an [N] f32 vector)
+// weak, as launch_camera_grad: capi.o must load in a library linked without projection_bundle.o
+__attribute__((weak)) int launch_project_bundle_fwd(const MarchArgs &a, const BundleArgs &b, const ProjArgs &q, hipStream_t stream);
+__attribute__((weak)) int launch_project_bundle_bwd(const MarchArgs &a, const BundleArgs &b, const ProjArgs &q, hipStream_t stream);
+__attribute__((weak)) int launch_project_bundle_ray_grad(const MarchArgs &a, const BundleArgs &b, const ProjArgs &q, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -19,6 +19,28 @@ __device__ __forceinline__ int wave_incl_sum(int v) {
 }
 
 
+// minimum / maximum of an int or a float over the wave, in every lane (butterfly through the LDS crossbar)
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_minf(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_maxf(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
 struct Over { float c0, c1, c2, a; };  // premultiplied composite element
 __device__ __forceinline__ Over over(const Over &front, const Over &back) {  // front-to-back "over"
     const float T = 1.0f - front.a;

@@ -5,13 +5,12 @@
 // camera and the light at origin + e_y per ray: a bundle made of a pinhole camera's rays is that camera's image, bit for bit.
 // One departure: the volume / TF backward projects a sample's adjoint with a normal from double taps (shade_for_adjoint).
 //
-// Shape: one lane per ray, 256-lane workgroups over the linear ray index p in [0, N) -- no pixel tile: 64 consecutive rays share
-// a wave, so the memory coherence of a bundle is the caller's ray order.
+// Shape: dr_bundle.h's -- one lane per ray over the linear ray index, the coherence of a bundle being the caller's ray order.
 //
 // Like ray_setup.hip this translation unit is built with -ffp-contract=off: bundle_setup_kernel's sample count
 // n = floor(sr * len * diag) + 1 is then ray_setup_kernel's for the same origin and direction.
+#include "dr_bundle.h"
 #include "dr_camera.h"
-#include "dr_tile.h"
 
 namespace dr {
 
@@ -32,9 +31,6 @@ struct BundleSetupParams {
     float *entry, *exit_;
     int32_t *nsamp;
 };
-
-__device__ __forceinline__ int bundle_ray() { return (int)(blockIdx.x * 256u + threadIdx.x); }
-__device__ __forceinline__ f3 load_f3(const float *a, size_t p) { return make_f3(a[3 * p], a[3 * p + 1], a[3 * p + 2]); }
 
 // ray_setup_kernel's statements from the slab test on, in its order, for the ray (o, vd) as given. t_near (-INFINITY: off)
 // clamps the entry distance before the hit test and the sample count: 0 makes a ray a ray, where the reference marches the
@@ -63,17 +59,6 @@ __global__ __launch_bounds__(256) void bundle_setup_kernel(BundleSetupParams P) 
     P.entry[p] = tmin;
     P.exit_[p] = tmax;
     P.nsamp[p] = (int32_t)n_samples;
-}
-
-// open_ray for a lane's own origin: the (single) volume, the ray buffers' entries, the direction; ADJ: the upstream gradient and
-// the forward's pixel too
-template <bool ADJ, typename VT>
-__device__ __forceinline__ void open_bundle_ray(Ray<VT> &r, size_t p, VolView<VT> vol, const float *origins, const float *entry,
-                                                const float *exit_, const float *dirs, const int32_t *nsamp,
-                                                const float *grad_out = nullptr, const float *out_fwd = nullptr) {
-    r.vol = vol;
-    r.cam = load_f3(origins, p);
-    open_geom<ADJ>(r, p, entry, exit_, dirs, nsamp, grad_out, out_fwd);
 }
 
 // march_fwd_baseline_kernel in DR_MODE_DIFF
@@ -298,8 +283,6 @@ __global__ __launch_bounds__(256) void bundle_ray_grad_kernel(BundleParams<VT> P
     P.d_dirs[q] = d_d.x; P.d_dirs[q + 1] = d_d.y; P.d_dirs[q + 2] = d_d.z;
 }
 
-static dim3 bundle_grid(int N) { return dim3((unsigned)(((int64_t)N + 255) / 256)); }
-
 template <typename VT>
 static BundleParams<VT> make_bundle_params(const MarchArgs &a, const BundleArgs &b) {
     BundleParams<VT> P{make_ray_params<VT>(a)};
@@ -307,14 +290,6 @@ static BundleParams<VT> make_bundle_params(const MarchArgs &a, const BundleArgs 
     P.N = b.N; P.fwd_steps = b.steps; P.t_near = b.t_near; P.jitter_seed = b.jitter_seed; P.ray_base = b.ray_base;
     P.d_origins = b.d_origins; P.d_dirs = b.d_dirs;
     return P;
-}
-
-// One launch of a bundle kernel: ceil(N / 256) workgroups of 256 lanes, `lds` bytes of dynamic LDS.
-template <typename Params>
-static int launch_bundle(void (*kernel)(Params), int N, size_t lds, hipStream_t stream, const Params &P) {
-    if (big_lds(kernel, lds) != hipSuccess) return DR_EUNSUPPORTED;
-    hipLaunchKernelGGL(kernel, bundle_grid(N), dim3(256), lds, stream, P);
-    return (int)hipGetLastError();
 }
 
 int launch_bundle_setup(const BundleArgs &b, const float *dirs, int VX, int VY, int VZ, float sr, float *entry, float *exit_,

@@ -10,6 +10,7 @@
 // pixel tile's taps of one depth window in LDS and adds the box to d_vol row by row (below).
 #include "dr_camera.h"
 #include "dr_tile.h"
+#include "dr_wave.h"
 
 namespace dr {
 
@@ -105,27 +106,6 @@ constexpr int PW_TILE = 16;
 constexpr int PW_BOX = 7680;        // LDS floats of the box: 30 KiB, five workgroups (20 waves) per CU by LDS
 constexpr float PW_WIN_VOX = 16.0f;  // first window depth, in voxels of the finest axis
 constexpr float PW_MIN_VOX = 2.0f;   // shallowest window before the global fallback
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_minf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // INNER_X: d_vol's x axis is its contiguous one (the (1, D, H, W) tensor seen through Projector); otherwise z is (field order)
 template <typename VT, bool INNER_X>

@@ -19,6 +19,7 @@ __all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd",
            "mse_loss_grad", "dssim_mse_fwd", "dssim_mse_bwd", "dssim_mse_loss_grad", "msssim_mse_fwd", "msssim_mse_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 __all__ += ["bundle_setup", "march_bundle_fwd", "march_bundle_bwd", "march_bundle_bwd_rays"]
+__all__ += ["project_bundle_fwd", "project_bundle_bwd", "project_bundle_bwd_rays"]
 
 
 def _stream():
@@ -947,6 +948,66 @@ def project_bwd_cam(vol, cam, entry, exit_, rays, n, grad_out, max_samples=None,
     vargs = _vol_args(vol, V)
     return _camera_bwd("dr_project_bwd", vol, n, (*vargs, *rargs, *pargs), (fov_deg, near, jitter_seed, view_base),
                        (grad_out.data_ptr(), _ptr(arg)), per_ray, pose, fov_v)
+
+
+def _proj_bundle_head(vol, origins, dirs, entry, exit_, n, max_samples, mode):
+    """What the three bundle projections start with -> (origins, dirs, N, their C-ABI arguments up to mode): one volume
+    (VX, VY, VZ) with any strides."""
+    _require_gpu(vol, "volume")
+    origins, dirs, n_rays = _bundle_rays(origins, dirs)
+    if vol.ndim != 3:
+        raise ValueError("a bundle is projected through one volume (VX,VY,VZ)")
+    for name, t in (("entry", entry), ("exit", exit_), ("n", n)):
+        if tuple(t.shape) != (n_rays,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be bundle_setup's contiguous ({n_rays},) buffer, got {tuple(t.shape)}")
+    return origins, dirs, n_rays, (*_vol_args(vol, 1)[:8], origins.data_ptr(), dirs.data_ptr(), entry.data_ptr(), exit_.data_ptr(),
+                                   n.data_ptr(), n_rays, _max_samples(max_samples), _proj_mode(mode))
+
+
+def _ray_values(t, n_rays, name):
+    """A per-ray vector (N,) as the float32 contiguous tensor the kernels read."""
+    if tuple(t.shape) != (n_rays,):
+        raise ValueError(f"{name} must be ({n_rays},), got {tuple(t.shape)}")
+    return t.to(torch.float32).contiguous()
+
+
+def project_bundle_fwd(vol, origins, dirs, entry, exit_, n, max_samples=None, mode="sum"):
+    """project_fwd over a bundle of rays (dr_project_bundle_fwd): origins, dirs (N, 3) and the buffers of
+    bundle_setup. Returns out (N,) float32 and, for "max", arg_max (N,) int32 -- None for "sum". For a pinhole view's rays, the
+    bits of project_fwd."""
+    origins, dirs, n_rays, head = _proj_bundle_head(vol, origins, dirs, entry, exit_, n, max_samples, mode)
+    out = torch.empty((n_rays,), dtype=torch.float32, device=vol.device)
+    arg = torch.empty((n_rays,), dtype=torch.int32, device=vol.device) if head[-1] == N.DR_PROJ_MAX else None
+    _call("dr_project_bundle_fwd", vol.device, *head, out.data_ptr(), _ptr(arg))
+    return out, arg
+
+
+def project_bundle_bwd(vol, origins, dirs, entry, exit_, n, grad_out, max_samples=None, mode="sum", arg_max=None,
+                       variant=N.DR_VARIANT_AUTO):
+    """d_vol of sum(project_bundle_fwd(...) * grad_out) (dr_project_bundle_bwd): a back-projection. variant DR_VARIANT_AUTO: the
+    "sum" kernel that collects the taps of 256 consecutive rays per depth window in LDS (order an image's rays with
+    bundle.tile_order); DR_VARIANT_BASELINE: per-tap global atomics. "max" needs the forward's arg_max."""
+    origins, dirs, n_rays, head = _proj_bundle_head(vol, origins, dirs, entry, exit_, n, max_samples, mode)
+    arg, _ = _proj_bwd_args(max_samples, mode, arg_max)
+    grad_out = _ray_values(grad_out, n_rays, "grad_out")
+    d_vol, dv = _d_vol(vol, True)
+    _call("dr_project_bundle_bwd", vol.device, *head, grad_out.data_ptr(), _ptr(arg), *dv[:4], int(variant))
+    return d_vol
+
+
+def project_bundle_bwd_rays(vol, origins, dirs, entry, exit_, n, grad_out, max_samples=None, mode="sum", arg_max=None,
+                            t_near=None, jitter_seed=0, ray_base=0):
+    """Gradient of project_bundle_fwd w.r.t. every ray's origin and direction (dr_project_bundle_bwd_rays): t_near, jitter_seed
+    and ray_base those of bundle_setup. Returns d_origins, d_dirs (N, 3) float32 -- d_dirs w.r.t. the direction as a free
+    3-vector. A NaN ray gets zeros (D5)."""
+    origins, dirs, n_rays, head = _proj_bundle_head(vol, origins, dirs, entry, exit_, n, max_samples, mode)
+    arg, _ = _proj_bwd_args(max_samples, mode, arg_max)
+    grad_out = _ray_values(grad_out, n_rays, "grad_out")
+    d_origins = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
+    d_dirs = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
+    _call("dr_project_bundle_bwd_rays", vol.device, *head, _t_near(t_near), int(jitter_seed) & 0xFFFFFFFF,
+          int(ray_base) & 0xFFFFFFFF, grad_out.data_ptr(), _ptr(arg), d_origins.data_ptr(), d_dirs.data_ptr())
+    return d_origins, d_dirs
 
 
 def mse_loss_grad(out, reference, inv_norm=None, want_grad=True, loss=None):

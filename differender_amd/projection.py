@@ -8,16 +8,24 @@ Raycaster at the same sampling rate, camera and jitter; there is no transfer fun
     line_integral = proj(mu, look_from)          # mu ([BS,]1,D,H,W), look_from ([BS,]3) -> ([BS,]1,H,W)
     radiograph = torch.exp(-line_integral)       # Beer-Lambert: transmitted intensity of a monochromatic beam
 
+RayBundleProjector projects along rays that are an input -- a parallel beam, a cone beam with a flat detector,
+a random minibatch of rays across views -- instead of one pinhole camera's:
+
+    proj = RayBundleProjector(volume.shape[-3:], mode="sum")
+    sinogram_row = proj(mu, *orthographic_rays(...))      # origins, directions (..., 3) -> (...)
+
 Batching, image orientation and AMP casting are those of volume_raycaster.Raycaster. Gradients flow to the volume (a
 back-projection) and to look_from (when it requires grad). Lengths are in world units of the renderer's [-1, 1]^3 box: a
 constant volume c gives c times the chord of the ray through the box.
 """
+import math
+
 import torch
 
 from . import _layout as L
 from . import functional as F
 
-__all__ = ["Projector", "ProjectFunction"]
+__all__ = ["Projector", "ProjectFunction", "RayBundleProjector", "RayBundleProjectFunction"]
 
 _MODES = ("sum", "max")
 
@@ -110,3 +118,101 @@ class Projector(L.RayModule):
     def extra_repr(self):
         return (f"Volume ({self.volume_shape}), Output ({self.output_shape}), mode = {self.mode}, "
                 f"Max Samples = {self.max_samples}")
+
+
+class RayBundleProjectFunction(torch.autograd.Function):
+    """Autograd boundary of the bundle projections: `apply(pj, volume, origins, dirs, jitter)`. volume (W,D,H), any strides;
+    origins, dirs (N,3), the directions of unit length. Returns (N,). origins and dirs receive gradients where they require them
+    (RayBundleProjector refuses that unless built with ray_grad=True)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, pj, volume, origins, dirs, jitter=True):
+        volume = F.as_volume(volume)
+        origins, dirs = origins.float().contiguous(), dirs.float().contiguous()
+        seed = F.new_jitter_seed() if jitter else 0
+        e, x, n = F.bundle_setup(origins, dirs, volume.shape[-3:], pj.sampling_rate, pj.t_near, seed)
+        out, arg = F.project_bundle_fwd(volume, origins, dirs, e, x, n, pj.max_samples, pj.mode)
+        ctx.save_for_backward(volume, origins, dirs, e, x, n, *((arg,) if arg is not None else ()))
+        ctx.pj, ctx.seed = pj, seed
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_output):
+        volume, origins, dirs, e, x, n, *arg = ctx.saved_tensors
+        pj, arg = ctx.pj, arg[0] if arg else None
+        dv = d_o = d_d = None
+        if ctx.needs_input_grad[1]:
+            dv = torch.nan_to_num(F.project_bundle_bwd(volume, origins, dirs, e, x, n, grad_output, pj.max_samples, pj.mode, arg))
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            d_o, d_d = F.project_bundle_bwd_rays(volume, origins, dirs, e, x, n, grad_output, pj.max_samples, pj.mode, arg,
+                                                 pj.t_near, ctx.seed)
+        return (None, dv, d_o if ctx.needs_input_grad[2] else None, d_d if ctx.needs_input_grad[3] else None, None)
+
+
+class RayBundleProjector(torch.nn.Module):
+    """Line-integral (mode "sum") or maximum intensity ("max") projection of a volume along a bundle of rays.
+
+    volume_shape (D, H, W), mode, sampling_rate, jitter and max_samples as for Projector.
+    forward(volume (1,D,H,W), origins (...,3), directions (...,3)) -> (...); one volume per call. Rays live in look_from's world
+    coordinates (the volume fills [-1, 1]^3): bundle.orthographic_rays is a parallel beam, bundle.cone_beam_rays a point source
+    and a flat detector, bundle.pinhole_rays Projector's own rays. The volume backward is fastest where 256 consecutive rays
+    are neighbours: order an image's rays with bundle.tile_order.
+    t_near: None integrates along the reference's whole line through the box, also behind an origin inside it; 0.0 makes every
+    ray start at its origin.
+    ray_grad=True: origins and directions may require grad and receive their gradients."""
+
+    def __init__(self, volume_shape, mode="sum", sampling_rate=1.0, jitter=True, max_samples=None, t_near=None, ray_grad=False):
+        super().__init__()
+        if len(tuple(volume_shape)) != 3:
+            raise ValueError("expected volume_shape (D, H, W)")
+        if min(volume_shape) < 2:
+            raise ValueError(f"volume_shape needs >= 2 voxels per axis, got {tuple(volume_shape)}")
+        if mode not in _MODES:
+            raise ValueError(f"mode must be 'sum' or 'max', got {mode!r}")
+        if not (sampling_rate > 0):
+            raise ValueError(f"sampling_rate must be > 0, got {sampling_rate}")
+        if max_samples is not None and int(max_samples) < 1:
+            raise ValueError(f"max_samples must be None or >= 1, got {max_samples}")
+        if t_near is not None and math.isnan(float(t_near)):
+            raise ValueError("t_near must be a number or None")
+        self.volume_shape = (int(volume_shape[2]), int(volume_shape[0]), int(volume_shape[1]))  # (W, D, H), as Raycaster
+        self.mode, self.sampling_rate, self.jitter = mode, float(sampling_rate), jitter
+        self.max_samples = None if max_samples is None else int(max_samples)
+        self.t_near = None if t_near is None else float(t_near)
+        self.ray_grad = bool(ray_grad)
+        from . import _native
+        _native.lib()  # fail loudly at construction time if the HIP library is missing
+
+    def _check(self, volume, origins, directions):
+        expected = "volume (1,D,H,W), origins (...,3), directions (...,3) of one shape"
+        if volume.ndim != 4 or volume.shape[0] != 1:
+            raise ValueError(f"expected {expected}; got volume {tuple(volume.shape)}")
+        w, d, h = self.volume_shape
+        if tuple(volume.shape[-3:]) != (d, h, w):
+            raise ValueError(f"volume has (D, H, W) = {tuple(volume.shape[-3:])}, the module was built for {(d, h, w)}")
+        if origins.ndim < 1 or origins.shape[-1] != 3 or origins.shape != directions.shape or origins.numel() == 0:
+            raise ValueError(f"expected {expected}; got origins {tuple(origins.shape)}, directions {tuple(directions.shape)}")
+
+    def forward(self, volume, origins, directions):
+        """volume (1,D,H,W), origins, directions (...,3) -> (...). The directions are normalised here, in torch (a zero-length
+        one raises), so their gradient is that of the direction handed in."""
+        self._check(volume, origins, directions)
+        if not self.ray_grad:
+            L.refuse_pose_grad("RayBundleProjector", "construct RayBundleProjector(..., ray_grad=True) for ray gradients",
+                               origins=origins, directions=directions)
+        length = torch.sqrt((directions * directions).sum(-1, keepdim=True))
+        if bool((length == 0).any()):
+            raise ValueError("a direction has zero length")
+        for name, t in (("volume", volume), ("origins", origins), ("directions", directions)):
+            F._require_gpu(t, name)
+            if t.device != volume.device:
+                raise ValueError(f"{name} lives on {t.device}, the volume on {volume.device}")
+        out = RayBundleProjectFunction.apply(self, L.field_view(volume), origins.reshape(-1, 3), (directions / length).reshape(-1, 3),
+                                             self.jitter)
+        return out.reshape(origins.shape[:-1])
+
+    def extra_repr(self):
+        return (f"Volume ({self.volume_shape}), mode = {self.mode}, Max Samples = {self.max_samples}, t_near = {self.t_near}, "
+                f"ray_grad = {self.ray_grad}")

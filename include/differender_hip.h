@@ -670,6 +670,42 @@ int dr_march_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int
                              const float *grad_out, const float *out_rgba,
                              float *d_origins, float *d_dirs, void *stream);
 
+/* X-ray line-integral and maximum-intensity projections of an arbitrary bundle of rays: dr_project_fwd / _bwd
+ * with a ray as an input, as the entries above are dr_march_fwd's. origins, dirs, the ray buffers of dr_bundle_setup (at any
+ * sampling rate) and N as above; no table. mode is DR_PROJ_SUM or DR_PROJ_MAX; out, grad_out [N] f32, arg_max [N] i32 (written
+ * by the forward and read by both backwards for DR_PROJ_MAX, ignored and nullable for DR_PROJ_SUM). The samples are
+ * dr_project_fwd's: the rays of a dr_ray_setup view with its camera repeated as the origins give that view's out and arg_max bit
+ * for bit.
+ * dr_project_bundle_bwd ACCUMULATES d_vol (element strides dsx, dsy, dsz; caller zeroes); d_vol NULL returns 0 before any HIP
+ * call. A ray whose g D (SUM) or g (MAX) is NaN contributes nothing, infinities are clamped to +-1e30 (D5). variant
+ * DR_VARIANT_BASELINE: one global float atomic per tap; DR_VARIANT_AUTO: for DR_PROJ_SUM, groups of 256 consecutive rays collect
+ * their taps per depth window in LDS and flush along d_vol's contiguous axis (a group too incoherent for that finishes per
+ * tap): order an image's rays by 16 x 16 tiles.
+ * dr_project_bundle_bwd_rays writes d_origins and d_dirs [N][3] f32 (overwritten), as dr_march_bundle_bwd_rays does: the frozen
+ * branches are n, the jitter draw, the slab faces, the t_near clamp, the cells and the argmax. t_near, jitter_seed and ray_base
+ * must be those of the dr_bundle_setup call that made the buffers. A ray with n <= 1 gets zeros; D5 as above.
+ * Invalid arguments (null required pointers, N <= 0, N >= 2^31, a volume extent < 2, max_samples < 1, a NaN t_near, an unknown
+ * mode, variant or dtype, DR_PROJ_MAX without arg_max) return DR_EINVAL before any HIP call; a library linked without these
+ * kernels returns DR_EUNSUPPORTED. */
+int dr_project_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                          int64_t sx, int64_t sy, int64_t sz,
+                          const float *origins, const float *dirs, const float *entry, const float *exit_,
+                          const int32_t *nsamp, int64_t N, int max_samples, int mode,
+                          float *out, int32_t *arg_max, void *stream);
+int dr_project_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                          int64_t sx, int64_t sy, int64_t sz,
+                          const float *origins, const float *dirs, const float *entry, const float *exit_,
+                          const int32_t *nsamp, int64_t N, int max_samples, int mode,
+                          const float *grad_out, const int32_t *arg_max,
+                          float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int variant, void *stream);
+int dr_project_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                               int64_t sx, int64_t sy, int64_t sz,
+                               const float *origins, const float *dirs, const float *entry, const float *exit_,
+                               const int32_t *nsamp, int64_t N, int max_samples, int mode,
+                               float t_near, uint32_t jitter_seed, uint32_t ray_base,
+                               const float *grad_out, const int32_t *arg_max,
+                               float *d_origins, float *d_dirs, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
