@@ -1,7 +1,8 @@
 """Projections of ray bundles, DESIGN.md D20, without a GPU: the C ABI and its argument checks, cone_beam_rays and tile_order,
 the reference (tests/proj_bundle_reference.py) pinned to proj_reference.project_camera on a pinhole's rays, what the float64
 comparisons of the GPU file owe their own rule (rays kept, a mutated tail coefficient refused), the windowed cases held to the
-plan model, and the module's argument checks."""
+plan model, the cases of tests/test_gpu_proj_bundle_edges.py held to their declared paths and to the conditions their
+comparisons rest on, and the module's argument checks."""
 import ctypes
 import math
 import os
@@ -239,6 +240,121 @@ def test_window_cases_cover_every_path_and_the_ragged_group():
     assert (PB.slab32(o, d, case["vshape"], 1.0)[2][:256] == 0).all()
     # the projections' own constants stay where proj_reference reads them
     assert PR.window_constants() == {"PW_TILE": 16.0, "PW_BOX": 7680.0, "PW_WIN_VOX": 16.0, "PW_MIN_VOX": 2.0}
+
+
+# --- 5b. the cases of tests/test_gpu_proj_bundle_edges.py, from the float32 slab and the plan alone ------------------------------------
+
+def _edge_trace(case, S):
+    e, x, n = PB.slab32(case["origins"], case["dirs"], case["vshape"], case["sr"], case["t_near"], case["seed"], PB.RAY_BASE)
+    return PB.group_trace(case["origins"], e, x, case["dirs"], n, case["vshape"], S, case["live"]), n
+
+
+@pytest.mark.parametrize("name", sorted(PB.EDGE_CASES))
+def test_edge_cases_take_their_declared_paths(name):
+    case = PB.edge_case(name)
+    vol = PR.layout_volume(torch.zeros(case["vshape"]), case["layout"])
+    assert PB.LAYOUT_STRIDES[case["layout"]](tuple(vol.stride()), case["vshape"]) and sorted(vol.stride())[0] == 1
+    assert ("xyz"[int(np.argmin(vol.stride()))] == case["layout"]) and tuple(vol.shape) == tuple(case["vshape"])
+    for S in case["clips"]:
+        trace, n = _edge_trace(case, S)
+        PB.check_paths(case, S, trace)
+        assert len(trace) == -(-n.shape[0] // 256)
+        # group_plan is the trace summed: its fields keep their meaning
+        plan = PB.group_plan(case["origins"], *PB.slab32(case["origins"], case["dirs"], case["vshape"], case["sr"], case["t_near"],
+                                                         case["seed"], PB.RAY_BASE)[:2], case["dirs"], n, case["vshape"], S, case["live"])
+        walked = [t for t in trace if t is not None]
+        assert plan == PB.GroupPlan(sum(t.lds_full for t in walked), sum(t.lds_halved for t in walked),
+                                    sum(t.fell for t in walked), len(trace) - len(walked), len(walked))
+        if S is not None:
+            assert (n > S).any()   # the clip clips
+
+
+def test_the_spreading_cone_falls_through_with_samples_taken_and_the_clips_end_it_earlier():
+    case = PB.edge_case("cone_spreading")
+    counts = {}
+    for S in case["clips"]:
+        trace, n = _edge_trace(case, S)
+        counts[S] = (sum(t.lds_full for t in trace), sum(t.lds_halved for t in trace), sum(t.fell for t in trace))
+        if S is None:   # every group leaves through the per-tap loop from s_cur > 0, most of its samples still to come
+            total = [int(n[g0:g0 + 256].sum()) for g0 in range(0, 1024, 256)]
+            assert all(t.fell and 0 < t.s_cur_at_fall < tot for t, tot in zip(trace, total)), trace
+    assert counts == {None: (4, 28, 4), 150: (4, 24, 0), 100: (8, 0, 0), 1: (4, 0, 0)}, counts
+
+
+def test_the_staggered_group_and_the_group_edges_are_what_they_say():
+    case = PB.edge_case("staggered_depths")
+    (trace,), n = _edge_trace(case, None)
+    assert trace.staggered and n.shape == (256,)
+    inside, missing = np.arange(256) % 8 == 3, np.arange(256) % 16 == 5
+    assert (n[missing] == 0).all() and (n[~missing] > 1).all()
+    assert n[inside].max() < PB.STAGGERED_CLIP < n[~inside & ~missing].min()   # the clip clips the longer rays alone
+    g = case["grad_out"]
+    assert np.isnan(g[PB.NAN_LANE]) and n[PB.NAN_LANE] > 1 and (g[np.arange(256) % 16 == 9] == 0).all()
+    assert not case["live"][PB.NAN_LANE] and case["live"].sum() == 256 - 16 - 1
+    # the flag does not hang on the rays from inside the box alone
+    e, x, _ = PB.slab32(case["origins"], case["dirs"], case["vshape"], case["sr"], case["t_near"], case["seed"], PB.RAY_BASE)
+    for S in case["clips"]:
+        assert PB.group_trace(case["origins"], e, x, case["dirs"], n, case["vshape"], S, case["live"] & ~inside)[0].staggered
+    for r in (1, 64, 65):
+        case = PB.edge_case("group_edges_%d" % r)
+        trace, n = _edge_trace(case, None)
+        assert n.shape[0] == 512 + r and len(trace) == 3
+        assert trace[0] is not None and trace[1] is None and trace[2] is not None   # the middle group returns early
+        assert (n[256:512] > 1).all() and (case["grad_out"][256:512] == 0).all()
+        assert (n[512:-1] == 0).all() and n[-1] > 1 and case["live"][-1]          # the last lane alone is live
+
+
+@pytest.mark.parametrize("mode", ["sum", "max"])
+@pytest.mark.parametrize("shape", sorted(PB.SHAPES))
+@pytest.mark.parametrize("bundle", sorted(BR.BUNDLES))
+def test_every_clipped_gradient_case_keeps_its_rays(bundle, shape, mode):
+    n_free = PB.run(PB.inputs(bundle, *PB.SHAPES[shape]), mode, grads=False)["n"]
+    for S in PB.CLIPS:
+        inp = PB.inputs(bundle, *PB.SHAPES[shape], max_samples=PB.clip(S, n_free))
+        ref, ref32 = PB.run(inp, mode), PB.run(inp, mode, torch.float32)
+        same, live = PB.agree(ref, ref32, mode)
+        assert live.sum() >= 100 and (same & live).sum() >= 0.9 * live.sum(), (S, same.sum(), live.sum())
+        assert np.isfinite(ref["d_origin"]).all() and np.abs(ref["d_origin"][live]).max() > 0
+
+
+@pytest.mark.parametrize("mode", ["sum", "max"])
+@pytest.mark.parametrize("axis,sign", PB.AXES)
+def test_axis_parallel_reference_gradients_are_finite_and_keep_their_rays(axis, sign, mode):
+    for S in PB.AXIS_CLIPS:
+        inp = PB.axis_inputs(axis, sign, S)
+        assert (inp["dirs"][:, axis] == sign).all() and (np.delete(inp["dirs"], axis, 1) == 0).all()
+        assert (np.abs(np.delete(inp["origins"], axis, 1)) < 0.9).all() and (inp["origins"][:, axis] == -2.5 * sign).all()
+        ref, ref32 = PB.run(inp, mode), PB.run(inp, mode, torch.float32)
+        same, live = PB.agree(ref, ref32, mode)
+        assert live.all() and (ref["n"] > 9).all() and (same & live).sum() >= 0.9 * live.sum()
+        for r in (ref, ref32):
+            six = np.concatenate([r["d_origin"], r["d_dir"]], 1)
+            assert np.isfinite(six).all() and (six != 0).any(1).all()
+
+
+@pytest.mark.parametrize("mode", ["sum", "max"])
+def test_the_f16_volume_case_keeps_its_rays(mode):
+    inp = PB.inputs("random", *PB.SHAPES["sr1"], dtype=torch.float16)
+    assert np.array_equal(inp["vol"], inp["vol"].astype(np.float16).astype(np.float64))
+    same, live = PB.agree(PB.run(inp, mode, grads=False), PB.run(inp, mode, torch.float32, grads=False), mode)
+    assert live.sum() >= 100 and (same & live).sum() >= 0.9 * live.sum()
+
+
+@pytest.mark.parametrize("mode", ["sum", "max"])
+def test_the_cone_source_case_keeps_its_rays(mode):
+    cone, seed = PB.CONE_SMALL, PB.module_jitter_seed()
+    assert seed == PB.module_jitter_seed() != 0
+    vol = torch.rand((24, 24, 24), generator=torch.Generator().manual_seed(9)).double().numpy()
+    inp = dict(vol=vol, sr=1.0, max_samples=None, jitter_seed=seed, ray_base=0)
+    ref, ref32 = (PB.source_gradient(cone, inp, mode, dt) for dt in (torch.float64, torch.float32))
+    same, live = PB.agree(ref, ref32, mode)
+    assert live.sum() > 200 and (same & live).sum() >= 0.9 * live.sum(), (same.sum(), live.sum())
+    g = PB.F32(np.random.RandomState(5).standard_normal(live.size) * (same & live))
+    want = PB.source_gradient(cone, inp, mode, torch.float64, g)["d_source"]
+    assert np.isfinite(want).all() and np.abs(want).max() > 0
+    # the small cone is the spreading cone's: the same source, detector plane and extent
+    assert all(PB.CONE[k] == cone[k] for k in ("source", "det_center"))
+    assert cone["det"][0] * cone["det_u"][0] == PB.CONE["det"][0] * PB.CONE["det_u"][0]
 
 
 # --- 6. the module's argument checks ------------------------------------------------------------------------------------------------
