@@ -3,7 +3,8 @@
 // and unit directions [N][3] in look_from's world coordinates, with gradients back to both. The per-sample work is the plain
 // kernels' (march_baseline.hip, camera_grad.hip), statement for statement, with the ray's origin where they read the view's
 // camera and the light at origin + e_y per ray: a bundle made of a pinhole camera's rays is that camera's image, bit for bit.
-// One departure: the volume / TF backward projects a sample's adjoint with a normal from double taps (shade_for_adjoint).
+// One departure: the backwards project a sample's adjoint with a normal from double taps (shade_for_adjoint; the ray gradient
+// around the sample's position in double as well, shade_for_ray_adjoint).
 //
 // Shape: dr_bundle.h's -- one lane per ray over the linear ray index, the coherence of a bundle being the caller's ray order.
 //
@@ -130,6 +131,42 @@ __device__ __forceinline__ Sample shade_for_adjoint(const VolView<VT> &v, f3 lig
     return sa;
 }
 
+// A ray's sample distances in double, from the origin and direction the kernels read: bundle_setup_kernel's slab test, t_near
+// clamp and jitter offset and load_ray's t0, every operation in double (n is the forward's). For the ray gradient's normal.
+struct GeomF64 { double t0, exit_; };
+__device__ __forceinline__ GeomF64 bundle_geom_f64(f3 lf, f3 vd, int n, float t_near, float u) {
+    const double fx = 1.0 / (double)vd.x, fy = 1.0 / (double)vd.y, fz = 1.0 / (double)vd.z;
+    const double t1 = (-1.0 - (double)lf.x) * fx, t2 = (1.0 - (double)lf.x) * fx;
+    const double t3 = (-1.0 - (double)lf.y) * fy, t4 = (1.0 - (double)lf.y) * fy;
+    const double t5 = (-1.0 - (double)lf.z) * fz, t6 = (1.0 - (double)lf.z) * fz;
+    double tmin = fmax(fmax(fmin(t1, t2), fmin(t3, t4)), fmin(t5, t6));
+    const double tmax = fmin(fmin(fmax(t1, t2), fmax(t3, t4)), fmax(t5, t6));
+    if (t_near > -INFINITY) tmin = fmax(tmin, (double)t_near);
+    const double entry = tmin + (double)u * (tmax - tmin) / (double)n;
+    GeomF64 g;
+    g.t0 = entry + 0.5 * (tmax - entry) / (double)n;
+    g.exit_ = tmax;
+    return g;
+}
+
+// The sample `sm` of a ray gradient shaded again for the adjoint: shade_for_adjoint's double taps, taken around sample s's
+// position in double (GeomF64) rather than around the float32 position. A sample whose normal taps straddle a cell boundary
+// where |grad| is 1e-4 can carry a ray's whole d_origin and d_dir (the slope's jump across the boundary over |grad|), and its
+// normal then moves by 5e-4 with the 1e-7 of a float32 position as it does with the 6e-8 of two float32 taps (measured:
+// tests/test_gpu_bundle_edges.py, the f16 volume's ray 1 and c_clip x ortho's ray 33).
+template <typename VT>
+__device__ __forceinline__ Sample shade_for_ray_adjoint(const VolView<VT> &v, f3 lf, f3 light, f3 vd, const GeomF64 &gd, int n,
+                                                        int s, const Sample &sm) {
+    const double f = (double)s / (double)(n - 1), t = gd.t0 * (1.0 - f) + gd.exit_ * f, delta = 1e-3;
+    const double px = (double)lf.x + t * (double)vd.x, py = (double)lf.y + t * (double)vd.y, pz = (double)lf.z + t * (double)vd.z;
+    const float dx = (float)(tri_sample_f64(v, px + delta, py, pz) - tri_sample_f64(v, px - delta, py, pz));
+    const float dy = (float)(tri_sample_f64(v, px, py + delta, pz) - tri_sample_f64(v, px, py - delta, pz));
+    const float dz = (float)(tri_sample_f64(v, px, py, pz + delta) - tri_sample_f64(v, px, py, pz - delta));
+    Sample sa = sm;
+    shade_from_grad<false>(dx, dy, dz, light, vd, true, sa);
+    return sa;
+}
+
 // march_bwd_baseline_kernel without the RayFilter machinery, the adjoint projected with shade_for_adjoint's normal; TABLES: its
 // three tiers (dr_tile.h's table_tier)
 template <typename VT, int TABLES>
@@ -207,6 +244,8 @@ __global__ __launch_bounds__(256) void bundle_ray_grad_kernel(BundleParams<VT> P
         open_adjoint(ray, p, P.grad_out, P.out_fwd);
         const float4 go = ray.go, of = ray.of;
         const float delta = 1e-3f;
+        const float u = P.jitter_seed != 0u ? jitter_u(P.jitter_seed, P.ray_base, (uint32_t)p) : 0.0f;
+        const GeomF64 gd = bundle_geom_f64(lf, vd, rg.n, P.t_near, u);
         f3 sP = make_f3(0.f, 0.f, 0.f), sTG = make_f3(0.f, 0.f, 0.f);
         float s0 = 0.f, s1 = 0.f;
         Composite c;
@@ -226,8 +265,9 @@ __global__ __launch_bounds__(256) void bundle_ray_grad_kernel(BundleParams<VT> P
             const float dz = vp - vm;
             ddz = make_f3(gp.x - gm.x, gp.y - gm.y, gp.z - gm.z);
             shade_from_grad<false>(dx, dy, dz, light, vd, true, sm);
-            const float T = c.add(sm);
+            const float T = c.add(sm);   // (the forward's composite, its bits)
             const bool last = s == nmarch - 1;
+            sm = shade_for_ray_adjoint(vol, lf, light, vd, gd, rg.n, s, sm);   // from here on: the adjoint's normal
             SampleAdj ad;
             sample_adjoint(sm, vd, T, c.suffix(go, of), last, go, P.inv_sr, ad);
             const float I_bar = intensity_adjoint(sm, tf[sm.lo], tf[sm.hi], ad, P.tf_len);
@@ -266,7 +306,6 @@ __global__ __launch_bounds__(256) void bundle_ray_grad_kernel(BundleParams<VT> P
         const SlabFaces sf = slab_faces(lf, vd);
         const bool clamped = P.t_near > -INFINITY && sf.tmin < P.t_near;
         const float nf = (float)rg.n;
-        const float u = P.jitter_seed != 0u ? jitter_u(P.jitter_seed, P.ray_base, (uint32_t)p) : 0.0f;
         const float Acoef = (1.0f - u / nf) * (1.0f - 0.5f / nf);
         const float k_min = clamped ? 0.0f : s0 * Acoef, k_max = fmaf(s0, 1.0f - Acoef, s1);
         const f3 emin = make_f3(sf.amin == 0 ? 1.0f : 0.0f, sf.amin == 1 ? 1.0f : 0.0f, sf.amin == 2 ? 1.0f : 0.0f);

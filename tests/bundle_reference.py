@@ -161,13 +161,134 @@ GRAD_CASES += [("a_orbit_sr1", "random_jitter"), ("m_object_in_air", "ortho"), (
 RAY_BASE = 3
 
 
+# ---- the bundles of tests/test_gpu_bundle_edges.py: exact zeros in the direction, the t_near clamp some rays take, one sample ----
+# (No origin has a coordinate of exactly +-1 on an axis whose direction component is 0: there the kernels' 0 * inf is a NaN that
+# fminf / fmaxf drop and torch.minimum keeps, and the two programs define different things.)
+
+def axial_bundle(per_axis=16):
+    """16 rays along each of +-x, +-y, +-z: the direction exactly +-e_axis, the origin 2.5 off the centre on that axis and
+    uniform in (-0.85, 0.85) on the two others (proj_bundle_reference.axis_inputs' rays, all six axes in one bundle)."""
+    os_, ds = [], []
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            rng = np.random.RandomState(10 * axis + (sign > 0))
+            o = rng.uniform(-0.85, 0.85, (per_axis, 3))
+            o[:, axis] = -2.5 * sign
+            d = np.zeros((per_axis, 3))
+            d[:, axis] = sign
+            os_.append(o)
+            ds.append(d)
+    return np.concatenate(os_), np.concatenate(ds)
+
+
+def one_zero_bundle(P=96):
+    """Rays with exactly one zero direction component, ray p's at index p % 3, aimed at points in [-0.8, 0.8]^3 from 2.2 .. 3.5
+    units back along the direction: every ray hits, and its origin's coordinate on the zero axis is its target's."""
+    rng = np.random.RandomState(21)
+    d = rng.standard_normal((P, 3))
+    d[np.arange(P), np.arange(P) % 3] = 0.0
+    d = _unit(d)
+    return rng.uniform(-0.8, 0.8, (P, 3)) - rng.uniform(2.2, 3.5, (P, 1)) * d, d
+
+
+SINGLE = np.arange(64) % 8 == 3   # where single_sample_bundle puts its short rays: eight lanes of one wave
+
+
+def single_sample_bundle():
+    """random_bundle's first 56 rays with eight rays among them (SINGLE) that start inside the box 0.01 in front of the face
+    x = 1 they leave through: under t_near = 0, which touches none of the 56 (their entry distances are positive), their chord
+    is 0.01 < 1 / (sr diag) and n == 1."""
+    o56, d56 = random_bundle(56)
+    rng = np.random.RandomState(33)
+    d8 = _unit(np.concatenate([rng.uniform(0.5, 1.0, (8, 1)), rng.uniform(-0.5, 0.5, (8, 2))], 1))
+    o8 = np.concatenate([np.ones((8, 1)), rng.uniform(-0.6, 0.6, (8, 2))], 1) - 0.01 * d8
+    o, d = np.empty((64, 3)), np.empty((64, 3))
+    o[SINGLE], d[SINGLE], o[~SINGLE], d[~SINGLE] = o8, d8, o56, d56
+    return o, d
+
+
+EDGE_BUNDLES = {
+    "axial": (axial_bundle, None, 0),
+    "one_zero": (one_zero_bundle, None, 0),
+    "random_near2": (random_bundle, 2.0, 0),      # some rays take the clamp, others do not
+    "random_near3": (random_bundle, 3.0, 0),      # ... and some die: t_near past their exit
+    "interior_near0_jitter": (interior_bundle, 0.0, 777),
+    "single_sample": (single_sample_bundle, 0.0, 0),
+}
+EDGE_CASES = [(scene, b) for scene in ("a_orbit_sr1", "b_sr2_ert") for b in ("axial", "one_zero")]
+EDGE_CASES += [("c_clip", b) for b in ("random", "ortho", "interior_near0")]   # max_samples = 23 at 24^3: the cap bites
+EDGE_CASES += [("a_orbit_sr1", b) for b in ("random_near2", "random_near3", "interior_near0_jitter")]
+
+TIER_EDGE_R = (3393, 10176, 10177)   # the table in LDS beside d_tf's global atomics; the last R in LDS; the first in global memory
+
+
+def smooth_tier_inputs(R):
+    """The 13 x 12 x 14 volume of tests/test_gpu_bundle.py's table tiers under scene a_orbit_sr1's own 8-texel table resampled
+    linearly to R texels, and random_bundle's first 64 rays: the table is as smooth as the scene's at every R, so a sample's
+    intensity adjoint (a texel slope times R - 1) is conditioned as in the scene."""
+    from oracle import oracle as O
+    rng = np.random.RandomState(R)
+    vol = np.clip(O.synth_volume((13, 12, 14), dtype=np.float64) + 0.02 * rng.standard_normal((13, 12, 14)), 0.0, 1.0)
+    tf8 = CG.make_inputs("a_orbit_sr1")["tf"]
+    at = np.linspace(0.0, 1.0, R)
+    tf = np.stack([np.interp(at, np.linspace(0.0, 1.0, tf8.shape[0]), tf8[:, c]) for c in range(4)], 1)
+    return inputs("a_orbit_sr1", "random", vol=vol, tf=tf, head=64)
+
+
+# The module's cone beam: a 12 x 10 detector behind the box, its centre off the source's axis; detector column 4 lies at
+# x = 0.125 + (4 - 4.5) 0.25 = 0, the source's x, in float32 as in float64 (every term is dyadic): its rays' x component is 0.
+CONE = dict(source=(0.0, 0.15, -2.6), det_center=(0.125, 0.1, 1.5), det_u=(0.25, 0.0, 0.0), det_v=(0.0, 0.2, 0.0), det=(12, 10))
+CONE_ZERO_COLUMN = 4
+
+
+def cone_scale():
+    """The per-ray factor in [0.5, 2] the cone's unit directions are scaled by before the module sees them, (H, W, 1)."""
+    return F32(np.random.RandomState(12).uniform(0.5, 2.0, (*CONE["det"], 1)))
+
+
+def cone_inputs():
+    """Scene a_orbit_sr1 for the cone: vol, tf, sr, max_samples, a random upstream gradient (P, 4); no jitter."""
+    base = CG.make_inputs("a_orbit_sr1")
+    P = CONE["det"][0] * CONE["det"][1]
+    return dict(vol=F32(base["vol"]), tf=F32(base["tf"]), grad_out=F32(np.random.RandomState(P).standard_normal((P, 4))),
+                sr=base["sr"], max_samples=base["max_samples"])
+
+
+def cone_gradient(inp, dtype=torch.float64, pixels=None, grads=True):
+    """`run`'s program behind cone_beam_rays, cone_scale and RayBundleRaycaster.forward's own normalisation, all in `dtype`,
+    the source and the table the leaves -> run's rgba, steps, n (P, 1, ...) in the detector's row-major order, dirs (P, 3), and
+    with grads d_source (3,) and dtf (R, 4) of sum(rgba grad_out) over the rays of `pixels`."""
+    import differender_amd.bundle as B
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64))).to(dtype)
+    src, tf, vol = T(F32(CONE["source"])).requires_grad_(grads), T(inp["tf"]).requires_grad_(grads), T(inp["vol"])
+    o, d = B.cone_beam_rays(src, CONE["det_center"], CONE["det_u"], CONE["det_v"], CONE["det"])
+    d = d * T(cone_scale())
+    d = d / torch.sqrt((d * d).sum(-1, keepdim=True))
+    o, d = o.reshape(-1, 3), d.reshape(-1, 3)
+    P = o.shape[0]
+    e, x, n = slab(o, d, inp["vol"].shape, float(inp["sr"]))
+
+    def march_rays(sel):
+        out, cnt = G.raycast(vol, tf, o[sel], e[sel], x[sel], d[sel], n[sel], int(inp["max_samples"]), float(inp["sr"]))
+        return out, dict(steps=cnt.int())
+
+    with torch.set_grad_enabled(grads):
+        loss, res = G.render_view((P, 1), n, pixels, T(inp["grad_out"]).reshape(P, 4) if grads else None, march_rays)
+    if torch.is_tensor(loss):
+        loss.backward()
+    res.update(n=n.numpy().astype(np.int32).reshape(P, 1), dirs=d.detach().double().numpy())
+    if grads:
+        res.update(d_source=G.grad_or_zero(src), dtf=G.grad_or_zero(tf))
+    return res
+
+
 def inputs(scene, bundle, vol=None, tf=None, head=None, rays=None):
     """The scene of a camera-gradient case (make_camgrad_golden.make_inputs: volume, TF, rate, max_samples) with a bundle of
-    BUNDLES in its camera's place, rounded to what the kernels read; the directions are unit vectors up to that rounding to
-    float32's spacing. vol, tf: others in the scene's place; head: the first `head` rays only; rays: (origins, dirs) in the
-    place of the bundle's own."""
+    BUNDLES or EDGE_BUNDLES in its camera's place, rounded to what the kernels read; the directions are unit vectors up to that
+    rounding to float32's spacing. vol, tf: others in the scene's place; head: the first `head` rays only; rays: (origins, dirs)
+    in the place of the bundle's own."""
     base = CG.make_inputs(scene)
-    make, t_near, seed = BUNDLES[bundle]
+    make, t_near, seed = (BUNDLES.get(bundle) or EDGE_BUNDLES[bundle])
     o, d = make() if rays is None else rays
     o, d = F32(o)[:head], F32(d)[:head]
     P = o.shape[0]

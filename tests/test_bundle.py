@@ -1,6 +1,7 @@
 """Ray bundles, DESIGN.md D19, without a GPU: the C ABI and its argument checks, the two torch helpers against the float64
 pose reference, the new reference (tests/bundle_reference.py) pinned to that one through torch autograd of pinhole_rays, the
-conditions every bundle of the GPU file owes the conditioned pass, and the module's argument checks."""
+conditions every bundle of the GPU files owes the conditioned pass (and, for the edge bundles, that each edge changes the
+gradient), and the module's argument checks."""
 import ctypes
 import math
 import os
@@ -200,6 +201,88 @@ def test_every_gradient_bundle_keeps_its_well_conditioned_rays(scene, bundle):
         assert (ref["n"] == 0).sum() == 4 and (ref["dray"][ref["n"][..., 0] == 0] == 0).all()
     if "near0" in bundle:
         assert (ref["entry"] == 0).all()   # every interior origin takes the clamp
+
+
+def _differs(a, b, rays=None):
+    """The float64 gradients a and b (over `rays`) differ by more than 1e-2 of a's scale."""
+    rays = np.ones(a.shape[:2], bool) if rays is None else rays
+    return np.abs(a - b)[rays].max() > 1e-2 * np.abs(a[rays]).max()
+
+
+@pytest.mark.parametrize("scene,bundle", BR.EDGE_CASES, ids=lambda v: str(v))
+def test_every_edge_bundle_keeps_its_well_conditioned_rays_and_tells_right_from_wrong(scene, bundle):
+    """The same check for the bundles of tests/test_gpu_bundle_edges.py, the structure each is there for, and that the edge
+    matters: the float64 d_origin / d_dir of the program without it is more than 1e-2 of the scale away.
+    Good of n > 1 rays: a_orbit_sr1 axial 93 of 96, one_zero 94 of 96; b_sr2_ert axial 93 of 96, one_zero 89 of 96; c_clip random
+    187 of 192 (all clipped), ortho 136 of 140 (126 clipped), interior_near0 123 of 128 (114 clipped); a_orbit_sr1 random_near2
+    187 of 192 (135 rays take the clamp, 57 do not), random_near3 175 of 180 (12 killed), interior_near0_jitter 123 of 128.
+    BR.keep keeps every ray of all of them."""
+    inp = BR.inputs(scene, bundle)
+    ref, ref32 = BR.refs(inp)
+    K.check_conditions([(ref, ref32, BR.keep(ref, ref32), None)], "dray", BR.COLUMNS)
+    live = ref["n"] > 1
+    o, d = inp["origins"], inp["dirs"]
+    assert not ((d == 0) & (np.abs(o) == 1)).any()   # no origin on a face plane of an axis the ray does not move along
+    other = lambda **kw: BR.run(dict(inp, **kw))
+    if bundle == "axial":
+        assert ((d == 0).sum(1) == 2).all() and (np.abs(d).sum(1) == 1).all() and live.all()
+        assert sorted(set(map(tuple, d))) == sorted(tuple(s * e) for e in np.eye(3) for s in (1.0, -1.0))
+    if bundle == "one_zero":
+        assert ((d == 0).sum(1) == 1).all() and (d[np.arange(len(d)), np.arange(len(d)) % 3] == 0).all() and live.all()
+    if scene == "c_clip":
+        S = int(inp["max_samples"])
+        assert S == 23 and (ref["n"][live] > S).sum() >= 0.8 * live.sum() and ref["steps"].max() == S
+        assert _differs(ref["dray"], other(max_samples=4096)["dray"])
+    if bundle == "random_near2":
+        off = other(t_near=None)
+        clamped = ref["entry"] > off["entry"]
+        assert (ref["entry"][clamped] == 2.0).all() and (ref["n"][clamped] <= off["n"][clamped]).all()
+        assert (ref["n"][clamped] < off["n"][clamped]).sum() > 50   # (a clamp of less than a sample's spacing keeps n)
+        assert (clamped & live).sum() > 50 and (~clamped & live).sum() > 50
+        assert _differs(ref["dray"], off["dray"], clamped)
+        assert np.array_equal(ref["dray"][~clamped], off["dray"][~clamped])
+    if bundle == "random_near3":
+        off = BR.run(dict(inp, t_near=None), grads=False)
+        killed = (ref["n"] == 0) & (off["n"] > 1)
+        assert killed.sum() >= 8 and (ref["dray"][killed] == 0).all() and (ref["rgba"][killed] == 0).all()
+    if bundle == "interior_near0_jitter":
+        assert (ref["entry"] > 0).all()   # every origin takes the clamp, and the draw moves the first sample off it
+        assert _differs(ref["dray"], other(jitter_seed=0)["dray"])
+
+
+def test_the_single_sample_set_has_single_sample_rays_among_rays_the_clamp_leaves_alone():
+    inp = BR.inputs("a_orbit_sr1", "single_sample")
+    ref, ref32 = BR.run(inp), BR.run(inp, torch.float32)
+    off = BR.run(dict(inp, t_near=None), grads=False)
+    one, rest = BR.SINGLE, ~BR.SINGLE
+    assert one.sum() == 8 and (ref["n"][one] == 1).all() and (ref32["n"][one] == 1).all() and (off["n"][one] > 1).all()
+    assert (ref["dray"][one] == 0).all() and (ref["rgba"][one] == 0).all()   # H6: the reference marches no such ray
+    assert (ref["n"][rest] > 1).all() and np.array_equal(ref["n"][rest], off["n"][rest])
+    assert np.array_equal(ref["entry"][rest], off["entry"][rest])
+
+
+@pytest.mark.parametrize("R", BR.TIER_EDGE_R)
+def test_the_smooth_table_tiers_keep_their_well_conditioned_rays(R):
+    """Good of 64: R = 3393 59, 10176 64, 10177 62."""
+    inp = BR.smooth_tier_inputs(R)
+    assert inp["tf"].shape == (R, 4) and inp["origins"].shape == (64, 3)
+    ref, ref32 = BR.refs(inp)
+    assert (ref["n"] > 1).all()
+    K.check_conditions([(ref, ref32, BR.keep(ref, ref32), None)], "dray", BR.COLUMNS)
+
+
+def test_the_modules_cone_beam_has_a_zero_component_column_and_keeps_its_rays():
+    """120 of 120 rays hit and are kept; detector column 4's x component is exactly 0 in both precisions."""
+    inp = BR.cone_inputs()
+    ref, ref32 = BR.cone_gradient(inp, grads=False), BR.cone_gradient(inp, torch.float32, grads=False)
+    H, W = BR.CONE["det"]
+    for r in (ref, ref32):
+        d = r["dirs"].reshape(H, W, 3)
+        assert (d[:, BR.CONE_ZERO_COLUMN, 0] == 0).all() and (d != 0).sum() == 3 * H * W - H
+    live = ref["n"] > 1
+    assert live.sum() > 0.8 * H * W and (BR.keep(ref, ref32) & live).sum() > 0.8 * live.sum()
+    scale = BR.cone_scale()
+    assert scale.min() >= 0.5 and scale.max() <= 2.0 and np.abs(scale - 1.0).min() > 1e-4   # no ray is handed over as a unit vector
 
 
 # --- 5. the module's argument checks ------------------------------------------------------------------------------------------------
