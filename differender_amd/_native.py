@@ -111,6 +111,12 @@ SIGNATURES = {
                                    _P, _L, _L, _L, _I, _P]),
     "dr_project_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _I, _F, _U, _U,
                                         _P, _P, _P, _P, _P]),
+    # the RGBA march of a ray bundle: the bundle's arguments with the RGBA volume's (sc, dsc) in the table's place
+    "dr_march_rgba_bundle_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P]),
+    "dr_march_rgba_bundle_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P,
+                                      _P, _L, _L, _L, _L, _P]),
+    "dr_march_rgba_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _F,
+                                           _P, _F, _U, _U, _P, _P, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

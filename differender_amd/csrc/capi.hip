@@ -979,6 +979,73 @@ int dr_project_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, i
     return launch_on(vol, launch_project_bundle_ray_grad, a, b, q, (hipStream_t)stream);
 }
 
+// the three RGBA bundle marches: fill_rgba for one volume and one view of N x 1 rays whose camera rows are the
+// origins (max_samples >= 1, a finite rate); always differentiable
+static int fill_rgba_bundle(MarchArgs &a, RgbaArgs &q, BundleArgs &b, const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                            int64_t sx, int64_t sy, int64_t sz, int64_t sc, const float *origins, const float *dirs,
+                            const float *entry, const float *exit_, const int32_t *nsamp, int64_t N, int max_samples,
+                            float sampling_rate, float t_near = 0.0f) {
+    if (!bundle_fits(N, t_near)) return DR_EINVAL;
+    const int rc = fill_rgba(a, q, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, 0, origins, entry, exit_, dirs, nsamp, 1, (int)N, 1,
+                             max_samples, sampling_rate);
+    if (rc) return rc;
+    a.mode = DR_MODE_DIFF;
+    b = BundleArgs{};
+    b.origins = origins; b.N = (int)N; b.t_near = t_near;
+    return 0;
+}
+
+int dr_march_rgba_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                             const float *origins, const float *dirs, const float *entry, const float *exit_,
+                             const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate, float *out_rgba,
+                             int32_t *steps, void *stream) {
+    MarchArgs a;
+    RgbaArgs q;
+    BundleArgs b;
+    const int rc = fill_rgba_bundle(a, q, b, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, origins, dirs, entry, exit_, nsamp, N,
+                                    max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!out_rgba) return DR_EINVAL;
+    a.out = out_rgba; a.steps = steps;
+    return launch_on(vol, launch_march_rgba_bundle_fwd, a, q, b, (hipStream_t)stream);
+}
+
+int dr_march_rgba_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                             const float *origins, const float *dirs, const float *entry, const float *exit_,
+                             const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate, const float *grad_out,
+                             const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dsc,
+                             void *stream) {
+    MarchArgs a;
+    RgbaArgs q;
+    BundleArgs b;
+    const int rc = fill_rgba_bundle(a, q, b, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, origins, dirs, entry, exit_, nsamp, N,
+                                    max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!grad_out || !out_rgba) return DR_EINVAL;
+    if (!d_vol) return 0;  // nothing requested
+    a.grad_out = grad_out; a.out_fwd = out_rgba;
+    a.d_vol = d_vol; a.dsx = dsx; a.dsy = dsy; a.dsz = dsz;
+    q.dsc = dsc;
+    return launch_on(vol, launch_march_rgba_bundle_bwd, a, q, b, (hipStream_t)stream);
+}
+
+int dr_march_rgba_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                                  int64_t sc, const float *origins, const float *dirs, const float *entry, const float *exit_,
+                                  const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate, const int32_t *steps,
+                                  float t_near, uint32_t jitter_seed, uint32_t ray_base, const float *grad_out,
+                                  const float *out_rgba, float *d_origins, float *d_dirs, void *stream) {
+    MarchArgs a;
+    RgbaArgs q;
+    BundleArgs b;
+    const int rc = fill_rgba_bundle(a, q, b, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, sc, origins, dirs, entry, exit_, nsamp, N,
+                                    max_samples, sampling_rate, t_near);
+    if (rc) return rc;
+    if (!steps || !grad_out || !out_rgba || !d_origins || !d_dirs) return DR_EINVAL;
+    a.grad_out = grad_out; a.out_fwd = out_rgba;
+    b.steps = steps; b.jitter_seed = jitter_seed; b.ray_base = ray_base; b.d_origins = d_origins; b.d_dirs = d_dirs;
+    return launch_on(vol, launch_rgba_bundle_ray_grad, a, q, b, (hipStream_t)stream);
+}
+
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,
                         void *stream) {
     if (!tf || !d_tf || !momentum || n <= 0 || !(max_grad >= 0.0f)) return DR_EINVAL;

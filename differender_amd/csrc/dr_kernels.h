@@ -217,6 +217,14 @@ __attribute__((weak)) int launch_project_bundle_fwd(const MarchArgs &a, const Bu
 __attribute__((weak)) int launch_project_bundle_bwd(const MarchArgs &a, const BundleArgs &b, const ProjArgs &q, hipStream_t stream);
 __attribute__((weak)) int launch_project_bundle_ray_grad(const MarchArgs &a, const BundleArgs &b, const ProjArgs &q, hipStream_t stream);
 
+// The RGBA march over a bundle of rays (march_rgba_bundle.hip): dr_march_rgba_bundle_fwd / _bwd / _bwd_rays take
+// the bundle's MarchArgs without a table (n_views = 1, W = N, H = 1, cam the origins, rays the directions; one volume, no view
+// strides), the RGBA march's RgbaArgs and the bundle's BundleArgs
+// weak, as launch_camera_grad: capi.o must load in a library linked without march_rgba_bundle.o
+__attribute__((weak)) int launch_march_rgba_bundle_fwd(const MarchArgs &a, const RgbaArgs &q, const BundleArgs &b, hipStream_t stream);
+__attribute__((weak)) int launch_march_rgba_bundle_bwd(const MarchArgs &a, const RgbaArgs &q, const BundleArgs &b, hipStream_t stream);
+__attribute__((weak)) int launch_rgba_bundle_ray_grad(const MarchArgs &a, const RgbaArgs &q, const BundleArgs &b, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

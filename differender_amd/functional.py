@@ -20,6 +20,7 @@ __all__ = ["ray_setup", "ray_setup_pose", "pack_pose", "march_fwd", "march_bwd",
            "msssim_mse_loss_grad", "tv3d_fwd", "tv3d_bwd", "tf_momentum_step", "as_volume", "bwd_is_sanitised", "termination_hints"]
 __all__ += ["bundle_setup", "march_bundle_fwd", "march_bundle_bwd", "march_bundle_bwd_rays"]
 __all__ += ["project_bundle_fwd", "project_bundle_bwd", "project_bundle_bwd_rays"]
+__all__ += ["march_rgba_bundle_fwd", "march_rgba_bundle_bwd", "march_rgba_bundle_bwd_rays"]
 
 
 def _stream():
@@ -870,6 +871,61 @@ def march_bundle_bwd_rays(vol, tf, origins, dirs, entry, exit_, n, steps, max_sa
     d_origins = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
     d_dirs = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
     _call("dr_march_bundle_bwd_rays", vol.device, *head, steps.data_ptr(), _t_near(t_near), int(jitter_seed) & 0xFFFFFFFF,
+          int(ray_base) & 0xFFFFFFFF, grad_out.data_ptr(), out.data_ptr(), d_origins.data_ptr(), d_dirs.data_ptr())
+    return d_origins, d_dirs
+
+
+def _rgba_bundle_head(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate):
+    """What the three RGBA bundle marches start with -> (origins, dirs, N, their C-ABI arguments up to sampling_rate): one RGBA
+    volume (4, VX, VY, VZ), float32 or float16, with any strides."""
+    _require_gpu(vol4, "volume")
+    origins, dirs, n_rays = _bundle_rays(origins, dirs)
+    if vol4.ndim != 4:
+        raise ValueError(f"a bundle is marched through one RGBA volume (4,VX,VY,VZ), got {tuple(vol4.shape)}")
+    for name, t in (("entry", entry), ("exit", exit_), ("n", n)):
+        if tuple(t.shape) != (n_rays,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be bundle_setup's contiguous ({n_rays},) buffer, got {tuple(t.shape)}")
+    return origins, dirs, n_rays, (*_vol4_args(vol4, 1)[:9], origins.data_ptr(), dirs.data_ptr(), entry.data_ptr(),
+                                   exit_.data_ptr(), n.data_ptr(), n_rays, int(max_samples), float(sampling_rate))
+
+
+def march_rgba_bundle_fwd(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate, want_steps=True):
+    """The differentiable RGBA march of a bundle's rays (dr_march_rgba_bundle_fwd): march_rgba_fwd's DR_MODE_DIFF
+    samples with the ray's origin in the camera's place; origins, dirs (N, 3) and the buffers of bundle_setup. Returns out (N, 4)
+    and steps (N,) int32 (or None): for a pinhole view's rays, the bits of march_rgba_fwd."""
+    origins, dirs, n_rays, head = _rgba_bundle_head(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    out = torch.empty((n_rays, 4), dtype=torch.float32, device=vol4.device)
+    steps = torch.empty((n_rays,), dtype=torch.int32, device=vol4.device) if want_steps else None
+    _call("dr_march_rgba_bundle_fwd", vol4.device, *head, out.data_ptr(), _ptr(steps))
+    return out, steps
+
+
+def march_rgba_bundle_bwd(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate, grad_out, out, d_vol=None):
+    """d_vol of sum(march_rgba_bundle_fwd(...) * grad_out) (dr_march_rgba_bundle_bwd): float32, in vol4's own layout -- or
+    accumulated into `d_vol`, a float32 tensor of vol4's shape with any strides, which is then returned. NaN propagates (the
+    plain kernels' convention: the caller applies nan_to_num, as rgba.RayBundleRaycasterRGBA does)."""
+    origins, dirs, n_rays, head = _rgba_bundle_head(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    grad_out, out = _bwd_images(grad_out, out)
+    if d_vol is None:
+        d_vol = torch.zeros_like(vol4, dtype=torch.float32, memory_format=torch.preserve_format)
+    elif d_vol.dtype != torch.float32 or d_vol.shape != vol4.shape or d_vol.device != vol4.device:
+        raise ValueError(f"d_vol must be a float32 tensor of the volume's shape {tuple(vol4.shape)} on its device")
+    dc, dx, dy, dz = d_vol.stride()
+    _call("dr_march_rgba_bundle_bwd", vol4.device, *head, grad_out.data_ptr(), out.data_ptr(), d_vol.data_ptr(), dx, dy, dz, dc)
+    return d_vol
+
+
+def march_rgba_bundle_bwd_rays(vol4, origins, dirs, entry, exit_, n, steps, max_samples, sampling_rate, grad_out, out, t_near=None,
+                               jitter_seed=0, ray_base=0):
+    """Gradient of march_rgba_bundle_fwd w.r.t. every ray's origin and direction (dr_march_rgba_bundle_bwd_rays):
+    the buffers, t_near, jitter_seed and ray_base those of bundle_setup, `steps` and `out` those of march_rgba_bundle_fwd.
+    Returns d_origins, d_dirs (N, 3) float32 -- d_dirs w.r.t. the direction as a free 3-vector. A NaN ray gets zeros (D5)."""
+    origins, dirs, n_rays, head = _rgba_bundle_head(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    grad_out, out = _bwd_images(grad_out, out)
+    steps = steps.to(torch.int32).contiguous()
+    d_origins = torch.empty((n_rays, 3), dtype=torch.float32, device=vol4.device)
+    d_dirs = torch.empty((n_rays, 3), dtype=torch.float32, device=vol4.device)
+    _call("dr_march_rgba_bundle_bwd_rays", vol4.device, *head, steps.data_ptr(), _t_near(t_near), int(jitter_seed) & 0xFFFFFFFF,
           int(ray_base) & 0xFFFFFFFF, grad_out.data_ptr(), out.data_ptr(), d_origins.data_ptr(), d_dirs.data_ptr())
     return d_origins, d_dirs
 

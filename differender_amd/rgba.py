@@ -17,8 +17,15 @@ gradients, as Raycaster and Projector do (pose.py); the default module refuses a
 
 `interleaved(volume)` stores the four channels of a voxel next to each other, which lets the kernels fetch a voxel with one
 load; the rendered bits are the same.
+
+RayBundleRaycasterRGBA marches the same volumes along rays that are inputs, as bundle.RayBundleRaycaster does
+for the TF raycaster: random minibatches of rays across views, parallel and cone beams, distorted lenses, per-ray masks.
+
+    rc = RayBundleRaycasterRGBA(volume.shape[-3:], ray_grad=True)
+    rgba = rc(volume, origins, directions)             # (4,D,H,W), (..., 3), (..., 3) -> (..., 4)
 """
 import functools
+import math
 
 import torch
 
@@ -26,7 +33,8 @@ from . import _layout as L
 from . import _native as N
 from . import functional as F
 
-__all__ = ["RaycasterRGBA", "RgbaRaycastFunction", "RgbaCameraFunction", "interleaved"]
+__all__ = ["RaycasterRGBA", "RgbaRaycastFunction", "RgbaCameraFunction", "interleaved", "RayBundleRaycasterRGBA",
+           "RgbaRayBundleFunction"]
 
 
 def interleaved(volume):
@@ -135,3 +143,100 @@ class RaycasterRGBA(L.RayModule):
 
     def extra_repr(self):
         return f"Volume ({self.volume_shape}), Output Render ({self.output_shape}), Max Samples = {self.max_samples}"
+
+
+class RgbaRayBundleFunction(torch.autograd.Function):
+    """Autograd boundary of the RGBA bundle march: `apply(rc, volume, origins, dirs, sampling_rate, jitter)`. volume (4,W,D,H),
+    float32 or float16, any strides; origins, dirs (N,3), the directions of unit length. Returns (N,4). origins and dirs receive
+    gradients where they require them (RayBundleRaycasterRGBA refuses that unless built with ray_grad=True)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, rc, volume, origins, dirs, sampling_rate, jitter=True):
+        volume = F.as_volume(volume)
+        origins, dirs = origins.float().contiguous(), dirs.float().contiguous()
+        seed = F.new_jitter_seed() if jitter else 0
+        e, x, n = F.bundle_setup(origins, dirs, volume.shape[-3:], sampling_rate, rc.t_near, seed)
+        out, steps = F.march_rgba_bundle_fwd(volume, origins, dirs, e, x, n, rc.max_samples, sampling_rate)
+        ctx.save_for_backward(volume, origins, dirs, e, x, n, steps, out)
+        ctx.rc, ctx.sampling_rate, ctx.seed = rc, sampling_rate, seed
+        rc._steps = steps
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_output):
+        volume, origins, dirs, e, x, n, steps, out = ctx.saved_tensors
+        rc, sr = ctx.rc, ctx.sampling_rate
+        dv = d_o = d_d = None
+        if ctx.needs_input_grad[1]:
+            dv = L.sanitised(F.march_rgba_bundle_bwd(volume, origins, dirs, e, x, n, rc.max_samples, sr, grad_output, out))
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            d_o, d_d = F.march_rgba_bundle_bwd_rays(volume, origins, dirs, e, x, n, steps, rc.max_samples, sr, grad_output, out,
+                                                    rc.t_near, ctx.seed)
+        return (None, dv, d_o if ctx.needs_input_grad[2] else None, d_d if ctx.needs_input_grad[3] else None, None, None)
+
+
+class RayBundleRaycasterRGBA(torch.nn.Module):
+    """The RGBA raycaster over a bundle of rays.
+
+    volume_shape (D, H, W) as for RaycasterRGBA.
+    forward(volume (4,D,H,W), origins (...,3), directions (...,3)) -> (...,4) RGBA; one volume per call, float32 or float16, any
+    strides (`interleaved(volume)`: a voxel is one load).
+    t_near: None marches the reference's line through the box, which also shows what lies behind an origin inside it (so a
+    pinhole camera's rays give RaycasterRGBA's image); 0.0 makes every ray start at its origin.
+    ray_grad=True: origins and directions may require grad and receive their gradients."""
+
+    def __init__(self, volume_shape, sampling_rate=1.0, jitter=True, max_samples=512, t_near=None, ray_grad=False):
+        super().__init__()
+        if len(tuple(volume_shape)) != 3:
+            raise ValueError("expected volume_shape (D, H, W)")
+        if int(max_samples) < 1:
+            raise ValueError(f"max_samples must be >= 1, got {max_samples}")
+        if t_near is not None and math.isnan(float(t_near)):
+            raise ValueError("t_near must be a number or None")
+        self.volume_shape = (int(volume_shape[2]), int(volume_shape[0]), int(volume_shape[1]))  # (W, D, H), as RaycasterRGBA
+        self.sampling_rate, self.jitter, self.max_samples = sampling_rate, jitter, int(max_samples)
+        self.t_near = None if t_near is None else float(t_near)
+        self.ray_grad = bool(ray_grad)
+        self._steps = None
+        N.lib()  # fail loudly at construction time if the HIP library is missing
+
+    def _check(self, volume, origins, directions):
+        expected = "volume (4,D,H,W), origins (...,3), directions (...,3) of one shape"
+        if volume.ndim != 4 or volume.shape[0] != 4:
+            raise ValueError(f"expected {expected}; got volume {tuple(volume.shape)}")
+        w, d, h = self.volume_shape
+        if tuple(volume.shape[-3:]) != (d, h, w):
+            raise ValueError(f"volume has (D, H, W) = {tuple(volume.shape[-3:])}, the module was built for {(d, h, w)}")
+        if origins.ndim < 1 or origins.shape[-1] != 3 or origins.shape != directions.shape or origins.numel() == 0:
+            raise ValueError(f"expected {expected}; got origins {tuple(origins.shape)}, directions {tuple(directions.shape)}")
+
+    @staticmethod
+    def _check_devices(volume, origins, directions):
+        for name, t in (("volume", volume), ("origins", origins), ("directions", directions)):
+            F._require_gpu(t, name)
+            if t.device != volume.device:
+                raise ValueError(f"{name} lives on {t.device}, the volume on {volume.device}")
+
+    def forward(self, volume, origins, directions):
+        """volume (4,D,H,W), origins, directions (...,3) -> (...,4). The directions are normalised here, in torch (a zero-length
+        one raises), so their gradient is that of the direction handed in."""
+        self._check(volume, origins, directions)
+        if not self.ray_grad:
+            L.refuse_pose_grad("RayBundleRaycasterRGBA", "construct RayBundleRaycasterRGBA(..., ray_grad=True) for ray gradients",
+                               origins=origins, directions=directions)
+        length = torch.sqrt((directions * directions).sum(-1, keepdim=True))
+        if bool((length == 0).any()):
+            raise ValueError("a direction has zero length")
+        self._check_devices(volume, origins, directions)
+        dirs = (directions / length).reshape(-1, 3)
+        out = RgbaRayBundleFunction.apply(self, L.field_view_rgba(volume), origins.reshape(-1, 3), dirs, self.sampling_rate,
+                                          self.jitter)
+        steps = self._steps
+        self._steps = None if steps is None else steps.reshape(origins.shape[:-1])
+        return out.reshape(*origins.shape[:-1], 4)
+
+    def extra_repr(self):
+        return (f"Volume ({self.volume_shape}), Max Samples = {self.max_samples}, t_near = {self.t_near}, "
+                f"ray_grad = {self.ray_grad}")

@@ -706,6 +706,42 @@ int dr_project_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, i
                                const float *grad_out, const int32_t *arg_max,
                                float *d_origins, float *d_dirs, void *stream);
 
+/* The differentiable march through a pre-classified RGBA volume over an arbitrary bundle of rays:
+ * dr_march_rgba_fwd's DR_MODE_DIFF march and its backwards with a ray as an input, as dr_march_bundle_fwd / _bwd / _bwd_rays
+ * are dr_march_fwd's. origins, dirs [N][3] f32 (UNIT directions, used as given), the ray buffers of dr_bundle_setup and N as
+ * above; the volume's arguments are dr_march_rgba_fwd's (element strides sx, sy, sz and the channel stride sc; one volume per
+ * call, no view stride; sc == 1 with every other stride a multiple of 4 and a 16-B (f32) / 8-B (f16) aligned pointer fetches a
+ * voxel with one load, same bits). No table, no light, no shading.
+ * dr_march_rgba_bundle_fwd: out_rgba [N][4] and steps [N] (nullable) as dr_march_rgba_fwd: the rays of a dr_ray_setup view with
+ * its camera repeated as the origins give that view's image and steps bit for bit.
+ * dr_march_rgba_bundle_bwd ACCUMULATES d_vol (f32; element strides dsx, dsy, dsz and channel stride dsc; caller zeroes); d_vol
+ * NULL returns 0 before any HIP call. NaN propagates as in the plain kernels.
+ * dr_march_rgba_bundle_bwd_rays writes d_origins and d_dirs [N][3] f32 (overwritten), as dr_march_bundle_bwd_rays does: the
+ * frozen branches are those of dr_march_rgba_bwd_cam (n, `steps` of dr_march_rgba_bundle_fwd, the jitter draw, the slab faces,
+ * the cells) and the t_near clamp. t_near, jitter_seed and ray_base must be those of the dr_bundle_setup call that made the
+ * buffers. A ray with n <= 1 gets zeros; a NaN ray gets zeros and infinities are clamped to +-1e30 (D5).
+ * Invalid arguments (null required pointers, N <= 0, N >= 2^31, a volume extent < 2, max_samples < 1, a NaN t_near, an unknown
+ * dtype, a non-finite or non-positive sampling rate) return DR_EINVAL before any HIP call; a library linked without these
+ * kernels returns DR_EUNSUPPORTED. */
+int dr_march_rgba_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                             int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                             const float *origins, const float *dirs, const float *entry, const float *exit_,
+                             const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                             float *out_rgba, int32_t *steps, void *stream);
+int dr_march_rgba_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                             int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                             const float *origins, const float *dirs, const float *entry, const float *exit_,
+                             const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                             const float *grad_out, const float *out_rgba,
+                             float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, int64_t dsc, void *stream);
+int dr_march_rgba_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                                  int64_t sx, int64_t sy, int64_t sz, int64_t sc,
+                                  const float *origins, const float *dirs, const float *entry, const float *exit_,
+                                  const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                                  const int32_t *steps, float t_near, uint32_t jitter_seed, uint32_t ray_base,
+                                  const float *grad_out, const float *out_rgba,
+                                  float *d_origins, float *d_dirs, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
