@@ -117,6 +117,12 @@ SIGNATURES = {
                                       _P, _L, _L, _L, _L, _P]),
     "dr_march_rgba_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _L, _I, _F,
                                            _P, _F, _U, _U, _P, _P, _P, _P, _P]),
+    # the depth moments of a ray bundle: exactly the argument lists of the D19 entries
+    "dr_march_depth_bundle_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P]),
+    "dr_march_depth_bundle_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P,
+                                       _P, _L, _L, _L, _P, _P]),
+    "dr_march_depth_bundle_bwd_rays": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F,
+                                            _P, _F, _U, _U, _P, _P, _P, _P, _P]),
     "dr_project_fwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dr_project_bwd": (_I, [_P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                             _P, _L, _L, _L, _L, _I, _P]),

@@ -1046,6 +1046,53 @@ int dr_march_rgba_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY
     return launch_on(vol, launch_rgba_bundle_ray_grad, a, q, b, (hipStream_t)stream);
 }
 
+// the three depth bundle marches: fill_bundle's arguments and checks as they are; out_rgba holds the moments
+int dr_march_depth_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                              const float *tf, int R, const float *origins, const float *dirs, const float *entry,
+                              const float *exit_, const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                              float *out_rgba, int32_t *steps, void *stream) {
+    MarchArgs a;
+    BundleArgs b;
+    const int rc = fill_bundle(a, b, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, tf, R, origins, dirs, entry, exit_, nsamp, N,
+                               max_samples, sampling_rate);
+    if (rc) return rc;
+    if (!out_rgba) return DR_EINVAL;
+    a.out = out_rgba; a.steps = steps;
+    return launch_on(vol, launch_march_depth_bundle_fwd, a, b, (hipStream_t)stream);
+}
+
+int dr_march_depth_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                              const float *tf, int R, const float *origins, const float *dirs, const float *entry,
+                              const float *exit_, const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                              const float *grad_out, const float *out_rgba, float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz,
+                              float *d_tf, void *stream) {
+    MarchArgs a;
+    BundleArgs b;
+    int rc = fill_bundle(a, b, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, tf, R, origins, dirs, entry, exit_, nsamp, N, max_samples,
+                         sampling_rate);
+    if (rc) return rc;
+    rc = fill_bwd(a, grad_out, out_rgba, d_vol, dsx, dsy, dsz, 0, d_tf, 0);
+    if (rc) return rc;
+    if (!d_vol && !d_tf) return 0;  // nothing requested
+    return launch_on(vol, launch_march_depth_bundle_bwd, a, b, (hipStream_t)stream);
+}
+
+int dr_march_depth_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ, int64_t sx, int64_t sy, int64_t sz,
+                                   const float *tf, int R, const float *origins, const float *dirs, const float *entry,
+                                   const float *exit_, const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                                   const int32_t *steps, float t_near, uint32_t jitter_seed, uint32_t ray_base,
+                                   const float *grad_out, const float *out_rgba, float *d_origins, float *d_dirs, void *stream) {
+    MarchArgs a;
+    BundleArgs b;
+    const int rc = fill_bundle(a, b, vol, vol_dtype, VX, VY, VZ, sx, sy, sz, tf, R, origins, dirs, entry, exit_, nsamp, N,
+                               max_samples, sampling_rate, t_near);
+    if (rc) return rc;
+    if (!steps || !grad_out || !out_rgba || !d_origins || !d_dirs) return DR_EINVAL;
+    a.grad_out = grad_out; a.out_fwd = out_rgba;
+    b.steps = steps; b.jitter_seed = jitter_seed; b.ray_base = ray_base; b.d_origins = d_origins; b.d_dirs = d_dirs;
+    return launch_on(vol, launch_depth_bundle_ray_grad, a, b, (hipStream_t)stream);
+}
+
 int dr_tf_momentum_step(float *tf, const float *d_tf, float *momentum, int n, float lr, float gamma, float max_grad,
                         void *stream) {
     if (!tf || !d_tf || !momentum || n <= 0 || !(max_grad >= 0.0f)) return DR_EINVAL;

@@ -225,6 +225,14 @@ __attribute__((weak)) int launch_march_rgba_bundle_fwd(const MarchArgs &a, const
 __attribute__((weak)) int launch_march_rgba_bundle_bwd(const MarchArgs &a, const RgbaArgs &q, const BundleArgs &b, hipStream_t stream);
 __attribute__((weak)) int launch_rgba_bundle_ray_grad(const MarchArgs &a, const RgbaArgs &q, const BundleArgs &b, hipStream_t stream);
 
+// The depth march over a bundle of rays (march_depth_bundle.hip): dr_march_depth_bundle_fwd / _bwd / _bwd_rays take
+// the bundle's MarchArgs and BundleArgs exactly as launch_march_bundle_fwd / _bwd / launch_bundle_ray_grad do; `out` holds the
+// moments [N][4] = (M1, M2, 0, A), and only the alpha column of d_tf is written
+// weak, as launch_camera_grad: capi.o must load in a library linked without march_depth_bundle.o
+__attribute__((weak)) int launch_march_depth_bundle_fwd(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
+__attribute__((weak)) int launch_march_depth_bundle_bwd(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
+__attribute__((weak)) int launch_depth_bundle_ray_grad(const MarchArgs &a, const BundleArgs &b, hipStream_t stream);
+
 // Loss / optimiser epilogue (epilogue.hip)
 hipError_t launch_mse_loss_grad(const float *out, const float *ref, int64_t n, float inv_norm, float *grad,
                                 double *loss, hipStream_t stream);

@@ -9,52 +9,12 @@
 // The camera gradient is the third kernel: D8's four per-ray sums (camera_grad.hip) without lighting terms and with one new
 // direct term, because t_s is in the integrand itself; dr_camera.h's once-per-ray tails and reductions.
 #include "dr_camera.h"
-#include "dr_tile.h"
+#include "dr_depth.h"
 
 namespace dr {
 
 template <typename VT>
 struct DepthParams : RayParams<VT> {};
-
-// t_s = mix(t0, exit, s/(n-1)): sample_pos's own statements (the same bits as the t it multiplies the direction with)
-__device__ __forceinline__ float sample_t(const RayGeom &rg, int s, float &f) {
-    f = (float)s / (float)(rg.n - 1);
-    return mixf(rg.t0, rg.exit_, f);
-}
-
-// Composite (dr_device.h) for the moments: the same fma shape, A the same statement
-struct CompositeDepth {
-    float M1 = 0.f, M2 = 0.f, A = 0.f;
-    // composites one sample at distance t; returns T = 1 - A in front of it
-    __device__ __forceinline__ float add(float t, float op) {
-        const float T = 1.0f - A;
-        M1 = fmaf(T, t * op, M1);
-        M2 = fmaf(T, (t * t) * op, M2);
-        A = fmaf(T, op, A);
-        return T;
-    }
-    __device__ __forceinline__ float4 pixel() const { return make_float4(M1, M2, 0.0f, A); }
-    // what the samples after this prefix contribute to the loss, over the three live channels (go.z is never read)
-    __device__ __forceinline__ float suffix(float4 go, float4 of) const {
-        return (go.x * (of.x - M1) + go.y * (of.y - M2)) + go.w * (of.w - A);
-    }
-};
-
-// samples of a ray (n <= 1: none, H6)
-__device__ __forceinline__ int depth_samples(int n, int S) { return n > 1 ? (n < S ? n : S) : 0; }
-
-// The adjoint of one composited sample: op_bar = T q - suffix / (1 - op) (0 suffix for the last live sample), q = g.x t + g.y t^2
-// + g.w, and a_bar = op_bar d op / d a in sample_adjoint's expression. The colour adjoints are 0.
-__device__ __forceinline__ float depth_alpha_adjoint(const Sample &sm, float t, float T, float suffix, bool last, float4 go,
-                                                     float inv_sr) {
-    const float qs = (go.x * t + go.y * (t * t)) + go.w;
-    const float op_bar = T * qs - (last ? 0.0f : suffix / (1.0f - sm.op));
-    return op_bar * ((inv_sr == 1.0f) ? 1.0f : inv_sr * powf(1.0f - sm.a, inv_sr - 1.0f));
-}
-// ... and of its intensity tap, from the alpha slope of the two texels (intensity_adjoint with r_bar = g_bar = b_bar = 0)
-__device__ __forceinline__ float depth_intensity_adjoint(const Sample &sm, float a0, float a1, float a_bar, float tf_len) {
-    return (0.0f < sm.xtf) ? ((a1 - a0) * a_bar) * tf_len : 0.0f;
-}
 
 template <typename VT, bool TF_LDS>
 __global__ __launch_bounds__(256) void march_depth_fwd_kernel(DepthParams<VT> P) {

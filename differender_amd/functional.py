@@ -875,6 +875,49 @@ def march_bundle_bwd_rays(vol, tf, origins, dirs, entry, exit_, n, steps, max_sa
     return d_origins, d_dirs
 
 
+def march_depth_bundle_fwd(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate, want_steps=True):
+    """The ray-depth moments of a bundle's rays (dr_march_depth_bundle_fwd): march_depth_fwd's samples with the
+    ray's origin in the camera's place. Returns out (N, 4) = (M1, M2, 0, A), the distances measured from each ray's origin along
+    its unit direction, and steps (N,) int32 (or None): for a pinhole view's rays the bits of march_depth_fwd, and on any
+    bundle A and steps are march_bundle_fwd's."""
+    origins, dirs, n_rays, head = _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    out = torch.empty((n_rays, 4), dtype=torch.float32, device=vol.device)
+    steps = torch.empty((n_rays,), dtype=torch.int32, device=vol.device) if want_steps else None
+    _call("dr_march_depth_bundle_fwd", vol.device, *head, out.data_ptr(), _ptr(steps))
+    return out, steps
+
+
+def march_depth_bundle_bwd(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate, grad_out, out, want_vol=True,
+                           want_tf=True):
+    """Adjoint of march_depth_bundle_fwd w.r.t. vol and tf (dr_march_depth_bundle_bwd). Returns (d_vol, d_tf), either None when
+    not wanted. Only the alpha column of d_tf is non-zero; channel 2 of grad_out is not used. NaN propagates (the plain kernels'
+    convention: the caller applies nan_to_num, as depth.RayBundleDepthRaycaster does)."""
+    origins, dirs, n_rays, head = _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    grad_out, out = _bwd_images(grad_out, out)
+    if not (want_vol or want_tf):
+        return None, None
+    d_vol, dv = _d_vol(vol, want_vol)
+    d_tf, dt = _d_tf(tf, want_tf, 3)
+    _call("dr_march_depth_bundle_bwd", vol.device, *head, grad_out.data_ptr(), out.data_ptr(), *dv[:4], dt[0])
+    return d_vol, d_tf
+
+
+def march_depth_bundle_bwd_rays(vol, tf, origins, dirs, entry, exit_, n, steps, max_samples, sampling_rate, grad_out, out,
+                                t_near=None, jitter_seed=0, ray_base=0):
+    """Gradient of march_depth_bundle_fwd w.r.t. every ray's origin and direction (dr_march_depth_bundle_bwd_rays, DESIGN.md
+    D22): the buffers, t_near, jitter_seed and ray_base those of bundle_setup, `steps` and `out` those of march_depth_bundle_fwd.
+    Returns d_origins, d_dirs (N, 3) float32 -- d_dirs w.r.t. the direction as a free 3-vector with the sample distances the
+    march's own parameter (no radial term). A NaN ray gets zeros (D5)."""
+    origins, dirs, n_rays, head = _bundle_head(vol, tf, origins, dirs, entry, exit_, n, max_samples, sampling_rate)
+    grad_out, out = _bwd_images(grad_out, out)
+    steps = steps.to(torch.int32).contiguous()
+    d_origins = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
+    d_dirs = torch.empty((n_rays, 3), dtype=torch.float32, device=vol.device)
+    _call("dr_march_depth_bundle_bwd_rays", vol.device, *head, steps.data_ptr(), _t_near(t_near), int(jitter_seed) & 0xFFFFFFFF,
+          int(ray_base) & 0xFFFFFFFF, grad_out.data_ptr(), out.data_ptr(), d_origins.data_ptr(), d_dirs.data_ptr())
+    return d_origins, d_dirs
+
+
 def _rgba_bundle_head(vol4, origins, dirs, entry, exit_, n, max_samples, sampling_rate):
     """What the three RGBA bundle marches start with -> (origins, dirs, N, their C-ABI arguments up to sampling_rate): one RGBA
     volume (4, VX, VY, VZ), float32 or float16, with any strides."""

@@ -742,6 +742,48 @@ int dr_march_rgba_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY
                                   const float *grad_out, const float *out_rgba,
                                   float *d_origins, float *d_dirs, void *stream);
 
+/* Ray-depth moments of the differentiable 1-D TF march over an arbitrary bundle of rays: dr_march_depth_fwd and
+ * its backwards with a ray as an input, as dr_march_bundle_fwd / _bwd / _bwd_rays are dr_march_fwd's, and with exactly their
+ * argument lists. origins, dirs [N][3] f32 (UNIT directions, used as given), the ray buffers of dr_bundle_setup, N, the volume
+ * (f32 or f16, any element strides) and the table [R][4] as above; one volume and one table per call. No light, no shading: only
+ * the table's alpha column is read. All arithmetic is float32.
+ * dr_march_depth_bundle_fwd: out_rgba [N][4] holds the moments (M1, M2, 0, A) = (sum w_s t_s, sum w_s t_s^2, 0, sum w_s),
+ * w_s = T_s op_s, where t_s is the march's own parameter mix(t0, exit, s / (n - 1)): the distance of sample s from the ray's origin
+ * along its unit direction. steps [N] is nullable. The rays of a dr_ray_setup view with its camera repeated as the origins give
+ * dr_march_depth_fwd's moments and steps bit for bit; on any bundle A and steps are dr_march_bundle_fwd's alpha channel and steps.
+ * With t_near = -INFINITY an origin inside the box collects negative distances behind it; t_near = 0 makes M1 / A a range.
+ * dr_march_depth_bundle_bwd ACCUMULATES d_vol (element strides dsx, dsy, dsz) and the ALPHA column of d_tf [R][4] (caller zeroes;
+ * the colour columns are never written); either may be NULL, both NULL returns 0 before any HIP call. grad_out [N][4]: its third
+ * channel is never read. NaN propagates as in the plain kernels.
+ * dr_march_depth_bundle_bwd_rays writes d_origins and d_dirs [N][3] f32 (overwritten), as dr_march_bundle_bwd_rays does: the
+ * derivative w.r.t. the origin and w.r.t. the direction as a free 3-vector WITH t_s THE MARCH PARAMETER -- not the dot product
+ * (pos - origin).dir, which for a free direction is t_s |dir|^2 and carries an extra radial term; through a caller that
+ * normalises the directions the two agree. The frozen branches are those of dr_march_depth_bwd_cam (n, `steps` of
+ * dr_march_depth_bundle_fwd, the jitter draw, the slab faces, the cells, 0 < x_tf) and the t_near clamp. t_near, jitter_seed and
+ * ray_base must be those of the dr_bundle_setup call that made the buffers. A ray with n <= 1 gets zeros; a NaN ray gets zeros
+ * and infinities are clamped to +-1e30 (D5).
+ * Invalid arguments (null required pointers, N <= 0, N >= 2^31, a volume extent < 2, R < 1, max_samples < 1, a NaN t_near, an
+ * unknown dtype, a non-finite or non-positive sampling rate) return DR_EINVAL before any HIP call; a library linked without
+ * these kernels returns DR_EUNSUPPORTED. */
+int dr_march_depth_bundle_fwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                              int64_t sx, int64_t sy, int64_t sz, const float *tf, int R,
+                              const float *origins, const float *dirs, const float *entry, const float *exit_,
+                              const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                              float *out_rgba, int32_t *steps, void *stream);
+int dr_march_depth_bundle_bwd(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                              int64_t sx, int64_t sy, int64_t sz, const float *tf, int R,
+                              const float *origins, const float *dirs, const float *entry, const float *exit_,
+                              const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                              const float *grad_out, const float *out_rgba,
+                              float *d_vol, int64_t dsx, int64_t dsy, int64_t dsz, float *d_tf, void *stream);
+int dr_march_depth_bundle_bwd_rays(const void *vol, int vol_dtype, int VX, int VY, int VZ,
+                                   int64_t sx, int64_t sy, int64_t sz, const float *tf, int R,
+                                   const float *origins, const float *dirs, const float *entry, const float *exit_,
+                                   const int32_t *nsamp, int64_t N, int max_samples, float sampling_rate,
+                                   const int32_t *steps, float t_near, uint32_t jitter_seed, uint32_t ray_base,
+                                   const float *grad_out, const float *out_rgba,
+                                   float *d_origins, float *d_dirs, void *stream);
+
 /* Momentum gradient step on the transfer function, in place (apply_grad, EX.py:375-381):
  *   momentum = gamma*momentum + lr*clamp(d_tf, -max_grad, max_grad);  tf = max(tf - momentum, 0)
  *   tf, d_tf, momentum [n] f32 (n = R*4). */
